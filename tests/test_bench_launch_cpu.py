@@ -27,6 +27,53 @@ def test_launch_argv():
     assert os.path.basename(argv[-7]) == "bench.py"
 
 
+def test_plain_run_is_the_headline_and_full_is_opt_in():
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and a.full is False and a.repeats is None and a.dump_outputs is None
+    b = bench.parse_args(["--full", "--dump-outputs", "outs", "--repeats", "3"])
+    assert b.full is True and b.dump_outputs == "outs" and b.repeats == 3
+    assert 1 <= bench.usable_cores() <= len(os.sched_getaffinity(0))
+
+
+def test_a_tree_the_benchmark_may_not_write_is_run_as_built(tmp_path, monkeypatch):
+    """bench.ensure_library: the library build() made is used without the build lock when nothing is newer, and also when a
+    source is newer but the package directory is read-only (a checkout built by another user); it is built when it is missing
+    or stale in a writable tree."""
+    import types
+    sys.path.insert(0, ROOT)
+    import bench
+    lib = tmp_path / "libcfear_hip.so"
+    calls = []
+    fake = types.SimpleNamespace(HERE=str(tmp_path), LIB=str(lib), stale=False)
+    fake.needs_build = lambda: fake.stale
+    fake.build = lambda: calls.append(1) or str(lib)
+    assert bench.ensure_library(fake) == str(lib) and calls == [1]  # missing: built
+    lib.write_bytes(b"")
+    calls.clear()
+    assert bench.ensure_library(fake) == str(lib) and calls == []  # up to date: no lock, no build
+    fake.stale = True
+    assert bench.ensure_library(fake) == str(lib) and calls == [1]  # stale, writable: rebuilt
+    calls.clear()
+    monkeypatch.setattr(bench.os, "access", lambda p, m: False)
+    assert bench.ensure_library(fake) == str(lib) and calls == []  # stale, read-only: run as built
+
+
+def test_synthetic_stream_cache_is_one_this_user_may_write(tmp_path, monkeypatch):
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.delenv("CFEAR_SYNTH_CACHE", raising=False)
+    shared = tmp_path / "cache"
+    assert bench.synth_cache_dir(str(shared)) == str(shared)  # not there yet: created by this run
+    shared.mkdir()
+    assert bench.synth_cache_dir(str(shared)) == str(shared)
+    monkeypatch.setattr(bench.os, "access", lambda p, m: False)  # another user's folder
+    assert bench.synth_cache_dir(str(shared)) == "%s_%d" % (shared, os.getuid())
+    monkeypatch.setenv("CFEAR_SYNTH_CACHE", str(tmp_path / "mine"))
+    assert bench.synth_cache_dir(str(shared)) == str(tmp_path / "mine")
+
+
 def test_gpus_2_spawns_two_ranks_and_reduces():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "1", "--sequences", "7",
                           "--dry-run"], cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=300)

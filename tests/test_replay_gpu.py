@@ -98,6 +98,42 @@ def test_bench_eight_ranks_through_the_launcher_on_one_gpu():
     assert r["state"]["replicas_bit_identical"] is True and r["config"]["keyframes_at_first_timed_step_min"] == 4
 
 
+def test_bench_plain_run_times_one_region_and_dumps_its_outputs(tmp_path):
+    """`python bench.py --steps K --dump-outputs DIR` without --full: ONE timed region of exactly K steps, the headline fields only,
+    and the outputs of the last timed step as float64 .npy files - identical in a second run with the same arguments."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    runs = []
+    for i in range(2):
+        d = tmp_path / ("out%d" % i)
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--sequences", "64",
+                              "--unique", "2", "--dump-outputs", str(d)], cwd=root, env=env, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        r = json.loads(lines[0])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in r
+        assert r["steps"] == 3 and r["repeats"]["count"] == 1 and r["config"]["full"] is False
+        assert abs(r["value"] - 64 * 3 / (r["ms_per_step"] * 3 / 1e3)) < 1e-6 * r["value"]
+        for leg in ("isolated", "reversal", "stream_mode", "parity", "single_sequence", "presets", "cpu_baseline"):
+            assert leg not in r, leg
+        files = {f: np.load(d / f) for f in sorted(os.listdir(d))}
+        assert set(files) == {"poses.npy", "covariances.npy", "summary_sample.npy"}
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 << 20
+        assert all(a.dtype == np.float64 for a in files.values())
+        assert np.all(np.isfinite(files["poses.npy"])) and np.all(np.isfinite(files["covariances.npy"]))
+        assert files["poses.npy"].shape == (64, 3) and files["covariances.npy"].shape == (64, 6, 6) and files["summary_sample.npy"].shape == (64, 6)
+        assert np.array_equal(files["poses.npy"][0], r["state"]["pose_seq0"])
+        runs.append(files)
+    for f in runs[0]:
+        assert np.array_equal(runs[0][f], runs[1][f]), f
+
+
 @pytest.mark.parametrize("B,persistent_max", [(1, 256), (1, 0), (3, 256), (3, 0)])
 def test_replay_host_equals_step_host(B, persistent_max):
     """cfear_odometry_replay_host (chunks copied and filtered ahead on a second stream; a persistent workgroup per sequence or the

@@ -13,7 +13,7 @@ echo "== instructions per row (uniform, world), production then pair"
 bash tools/pmc_k1_valu.sh "7,6" 2>&1 | tail -3
 CFEAR_K1_PAIR=1 bash tools/pmc_k1_valu.sh "7,6" 2>&1 | tail -3
 echo "== the step (bench.py --no-presets ...), production then pair"
-for pr in 0 1; do CFEAR_K1_PAIR=$pr timeout 600 python bench.py --no-cpu-baseline --no-presets --stream-steps 0 --single-sequence-sweeps 0 --no-isolated 2>/dev/null | python -c "
+for pr in 0 1; do CFEAR_K1_PAIR=$pr timeout 600 python bench.py --full --no-cpu-baseline --no-presets --stream-steps 0 --single-sequence-sweeps 0 --no-isolated 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('pair=$pr scans/s', round(d['value']), 'ms/step', round(d['ms_per_step'],4), 'filter us', round(d['kernels']['kstrongest_launch_us'],1), 'frac', round(d['roofline']['frac'],3))"; done
 } > $O/r06_k1_pair.txt 2>&1
