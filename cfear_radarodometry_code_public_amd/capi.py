@@ -75,7 +75,8 @@ EXPORTS = [
     "cfear_scan_from_cells", "cfear_scan_release", "cfear_scan_size", "cfear_scan_download_cells", "cfear_scan_closest",
     "cfear_register", "cfear_register_soft", "cfear_get_cost", "cfear_cov_by_sampling", "cfear_odometry_create", "cfear_odometry_destroy", "cfear_odometry_reset",
     "cfear_odometry_step_device", "cfear_odometry_step_cloud_device", "cfear_odometry_step_host", "cfear_odometry_poses",
-    "cfear_odometry_replay_host", "cfear_odometry_replay_device", "cfear_host_alloc", "cfear_host_free",
+    "cfear_odometry_replay_host", "cfear_odometry_replay_device", "cfear_odometry_replay_host_cov", "cfear_odometry_replay_device_cov",
+    "cfear_odometry_set_cov_sampling", "cfear_odometry_cov_samples", "cfear_host_alloc", "cfear_host_free",
     "cfear_odometry_covariances", "cfear_odometry_status", "cfear_odometry_summary", "cfear_odometry_profile", "cfear_odometry_profile_read", "cfear_odometry_profile_read_stages", "cfear_odometry_phase_times", "cfear_time_kstrongest",
 ]
 
@@ -146,6 +147,10 @@ def lib():
         "cfear_odometry_status": (C.c_int, [vp, vp, i32p]),
         "cfear_odometry_replay_host": (C.c_int, [vp, vp, u8p, C.c_int, vp]),
         "cfear_odometry_replay_device": (C.c_int, [vp, vp, u8p, C.c_int, vp]),
+        "cfear_odometry_replay_host_cov": (C.c_int, [vp, vp, u8p, C.c_int, vp, vp]),
+        "cfear_odometry_replay_device_cov": (C.c_int, [vp, vp, u8p, C.c_int, vp, vp]),
+        "cfear_odometry_set_cov_sampling": (C.c_int, [vp, vp, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double]),
+        "cfear_odometry_cov_samples": (C.c_int, [vp, vp, C.c_int, f64p, vp]),
         "cfear_host_alloc": (C.c_int, [vp, C.c_size_t, C.POINTER(vp)]),
         "cfear_host_free": (None, [vp, vp]),
         "cfear_odometry_summary": (C.c_int, [vp, vp, C.c_int, C.POINTER(RegSummary), C.POINTER(C.c_int),
@@ -524,24 +529,51 @@ class Odometry:
         self._ctx._check(self._ctx._L.cfear_odometry_step_host(self._ctx._h, self._h, polar.ctypes.data),
                          "cfear_odometry_step_host")
 
-    def replay_host(self, frames, records=True):
+    def replay_host(self, frames, records=True, covariances=False):
         """frames: uint8 [n, B, A, R] (or [n, A, R] for one sequence), e.g. a view of Context.pinned(). Runs the n sweeps with
-        no host round trip in between; -> structured array [n, B] of SWEEP_RECORD_DTYPE (or None)."""
+        no host round trip in between; -> structured array [n, B] of SWEEP_RECORD_DTYPE (or None). covariances=True: -> (records,
+        [n, B, 6, 6] cov_current after every sweep) (cfear_odometry_replay_host_cov)."""
         frames = np.ascontiguousarray(frames, dtype=np.uint8)
         if frames.ndim == 3:
             frames = frames[:, None]
         assert frames.shape[1:] == (self.B, self._ctx.A, self._ctx.R), frames.shape
         n = frames.shape[0]
         rec = np.zeros((n, self.B), dtype=SWEEP_RECORD_DTYPE) if records else None
-        self._ctx._check(self._ctx._L.cfear_odometry_replay_host(self._ctx._h, self._h, frames.ctypes.data, n,
-                                                                 rec.ctypes.data if records else None), "cfear_odometry_replay_host")
-        return rec
+        if not covariances:
+            self._ctx._check(self._ctx._L.cfear_odometry_replay_host(self._ctx._h, self._h, frames.ctypes.data, n,
+                                                                     rec.ctypes.data if records else None), "cfear_odometry_replay_host")
+            return rec
+        cov = np.zeros((n, self.B, 36))
+        self._ctx._check(self._ctx._L.cfear_odometry_replay_host_cov(self._ctx._h, self._h, frames.ctypes.data, n, rec.ctypes.data if records else None,
+                                                                     cov.ctypes.data), "cfear_odometry_replay_host_cov")
+        return rec, cov.reshape(n, self.B, 6, 6)
 
-    def replay_device(self, d_frames, n_sweeps, d_records=None):
+    def replay_device(self, d_frames, n_sweeps, d_records=None, d_cov=None):
         """d_frames: device pointer / torch tensor of n_sweeps x B x A x R bytes; d_records: device buffer of n_sweeps x B x 80 bytes or
-        None. Asynchronous on the context stream."""
-        self._ctx._check(self._ctx._L.cfear_odometry_replay_device(self._ctx._h, self._h, _addr(d_frames), int(n_sweeps),
-                                                                   _addr(d_records) if d_records is not None else None), "cfear_odometry_replay_device")
+        None; d_cov: device buffer of n_sweeps x B x 36 doubles (cov_current after every sweep) or None. Asynchronous on the context stream."""
+        if d_cov is None:
+            self._ctx._check(self._ctx._L.cfear_odometry_replay_device(self._ctx._h, self._h, _addr(d_frames), int(n_sweeps),
+                                                                       _addr(d_records) if d_records is not None else None), "cfear_odometry_replay_device")
+            return
+        self._ctx._check(self._ctx._L.cfear_odometry_replay_device_cov(self._ctx._h, self._h, _addr(d_frames), int(n_sweeps),
+                                                                       _addr(d_records) if d_records is not None else None, _addr(d_cov)),
+                         "cfear_odometry_replay_device_cov")
+
+    def set_cov_sampling(self, enable=True, xy_range=0.4, yaw_range=0.0043625, samples_per_axis=3, covariance_scaler=4.0):
+        """estimate_cov_by_sampling and its companions (odometrykeyframefuser.h:104-110) for every sequence, from the next sweep on"""
+        self._ctx._check(self._ctx._L.cfear_odometry_set_cov_sampling(self._ctx._h, self._h, int(bool(enable)), float(xy_range), float(yaw_range),
+                                                                       int(samples_per_axis), float(covariance_scaler)), "cfear_odometry_set_cov_sampling")
+        if enable:
+            self._cov_m = int(samples_per_axis) ** 3
+
+    def cov_samples(self, sequence):
+        """the last sweep's sampled costs of one sequence (samples_per_axis^3, the reference's order) and whether the sampled
+        covariance was used -> (costs, sampled)"""
+        costs = np.zeros(getattr(self, "_cov_m", 1))
+        ok = C.c_int()
+        self._ctx._check(self._ctx._L.cfear_odometry_cov_samples(self._ctx._h, self._h, int(sequence), costs.ctypes.data, C.byref(ok)),
+                         "cfear_odometry_cov_samples")
+        return costs, bool(ok.value)
 
     def profile(self, enable):
         self._ctx._check(self._ctx._L.cfear_odometry_profile(self._ctx._h, self._h, int(enable)), "cfear_odometry_profile")

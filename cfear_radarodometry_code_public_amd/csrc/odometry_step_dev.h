@@ -52,6 +52,28 @@ struct SeqState {  // OdometryKeyframeFuser members (odometrykeyframefuser.h:203
   Aff2 kf_pose[MAX_SCANS];
 };
 
+// Cost-sampling covariance (estimate_cov_by_sampling, odometrykeyframefuser.cpp:202-208, 261-380) of the batched routes: what the
+// registration of a sweep used - its scans and poses before AddToReference may hand the oldest slot to the next sweep - written by
+// register_step_body when CovSampling::ctx is set, read by the sampling stage (cov_sampling_dev.h) before the next sweep's features run.
+struct CovSampleCtx {
+  int n;              // scans of the registration (keyframes + current); 0: nothing to sample this sweep (a sequence's first)
+  int itr;            // radar_reg->itr_ after Register: the sweep's outer iterations (selects the association radius of GetCost)
+  int num_residuals;  // of the registration's last problem (GetCovarianceScaler)
+  int sampled;        // cov_sampled_success of the last sampling (written by the sampling stage)
+  double final_cost;
+  int slot[MAX_SCANS];
+  double pose[3 * MAX_SCANS];  // the registration's parameter vectors after the solve: keyframes, then the registered pose (T_vek)
+};
+struct CovSampling {  // null ctx: off (the production kernels do exactly the work they did without the option)
+  CovSampleCtx* ctx;    // [B]
+  const double* pinv;   // [10][m] minimum-norm pseudo-inverse of the sample design (odometrykeyframefuser.cpp:325-337)
+  const double* offs;   // [m][3] sample offsets (x, y, yaw) in the reference's order (:294-296)
+  double* costs;        // [B][m] sampled costs of the last sampling
+  double* cov_out;      // optional [B][36]: cov_current after the sweep (cfear_odometry_replay_*_cov; set per sweep)
+  double scaler;        // cov_sampling_covariance_scaler
+  int m;                // samples_per_axis^3
+};
+
 struct OdoParams {
   FeatureParams fp;
   RegParams rp;
@@ -71,6 +93,7 @@ struct OdoParams {
   // seq0 + blockIdx.x), work[q] = what sequence q's registration of THIS sweep cost (evaluations x residual blocks + associations),
   // the key the next sweep's order is sorted by (null: not recorded)
   const int* order; unsigned* work;
+  CovSampling cs;  // cost-sampling covariance and / or per-sweep covariances (cs.ctx / cs.cov_out null: neither)
   int* flags;  // word 0 for the odometry object, word 1 + q for sequence q: bit 0 = some scan had more cells than its block holds, bit 1 = some cloud had more points
                // than the object is sized for (both CFEAR_ERR_CAPACITY); null: cannot happen
 };
@@ -227,6 +250,7 @@ __device__ __forceinline__ void register_step_body(unsigned char* lds /* RegLds:
   __syncthreads();  // every thread has read the state before thread 0 rewrites it
   if (nkf == 0) {  // :171-177
     if (tid == 0) {
+      if (OP.cs.ctx) OP.cs.ctx[q].n = 0;  // no keyframes: no sampling
       st->ring[0] = cur_slot; st->kf_pose[0] = aff_identity(); st->nkf = 1; st->free_slot = (cur_slot + 1) % nslots;
       st->frames++; st->last_slot = cur_slot;
       if (OP.work) OP.work[q] = 0u;
@@ -266,6 +290,13 @@ __device__ __forceinline__ void register_step_body(unsigned char* lds /* RegLds:
   __syncthreads();
   if (TIMED) pt.mark();
   if (tid == 0) {
+    if (OP.cs.ctx) {  // estimate_cov_by_sampling: the scans and poses of this registration, before the sanity check and AddToReference (:202-208)
+      CovSampleCtx* c = OP.cs.ctx + q;
+      c->n = ns; c->itr = sum->outer_iterations; c->num_residuals = sum->num_residuals; c->final_cost = sum->final_cost;
+      for (int i = 0; i < nkf; i++) c->slot[i] = st->ring[i];
+      c->slot[ns - 1] = cur_slot;
+      for (int i = 0; i < 3 * ns; i++) c->pose[i] = poses[i];
+    }
     Aff2 Tcurrent = aff_from_xyt(poses[3 * (ns - 1)], poses[3 * (ns - 1) + 1], poses[3 * (ns - 1) + 2]);  // :195
     const Aff2 Tpi = aff_inv(T_prev);
     const Aff2 Tmot_current = aff_mul(Tpi, Tcurrent);

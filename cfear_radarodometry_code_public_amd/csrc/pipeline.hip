@@ -18,6 +18,7 @@
 
 #include "common.h"
 #include "odometry_step_dev.h"
+#include "cov_sampling_dev.h"
 
 namespace {
 
@@ -161,6 +162,12 @@ __global__ __launch_bounds__(BLOCK_R, CFEAR_REG_MIN_WG) void register_step64_ker
                                                                                    cfear_reg_summary* summaries, double* poses_out) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[RegLds::total];
   register_step_body<TIMED, KCOST>(lds, OP.order ? OP.order[blockIdx.x] : OP.seq0 + (int)blockIdx.x, OP, states, scratch, cov_work, summaries, poses_out);
+}
+// estimate_cov_by_sampling of the batched step (cov_sampling_dev.h): one workgroup per sequence after the sweep's registration, on its stream
+template <bool GENERAL>
+__global__ __launch_bounds__(BLOCK_R, 2) void cov_sample_kernel(OdoParams OP, const BlockScratch* scratch, double* cov_work) {
+  __shared__ __attribute__((aligned(16))) unsigned char lds[RegLds::total];
+  cov_sample_body<GENERAL>(lds, OP.seq0 + (int)blockIdx.x, OP, scratch, cov_work);
 }
 // the same stage from clouds on the device (filter_type CA-CFAR / cfear_odometry_step_cloud_device)
 __global__ __launch_bounds__(BLOCK_F, 4) void features_cloud_step_kernel(const float* xyi_all, int cap, const int* counts, OdoParams OP,
@@ -403,6 +410,15 @@ struct cfear_odometry {
   size_t pool_used = 0;
   std::vector<hipEvent_t> filter_events;  // 2 per profiled filter launch (borrowed from the pool)
   std::vector<hipEvent_t> stage_events;   // 3 per profiled step: before features, between, after registration
+  // estimate_cov_by_sampling (cfear_odometry_set_cov_sampling): the sampling stage runs after every registration while cov_on
+  bool cov_on = false;
+  int cov_m = 0, cov_m_cap = 0;           // samples per sweep (samples_per_axis^3); what d_cov_design / d_cov_costs are sized for
+  double cov_scaler = 4.0;
+  CovSampleCtx* d_cov_ctx = nullptr;      // [B] what each registration used (register_step_body)
+  double* d_cov_design = nullptr;         // [10][m] pseudo-inverse of the sample design, then [m][3] sample offsets
+  double* d_cov_costs = nullptr;          // [B][m] sampled costs of the last sweep
+  double* d_cov_seq = nullptr;            // cfear_odometry_replay_host_cov: cov_current of every sweep ([n][B][36])
+  size_t cov_seq_cap = 0;
 };
 // a timing event from the pool, recorded on `st`
 static int odo_timed_event(cfear_ctx* ctx, cfear_odometry* o, std::vector<hipEvent_t>& list, hipStream_t st) {
@@ -463,12 +479,17 @@ static OdoParams odo_params(const cfear_ctx* ctx, const cfear_odometry* o) {
   OP.records = nullptr;
   OP.flags = o->d_flags;
   OP.order = nullptr; OP.work = o->d_work;
+  OP.cs.ctx = nullptr; OP.cs.pinv = nullptr; OP.cs.offs = nullptr; OP.cs.costs = nullptr; OP.cs.cov_out = nullptr; OP.cs.scaler = 0; OP.cs.m = 0;
+  if (o->cov_on) {
+    OP.cs.ctx = o->d_cov_ctx; OP.cs.pinv = o->d_cov_design; OP.cs.offs = o->d_cov_design + 10 * (size_t)o->cov_m;
+    OP.cs.costs = o->d_cov_costs; OP.cs.scaler = o->cov_scaler; OP.cs.m = o->cov_m;
+  }
   return OP;
 }
 // features -> registration of one sweep of every sequence on `st`, from the filter's slots
 // the registration step kernel of a sweep. register_step.hip holds the production instantiations (one per cost metric, registrations of
 // up to CFEAR_STEP_SMALL_SCANS scans: a bigger LDS match array); a larger submap runs the instantiation of this file (any cost, 64 scans)
-static void launch_register_step(const OdoParams& P_in, int count, hipStream_t st, cfear_odometry* o) {
+static void launch_register_kernel(const OdoParams& P_in, int count, hipStream_t st, cfear_odometry* o) {
   OdoParams P = P_in;
   if (o->d_order && count == o->B && P.seq0 == 0) {  // (whole-batch launches only: the sub-batches of the overlap mode keep their ranges)
     if (o->order_ready) {
@@ -500,6 +521,16 @@ static void launch_register_step(const OdoParams& P_in, int count, hipStream_t s
   else if (P.rp.cost == CFEAR_COST_P2D) CFEAR_LAUNCH_REG(false, CFEAR_COST_P2D);
   else CFEAR_LAUNCH_REG(false, CFEAR_COST_P2P);
 #undef CFEAR_LAUNCH_REG
+}
+// ... and behind it, on the same stream, the cost-sampling stage (estimate_cov_by_sampling) and / or the copy of every sequence's cov_current
+// (the replay's per-sweep covariances): before the next sweep's features kernel may reuse a slot the registration read
+static void launch_register_step(const OdoParams& P, int count, hipStream_t st, cfear_odometry* o) {
+  launch_register_kernel(P, count, st, o);
+  if (!P.cs.ctx && !P.cs.cov_out) return;
+  if (CFEAR_COV_SAMPLING_NAIVE || P.rp.nn_tie != 0)  // (cov_sample_general)
+    hipLaunchKernelGGL(cov_sample_kernel<true>, dim3(count), dim3(BLOCK_R), 0, st, P, o->d_scratch_hdr, o->d_cov_work);
+  else
+    hipLaunchKernelGGL(cov_sample_kernel<false>, dim3(count), dim3(BLOCK_R), 0, st, P, o->d_scratch_hdr, o->d_cov_work);
 }
 static void odo_launch_sweep(const cfear_ctx* ctx, cfear_odometry* o, const OdoParams& P, const uint32_t* d_slots, int seq_count, hipStream_t st) {
   if (P.phase_times)
@@ -1014,10 +1045,9 @@ namespace {
 // singular values above the rank threshold (Eigen's SVDBase::threshold(): diagSize = min(m, n) times epsilon, times sigma_max; numpy's lstsq
 // default is max(m, n) - with 27-125 samples 3-12 x higher, which would cut a weakly observed yaw direction Eigen keeps). Works on A itself - no normal
 // equations - so nothing is lost to squaring the condition number (the yaw column is ~1e-5 of the others).
-static void lstsq10_svd(int m, const double* A, const double* b, double c[10]) {
+static void jacobi10(int m, const double* A, std::vector<double>& W, double V[100], double sig[10], double* thr_out) {
   const int n = 10;
-  std::vector<double> W((size_t)m * n);
-  double V[100];
+  W.assign((size_t)m * n, 0.0);
   for (int i = 0; i < m * n; i++) W[i] = A[i];
   for (int i = 0; i < n; i++) for (int j = 0; j < n; j++) V[i * n + j] = (i == j) ? 1.0 : 0.0;
   for (int sweep = 0; sweep < 60; sweep++) {
@@ -1042,14 +1072,20 @@ static void lstsq10_svd(int m, const double* A, const double* b, double c[10]) {
       }
     if (!rotated) break;
   }
-  double sig[10], smax = 0;
+  double smax = 0;
   for (int j = 0; j < n; j++) {
     double q = 0;
     for (int i = 0; i < m; i++) q += W[(size_t)i * n + j] * W[(size_t)i * n + j];
     sig[j] = sqrt(q);
     if (sig[j] > smax) smax = sig[j];
   }
-  const double thr = (double)(m < n ? m : n) * 2.220446049250313e-16 * smax;
+  *thr_out = (double)(m < n ? m : n) * 2.220446049250313e-16 * smax;
+}
+static void lstsq10_svd(int m, const double* A, const double* b, double c[10]) {
+  const int n = 10;
+  std::vector<double> W;
+  double V[100], sig[10], thr;
+  jacobi10(m, A, W, V, sig, &thr);
   for (int k = 0; k < n; k++) c[k] = 0.0;
   for (int j = 0; j < n; j++) {
     if (!(sig[j] > thr)) continue;
@@ -1059,6 +1095,23 @@ static void lstsq10_svd(int m, const double* A, const double* b, double c[10]) {
     for (int k = 0; k < n; k++) c[k] += V[k * n + j] * q;
   }
 }
+// The same decomposition as the minimum-norm pseudo-inverse P (10 x m, row-major): c = P b for every b (the batched routes' sample design
+// is fixed by (xy_range, yaw_range, samples_per_axis), so the device fit is a 10 x m product). Same rank threshold as lstsq10_svd.
+static void pinv10_svd(int m, const double* A, double* P) {
+  const int n = 10;
+  std::vector<double> W;
+  double V[100], sig[10], thr;
+  jacobi10(m, A, W, V, sig, &thr);
+  for (size_t i = 0; i < (size_t)n * m; i++) P[i] = 0.0;
+  for (int j = 0; j < n; j++) {
+    if (!(sig[j] > thr)) continue;
+    const double s2 = sig[j] * sig[j];
+    for (int k = 0; k < n; k++) {
+      const double v = V[k * n + j];
+      for (int i = 0; i < m; i++) P[(size_t)k * m + i] += v * (W[(size_t)i * n + j] / s2);
+    }
+  }
+}
 static void linspace(double start, double end, int num, std::vector<double>& v) {  // odometrykeyframefuser.cpp:497-524
   v.clear();
   if (num <= 0) return;
@@ -1066,6 +1119,24 @@ static void linspace(double start, double end, int num, std::vector<double>& v) 
   const double delta = (end - start) / ((double)num - 1);
   for (int i = 0; i < num - 1; i++) v.push_back(start + delta * i);
   v.push_back(end);
+}
+// the reference's sample design (odometrykeyframefuser.cpp:277-336): offsets [m][3] (x, y, yaw) in its loop order (:294-296) and the
+// rows [m][10] of the least-squares quadratic
+static void cov_sample_design(double xy_range, double yaw_range, int steps, std::vector<double>& offs, std::vector<double>& A) {
+  std::vector<double> xs, ths;  // :277-290
+  linspace(-xy_range * 0.5, xy_range * 0.5, steps, xs);
+  linspace(-yaw_range * 0.5, yaw_range * 0.5, steps, ths);
+  const size_t m = (size_t)steps * steps * steps;
+  offs.assign(3 * m, 0.0); A.assign(10 * m, 0.0);
+  int k = 0;
+  for (int it = 0; it < steps; it++)  // the reference's loop order (:294-296), as cfear_cov_by_sampling
+    for (int ix = 0; ix < steps; ix++)
+      for (int iy = 0; iy < steps; iy++, k++) {
+        const double x = xs[ix], y = xs[iy], z = ths[it];
+        offs[3 * k] = x; offs[3 * k + 1] = y; offs[3 * k + 2] = z;
+        double* r = &A[10 * (size_t)k];
+        r[0] = x * x; r[1] = y * y; r[2] = z * z; r[3] = x * y; r[4] = y * z; r[5] = z * x; r[6] = x; r[7] = y; r[8] = z; r[9] = 1.0;  // :325-336
+      }
 }
 }  // namespace
 
@@ -1132,25 +1203,7 @@ int cfear_cov_by_sampling(cfear_ctx* ctx, cfear_scan* const* scans, int n, const
   if (sample_costs) memcpy(sample_costs, costs.data(), sizeof(double) * m);
   double c[10];
   lstsq10_svd(m, A.data(), costs.data(), c);
-  const double H[9] = {2 * c[0], c[3], c[5], c[3], 2 * c[1], c[4], c[5], c[4], 2 * c[2]};  // :340-343
-  // "all eigenvalues positive" (:355-358) of a symmetric matrix = positive definite = all leading principal minors positive
-  // (Sylvester); the inverse by cofactors, as Eigen's Matrix3d::inverse() (:363)
-  const double C00 = H[4] * H[8] - H[5] * H[7], C01 = H[5] * H[6] - H[3] * H[8], C02 = H[3] * H[7] - H[4] * H[6];
-  const double det = H[0] * C00 + H[1] * C01 + H[2] * C02;
-  const double minor2 = H[0] * H[4] - H[1] * H[3];
-  if (!(H[0] > 0.0 && minor2 > 0.0 && det > 0.0)) return CFEAR_OK;  // not convex: sampling not used for this scan
-  if (num_residuals - 3 == 0) return CFEAR_OK;                      // GetCovarianceScaler false (n_scan_normal.cpp:435-441)
-  const double score_scale = final_cost / (double)(num_residuals - 3);
-  const double id = 1.0 / det;
-  const double Hi[9] = {C00 * id, (H[2] * H[7] - H[1] * H[8]) * id, (H[1] * H[5] - H[2] * H[4]) * id,
-                        C01 * id, (H[0] * H[8] - H[2] * H[6]) * id, (H[2] * H[3] - H[0] * H[5]) * id,
-                        C02 * id, (H[1] * H[6] - H[0] * H[7]) * id, minor2 * id};
-  double C3[9];
-  for (int i = 0; i < 9; i++) C3[i] = 2.0 * Hi[i] * score_scale * covariance_scaler;  // :363
-  for (int i = 0; i < 36; i++) cov6[i] = (i % 7 == 0) ? 1.0 : 0.0;  // :366-373
-  cov6[0] = C3[0]; cov6[1] = C3[1]; cov6[6] = C3[3]; cov6[7] = C3[4];
-  cov6[35] = C3[8]; cov6[5] = C3[2]; cov6[11] = C3[5]; cov6[30] = C3[6]; cov6[31] = C3[7];
-  *success = 1;
+  if (cov_from_quadratic(c, final_cost, num_residuals, covariance_scaler, cov6)) *success = 1;  // :340-373
   return CFEAR_OK;
 }
 
@@ -1178,7 +1231,8 @@ void cfear_odometry_destroy(cfear_ctx* ctx, cfear_odometry* o) {
   void* ptrs[] = {o->d_scans, o->d_scan_ptrs, o->d_scratch, o->d_scratch_hdr, o->d_states, o->d_poses_work, o->d_cov_work,
                   o->d_summaries, o->d_poses_out, o->d_slots[0], o->d_slots[1], o->d_polar, o->d_phase_times,
                   o->rp_polar[0], o->rp_polar[1], o->rp_slots[0], o->rp_slots[1], o->d_records, o->d_flags, o->d_order, o->d_work,
-                  o->d_cloud, o->d_cloud_n, o->d_cfar_rows, o->rp_cloud[0], o->rp_cloud[1], o->rp_cloud_n[0], o->rp_cloud_n[1], o->rp_cfar_rows};
+                  o->d_cloud, o->d_cloud_n, o->d_cfar_rows, o->rp_cloud[0], o->rp_cloud[1], o->rp_cloud_n[0], o->rp_cloud_n[1], o->rp_cfar_rows,
+                  o->d_cov_ctx, o->d_cov_design, o->d_cov_costs, o->d_cov_seq};
   for (hipEvent_t e : {o->rp_filt[0], o->rp_filt[1], o->rp_used[0], o->rp_used[1], o->rp_in}) if (e) (void)hipEventDestroy(e);
   if (o->rp_stream) (void)hipStreamDestroy(o->rp_stream);
   for (void* p : ptrs) if (p) (void)hipFree(p);
@@ -1609,7 +1663,8 @@ static int replay_ensure(cfear_ctx* ctx, cfear_odometry* o, int chunk, bool stag
 
 // frames: n_sweeps x B x A x R bytes on the host (copied chunk by chunk into the staging buffers) or on the device (filtered where
 // they lie); d_records: where the per-sweep records go on the device (null: none)
-static int replay_impl_queue(cfear_ctx* ctx, cfear_odometry* o, const uint8_t* frames, bool on_device, int n_sweeps, cfear_sweep_record* d_records) {
+static int replay_impl_queue(cfear_ctx* ctx, cfear_odometry* o, const uint8_t* frames, bool on_device, int n_sweeps, cfear_sweep_record* d_records,
+                             double* d_cov6) {
   const size_t sweep = (size_t)o->B * ctx->A * ctx->R, slots = (size_t)o->B * o->cap_points;
   // chunk: enough sweeps for the filter to run at its streaming rate (>= ~16 k azimuth rows per launch) and for the copy of the
   // next chunk to hide behind the odometry kernels of this one, at most 256 MB per buffer (host route: of staged sweeps; device
@@ -1654,6 +1709,7 @@ static int replay_impl_queue(cfear_ctx* ctx, cfear_odometry* o, const uint8_t* f
     // odometrykeyframefuser.cpp:143-259 sweep after sweep. Few sequences: one persistent workgroup per sequence walks the whole
     // chunk (no launch in between; a workgroup needs a compute unit's LDS to itself, so this pays while the sequences fit the
     // chip at one per compute unit). Many sequences: the batched kernels, two launches per sweep, whose occupancy is what counts.
+    OP.cs.cov_out = d_cov6 ? d_cov6 + (size_t)t0 * o->B * 36 : nullptr;  // (the persistent kernels step it on per sweep)
     if (persistent && cfar) {
       cfear_launch_replay_chunk_cloud(o->rp_cloud[b], o->cap_points, o->rp_cloud_n[b], cnt, o->B, &OP, o->d_states, o->d_scratch_hdr, o->d_cov_work, o->d_summaries,
                                       o->d_poses_out, d_records ? d_records + (size_t)t0 * o->B : nullptr, ctx->stream);
@@ -1663,6 +1719,7 @@ static int replay_impl_queue(cfear_ctx* ctx, cfear_odometry* o, const uint8_t* f
     } else {
       for (int t = 0; t < cnt; t++) {
         OP.records = d_records ? d_records + (size_t)(t0 + t) * o->B : nullptr;
+        OP.cs.cov_out = d_cov6 ? d_cov6 + (size_t)(t0 + t) * o->B * 36 : nullptr;
         if (cfar) odo_launch_sweep_cloud(o, OP, o->rp_cloud[b] + 3 * slots * (size_t)t, o->cap_points, o->rp_cloud_n[b] + (size_t)o->B * t, o->B, ctx->stream);
         else odo_launch_sweep(ctx, o, OP, o->rp_slots[b] + slots * (size_t)t, o->B, ctx->stream);
       }
@@ -1675,8 +1732,9 @@ static int replay_impl_queue(cfear_ctx* ctx, cfear_odometry* o, const uint8_t* f
   CFEAR_HIP_CHECK(ctx, hipGetLastError());
   return CFEAR_OK;
 }
-static int replay_impl(cfear_ctx* ctx, cfear_odometry* o, const uint8_t* frames, bool on_device, int n_sweeps, cfear_sweep_record* d_records) {
-  const int rc = replay_impl_queue(ctx, o, frames, on_device, n_sweeps, d_records);
+static int replay_impl(cfear_ctx* ctx, cfear_odometry* o, const uint8_t* frames, bool on_device, int n_sweeps, cfear_sweep_record* d_records,
+                       double* d_cov6) {
+  const int rc = replay_impl_queue(ctx, o, frames, on_device, n_sweeps, d_records, d_cov6);
   if (rc != CFEAR_OK && o->rp_stream) {
     // an error after work was queued: copies out of the caller's frames and kernels that read them may be in flight - nothing of
     // this call is left running when it returns (the error text is kept)
@@ -1700,21 +1758,89 @@ static int replay_check(cfear_ctx* ctx, cfear_odometry* o, const uint8_t* frames
   return odo_join(ctx, o);
 }
 
-int cfear_odometry_replay_host(cfear_ctx* ctx, cfear_odometry* o, const uint8_t* h_frames, int n_sweeps, cfear_sweep_record* records) {
+int cfear_odometry_replay_host_cov(cfear_ctx* ctx, cfear_odometry* o, const uint8_t* h_frames, int n_sweeps, cfear_sweep_record* records, double* cov6) {
   int rc = replay_check(ctx, o, h_frames, n_sweeps);
   if (rc != CFEAR_OK) return rc;
   if (records && (rc = replay_ensure(ctx, o, 0, false, (size_t)n_sweeps * o->B)) != CFEAR_OK) return rc;
-  rc = replay_impl(ctx, o, h_frames, false, n_sweeps, records ? o->d_records : nullptr);
+  const size_t ncov = cov6 ? (size_t)n_sweeps * o->B * 36 : 0;
+  if (ncov > o->cov_seq_cap) {
+    CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    if (o->d_cov_seq) (void)hipFree(o->d_cov_seq);
+    o->d_cov_seq = nullptr; o->cov_seq_cap = 0;
+    if (hipMalloc(&o->d_cov_seq, sizeof(double) * ncov) != hipSuccess) return cfear_fail(ctx, CFEAR_ERR_NOMEM, "hipMalloc per-sweep covariances");
+    o->cov_seq_cap = ncov;
+  }
+  rc = replay_impl(ctx, o, h_frames, false, n_sweeps, records ? o->d_records : nullptr, cov6 ? o->d_cov_seq : nullptr);
   if (rc != CFEAR_OK) return rc;
   if (records) CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(records, o->d_records, sizeof(cfear_sweep_record) * (size_t)n_sweeps * o->B, hipMemcpyDeviceToHost, ctx->stream));
+  if (cov6) CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(cov6, o->d_cov_seq, sizeof(double) * ncov, hipMemcpyDeviceToHost, ctx->stream));
   CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   return odo_capacity_check(ctx, o, "odometry_replay_host");
 }
+int cfear_odometry_replay_host(cfear_ctx* ctx, cfear_odometry* o, const uint8_t* h_frames, int n_sweeps, cfear_sweep_record* records) {
+  return cfear_odometry_replay_host_cov(ctx, o, h_frames, n_sweeps, records, nullptr);
+}
 
-int cfear_odometry_replay_device(cfear_ctx* ctx, cfear_odometry* o, const uint8_t* d_frames, int n_sweeps, cfear_sweep_record* d_records) {
+int cfear_odometry_replay_device_cov(cfear_ctx* ctx, cfear_odometry* o, const uint8_t* d_frames, int n_sweeps, cfear_sweep_record* d_records, double* d_cov6) {
   const int rc = replay_check(ctx, o, d_frames, n_sweeps);
   if (rc != CFEAR_OK) return rc;
-  return replay_impl(ctx, o, d_frames, true, n_sweeps, d_records);  // asynchronous: nothing is waited for
+  return replay_impl(ctx, o, d_frames, true, n_sweeps, d_records, d_cov6);  // asynchronous: nothing is waited for
+}
+int cfear_odometry_replay_device(cfear_ctx* ctx, cfear_odometry* o, const uint8_t* d_frames, int n_sweeps, cfear_sweep_record* d_records) {
+  return cfear_odometry_replay_device_cov(ctx, o, d_frames, n_sweeps, d_records, nullptr);
+}
+
+// ---- estimate_cov_by_sampling on the batched routes (cov_sampling_dev.h) ------------------------------------------------
+int cfear_odometry_set_cov_sampling(cfear_ctx* ctx, cfear_odometry* o, int enable, double xy_range, double yaw_range, int samples_per_axis,
+                                    double covariance_scaler) {
+  if (!ctx || !o) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_set_cov_sampling: bad argument");
+  if (!enable) {  // the buffers stay for a later switch back on; kernels already queued keep the parameters they were given
+    o->cov_on = false;
+    return CFEAR_OK;
+  }
+  if (samples_per_axis < 1 || !std::isfinite(xy_range) || !std::isfinite(yaw_range) || !std::isfinite(covariance_scaler))
+    return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_set_cov_sampling: samples_per_axis < 1 or a range / scaler that is not finite");
+  if (samples_per_axis > 8) return cfear_fail(ctx, CFEAR_ERR_UNSUPPORTED, "odometry_set_cov_sampling: at most 8 samples per axis (512 GetCost per sweep)");
+  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  { const int jrc = odo_join(ctx, o); if (jrc != CFEAR_OK) return jrc; }
+  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // nothing in flight reads the design or the costs while they are replaced
+  const int m = samples_per_axis * samples_per_axis * samples_per_axis;
+  std::vector<double> offs, A, design((size_t)13 * m);
+  cov_sample_design(xy_range, yaw_range, samples_per_axis, offs, A);
+  pinv10_svd(m, A.data(), design.data());
+  memcpy(design.data() + 10 * (size_t)m, offs.data(), sizeof(double) * 3 * m);
+  if (!o->d_cov_ctx) {
+    CFEAR_HIP_CHECK(ctx, hipMalloc(&o->d_cov_ctx, sizeof(CovSampleCtx) * (size_t)o->B));
+    CFEAR_HIP_CHECK(ctx, hipMemset(o->d_cov_ctx, 0, sizeof(CovSampleCtx) * (size_t)o->B));
+  }
+  if (m > o->cov_m_cap) {
+    for (double** p : {&o->d_cov_design, &o->d_cov_costs}) { if (*p) (void)hipFree(*p); *p = nullptr; }
+    o->cov_m_cap = 0;
+    if (hipMalloc(&o->d_cov_design, sizeof(double) * 13 * (size_t)m) != hipSuccess || hipMalloc(&o->d_cov_costs, sizeof(double) * (size_t)m * o->B) != hipSuccess)
+      return cfear_fail(ctx, CFEAR_ERR_NOMEM, "hipMalloc cost-sampling buffers");
+    o->cov_m_cap = m;
+  }
+  CFEAR_HIP_CHECK(ctx, hipMemset(o->d_cov_costs, 0, sizeof(double) * (size_t)m * o->B));
+  CFEAR_HIP_CHECK(ctx, hipMemcpy(o->d_cov_design, design.data(), sizeof(double) * 13 * (size_t)m, hipMemcpyHostToDevice));
+  // no sweep sampled yet under these settings (n = 0: cov_samples reads zeros and 'not sampled')
+  CFEAR_HIP_CHECK(ctx, hipMemset(o->d_cov_ctx, 0, sizeof(CovSampleCtx) * (size_t)o->B));
+  o->cov_m = m; o->cov_scaler = covariance_scaler; o->cov_on = true;
+  return CFEAR_OK;
+}
+
+int cfear_odometry_cov_samples(cfear_ctx* ctx, cfear_odometry* o, int sequence, double* costs, int* sampled) {
+  if (!ctx || !o || sequence < 0 || sequence >= o->B || (!costs && !sampled)) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_cov_samples: bad argument");
+  if (!o->cov_on) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_cov_samples: cost sampling is off (cfear_odometry_set_cov_sampling)");
+  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  { const int jrc = odo_join(ctx, o); if (jrc != CFEAR_OK) return jrc; }
+  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  if (costs) CFEAR_HIP_CHECK(ctx, hipMemcpy(costs, o->d_cov_costs + (size_t)sequence * o->cov_m, sizeof(double) * o->cov_m, hipMemcpyDeviceToHost));
+  if (sampled) {
+    CovSampleCtx c;
+    CFEAR_HIP_CHECK(ctx, hipMemcpy(&c, o->d_cov_ctx + sequence, sizeof(c), hipMemcpyDeviceToHost));
+    *sampled = c.n >= 2 ? c.sampled : 0;
+  }
+  return odo_capacity_check(ctx, o, "odometry_cov_samples");
 }
 
 // after a synchronisation of the context stream: has any scan of this object overflowed its cell capacity (CFEAR_TUNE_MAX_CELLS)?

@@ -15,6 +15,7 @@
 #define CFEAR_REG_LDS_BUDGET (160 * 1024)
 #include "common.h"
 #include "odometry_step_dev.h"
+#include "cov_sampling_dev.h"
 
 namespace {
 constexpr size_t kChunkLds = FeatLdsC::total > RegLds::total ? FeatLdsC::total : RegLds::total;
@@ -33,6 +34,13 @@ __device__ __noinline__ void register_stage(unsigned char* lds, int q, const Odo
                                             cfear_reg_summary* summaries, double* poses_out) {
   register_step_body<false>(lds, q, *P, states, scratch, cov_work, summaries, poses_out);
 }
+// estimate_cov_by_sampling and / or the sweep's cov_current (OdoParams::cs): after the registration, before the next sweep's features
+__device__ __noinline__ void cov_sample_stage(unsigned char* lds, int q, const OdoParams* P, const BlockScratch* scratch, double* cov_work) {
+  cov_sample_body<false>(lds, q, *P, scratch, cov_work);
+}
+__device__ __noinline__ void cov_sample_stage_general(unsigned char* lds, int q, const OdoParams* P, const BlockScratch* scratch, double* cov_work) {
+  cov_sample_body<true>(lds, q, *P, scratch, cov_work);
+}
 
 __global__ __launch_bounds__(BLOCK_F) void replay_chunk_kernel(const uint32_t* slots_chunk /*[cnt][B][A * k]*/, int cnt, int B, const double* trig,
                                                                OdoParams OP, SeqState* states, const BlockScratch* scratch, double* cov_work,
@@ -43,12 +51,20 @@ __global__ __launch_bounds__(BLOCK_F) void replay_chunk_kernel(const uint32_t* s
   __shared__ OdoParams P;  // by pointer to the stages: LDS, not a per-thread stack copy
   if (threadIdx.x == 0) P = OP;
   for (int t = 0; t < cnt; t++) {
-    if (threadIdx.x == 0) P.records = records ? records + (size_t)t * B : nullptr;
+    if (threadIdx.x == 0) {
+      P.records = records ? records + (size_t)t * B : nullptr;
+      P.cs.cov_out = OP.cs.cov_out ? OP.cs.cov_out + (size_t)t * B * 36 : nullptr;
+    }
     __syncthreads();
     features_stage(lds, q, slots_chunk + sweep_slots * (size_t)t, trig, &P, states, scratch);
     __syncthreads();  // the scan is complete (and visible to the whole workgroup) before it is registered
     register_stage(lds, q, &P, states, scratch, cov_work, summaries, poses_out);
-    __syncthreads();  // the state of the sequence (motion, keyframe ring, free slot) is written before the next sweep reads it
+    __syncthreads();
+    if (OP.cs.ctx || OP.cs.cov_out) {  // (kernel parameters: uniform over the workgroup)
+      if (cov_sample_general(OP.rp)) cov_sample_stage_general(lds, q, &P, scratch, cov_work);
+      else cov_sample_stage(lds, q, &P, scratch, cov_work);
+      __syncthreads();
+    }  // the state of the sequence (motion, keyframe ring, free slot) is written before the next sweep reads it
   }
 }
 // the same chunk from clouds (filter_type CA-CFAR): [cnt][B][cap][3] floats and [cnt][B] counts
@@ -60,12 +76,20 @@ __global__ __launch_bounds__(BLOCK_F) void replay_chunk_cloud_kernel(const float
   __shared__ OdoParams P;
   if (threadIdx.x == 0) P = OP;
   for (int t = 0; t < cnt; t++) {
-    if (threadIdx.x == 0) P.records = records ? records + (size_t)t * B : nullptr;
+    if (threadIdx.x == 0) {
+      P.records = records ? records + (size_t)t * B : nullptr;
+      P.cs.cov_out = OP.cs.cov_out ? OP.cs.cov_out + (size_t)t * B * 36 : nullptr;
+    }
     __syncthreads();
     features_cloud_stage(lds, q, xyi_chunk + 3 * (size_t)cap * B * t, cap, counts_chunk + (size_t)B * t, &P, states, scratch);
     __syncthreads();
     register_stage(lds, q, &P, states, scratch, cov_work, summaries, poses_out);
     __syncthreads();
+    if (OP.cs.ctx || OP.cs.cov_out) {  // (kernel parameters: uniform over the workgroup)
+      if (cov_sample_general(OP.rp)) cov_sample_stage_general(lds, q, &P, scratch, cov_work);
+      else cov_sample_stage(lds, q, &P, scratch, cov_work);
+      __syncthreads();
+    }
   }
 }
 }  // namespace

@@ -39,7 +39,8 @@ int main(int argc, char** argv) {
            "                      what a reader that owns its frame buffer can do (the image then goes to the device by DMA straight from it); a rosbag\n"
            "                      message is a fresh pageable allocation per sweep - the default 0 measures that\n"
            "       [--replay 1]   whole recording through cfear_odometry_replay_host (pieces of 256 sweeps in pinned memory, no\n"
-           "                      host round trip per sweep) instead of one CallbackOffline + pointcloudCallback per sweep\n");
+           "                      host round trip per sweep) instead of one CallbackOffline + pointcloudCallback per sweep; --covar_sampling and\n"
+           "                      --cov_file work there too (cfear_odometry_set_cov_sampling, cfear_odometry_replay_host_cov), --soft_constraint does not\n");
     return argc < 2;
   }
   const std::string frames = arg(argc, argv, "--frames", "");
@@ -93,8 +94,8 @@ int main(int argc, char** argv) {
     dev->check(cfear_tune(dev->ctx(), CFEAR_TUNE_NN_TIE_RULE, atoi(arg(argc, argv, "--nn-tie", "0"))), "cfear_tune");
     if (!atoi(arg(argc, argv, "--replay", "0"))) dev->check(cfear_tune(dev->ctx(), CFEAR_TUNE_VOXEL_ORDER, atoi(arg(argc, argv, "--voxel-order", "0"))), "cfear_tune");
     if (atoi(arg(argc, argv, "--replay", "0"))) {
-      if (rad_par.dataset != "oxford" || par.soft_constraint || par.estimate_cov_by_sampling)
-        throw std::runtime_error("--replay 1 runs the Oxford route without soft constraints / sampled covariances; use the per-sweep route for those");
+      if (rad_par.dataset != "oxford" || par.soft_constraint)
+        throw std::runtime_error("--replay 1 runs the Oxford route without soft constraints; use the per-sweep route for those");
       // maximum-rate replay: the same parameters the two classes would apply, set once; the loop of offline_odometry.cpp:103-125
       // runs on the device sweep after sweep, the poses of a piece come back together
       cfear_params q = p;
@@ -113,6 +114,9 @@ int main(int argc, char** argv) {
       dev->set_params(q);
       cfear_odometry* odo = nullptr;
       dev->check(cfear_odometry_create(dev->ctx(), 1, &odo), "cfear_odometry_create");
+      if (par.estimate_cov_by_sampling)  // odometrykeyframefuser.cpp:202-208 on the device, after every sweep's registration
+        dev->check(cfear_odometry_set_cov_sampling(dev->ctx(), odo, 1, par.cov_sampling_xy_range, par.cov_sampling_yaw_range,
+                                                   (int)par.cov_sampling_samples_per_axis, par.cov_sampling_covariance_scaler), "cfear_odometry_set_cov_sampling");
       const int piece = 256;
       const size_t sweep = (size_t)A * R;
       void* pinned = nullptr;
@@ -120,6 +124,9 @@ int main(int argc, char** argv) {
       std::vector<cfear_sweep_record> rec(piece);
       std::ofstream est(est_dir + "/est_00.txt");
       est << std::fixed; est.precision(6);
+      std::ofstream covs;  // the per-sweep route's --cov_file: cov_current after every sweep, 36 values per line
+      std::vector<double> cov;
+      if (!cov_file.empty()) { covs.open(cov_file); covs.precision(17); cov.resize((size_t)36 * piece); }
       int n = 0;
       double t_dev = 0;
       const auto t_start = std::chrono::steady_clock::now();
@@ -128,12 +135,17 @@ int main(int argc, char** argv) {
         const int got = (int)((size_t)in.gcount() / sweep);
         if (got <= 0) break;
         const auto t0 = std::chrono::steady_clock::now();
-        dev->check(cfear_odometry_replay_host(dev->ctx(), odo, static_cast<const uint8_t*>(pinned), got, rec.data()), "cfear_odometry_replay_host");
+        dev->check(cfear_odometry_replay_host_cov(dev->ctx(), odo, static_cast<const uint8_t*>(pinned), got, rec.data(), covs.is_open() ? cov.data() : nullptr),
+                   "cfear_odometry_replay_host_cov");
         t_dev += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         for (int i = 0; i < got; i++) {
           const double c = std::cos(rec[i].pose[2]), sn = std::sin(rec[i].pose[2]);
           est << c << " " << -sn << " 0.000000 " << rec[i].pose[0] << " " << sn << " " << c << " 0.000000 " << rec[i].pose[1] << " "
               << "0.000000 0.000000 1.000000 0.000000\n";
+          if (covs.is_open()) {  // (before its first registration the fuser's cov_current is the identity it was constructed with)
+            const bool first = n + i == 0;
+            for (int a = 0; a < 36; a++) covs << (first ? (a % 7 == 0 ? 1.0 : 0.0) : cov[(size_t)36 * i + a]) << (a == 35 ? "\n" : " ");
+          }
         }
         n += got;
         const double tot = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();

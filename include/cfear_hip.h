@@ -312,8 +312,24 @@ int cfear_odometry_poses(cfear_ctx* ctx, cfear_odometry* odo, double* poses_xyt)
 /* cov_current of every sequence after the last sweep (the Covariance& of the five-argument pointcloudCallback,
  * odometrykeyframefuser.cpp:196,397-411): n_sequences x 36 doubles row-major - the registration covariance of the sweep's
  * Register() (GetCovariance), the identity FormatScans starts from when the registration had no usable solution, zeros before
- * the second sweep. (The cost-sampling variant, estimate_cov_by_sampling, is the per-call cfear_cov_by_sampling.) Synchronises. */
+ * the second sweep - or, with cfear_odometry_set_cov_sampling on, the cost-sampling covariance of the sweep where it succeeded
+ * (odometrykeyframefuser.cpp:202-208). Synchronises. */
 int cfear_odometry_covariances(cfear_ctx* ctx, cfear_odometry* odo, double* cov6);
+/* estimate_cov_by_sampling and its companions (odometrykeyframefuser.h:104-110: cov_sampling_xy_range 0.4, cov_sampling_yaw_range
+ * 0.0043625, cov_sampling_samples_per_axis 3, cov_sampling_covariance_scaler 4.0) for every sequence of a batched odometry object, from
+ * its next sweep on, on every route of the object (cfear_odometry_step_*, cfear_odometry_replay_*). Off by default (= the behaviour
+ * without the call). On: after each sweep's Register and sanity check, GetCost at samples_per_axis^3 poses around the registered pose
+ * against the keyframes the registration used (:261-380, as cfear_cov_by_sampling; itr = the sweep's outer iterations), and
+ * cov_current becomes the sampled covariance where the fit is convex and num_residuals != 3. Poses, keyframes and records do not
+ * change. samples_per_axis 1..8 (CFEAR_ERR_UNSUPPORTED above, CFEAR_ERR_INVALID below 1 or for a range / scaler that is not finite;
+ * the object keeps its previous setting). enable = 0 switches it off (the other arguments are not read). cfear_odometry_reset keeps
+ * the setting. Synchronises the context stream. */
+int cfear_odometry_set_cov_sampling(cfear_ctx* ctx, cfear_odometry* odo, int enable, double xy_range, double yaw_range,
+                                    int samples_per_axis, double covariance_scaler);
+/* The last sweep's sampled costs of one sequence (samples_per_axis^3 doubles, the reference's sample order :294-296 - what
+ * cov_samples_to_file_as_well would dump) and whether the sampled covariance was used (cov_sampled_success; 0 on a sequence's first
+ * sweep, which samples nothing). Either pointer may be NULL. CFEAR_ERR_INVALID while sampling is off. Synchronises. */
+int cfear_odometry_cov_samples(cfear_ctx* ctx, cfear_odometry* odo, int sequence, double* costs, int* sampled);
 /* Has any scan of this object been truncated - more oriented surface points than CFEAR_TUNE_MAX_CELLS, or a cloud with more points than the object
  * holds? Synchronises the context stream; returns CFEAR_OK or CFEAR_ERR_CAPACITY (with the message the reading calls give). For callers of the
  * asynchronous cfear_odometry_replay_device, which read their records on the device and never pass through poses / summary / replay_host.
@@ -350,6 +366,14 @@ int cfear_odometry_replay_host(cfear_ctx* ctx, cfear_odometry* odo, const uint8_
  * afterwards (a copy of d_records, the next write into d_frames) is ordered behind all of it. */
 int cfear_odometry_replay_device(cfear_ctx* ctx, cfear_odometry* odo, const uint8_t* d_frames, int n_sweeps,
                                  cfear_sweep_record* d_records);
+/* cfear_odometry_replay_host / _device plus cov_current after every sweep: cov6 = n_sweeps x n_sequences x 36 doubles row-major
+ * (host memory for _host, device memory for _device, written by the kernels like d_records), or NULL = exactly the calls above. With
+ * cost sampling off this is the registration covariance of every sweep (as cfear_odometry_covariances after it); on, the sampled one
+ * where the sampling succeeded. */
+int cfear_odometry_replay_host_cov(cfear_ctx* ctx, cfear_odometry* odo, const uint8_t* h_frames, int n_sweeps,
+                                   cfear_sweep_record* records, double* cov6);
+int cfear_odometry_replay_device_cov(cfear_ctx* ctx, cfear_odometry* odo, const uint8_t* d_frames, int n_sweeps,
+                                     cfear_sweep_record* d_records, double* d_cov6);
 /* Page-locked host memory for the sweeps of a replay (hipHostMalloc / hipHostFree). */
 int cfear_host_alloc(cfear_ctx* ctx, size_t bytes, void** out);
 void cfear_host_free(cfear_ctx* ctx, void* p);
