@@ -77,6 +77,7 @@ EXPORTS = [
     "cfear_odometry_step_device", "cfear_odometry_step_cloud_device", "cfear_odometry_step_host", "cfear_odometry_poses",
     "cfear_odometry_replay_host", "cfear_odometry_replay_device", "cfear_odometry_replay_host_cov", "cfear_odometry_replay_device_cov",
     "cfear_odometry_set_cov_sampling", "cfear_odometry_cov_samples", "cfear_host_alloc", "cfear_host_free",
+    "cfear_surface_dims", "cfear_get_surface", "cfear_odometry_set_surface_recording", "cfear_odometry_surface",
     "cfear_odometry_covariances", "cfear_odometry_status", "cfear_odometry_summary", "cfear_odometry_profile", "cfear_odometry_profile_read", "cfear_odometry_profile_read_stages", "cfear_odometry_phase_times", "cfear_time_kstrongest",
 ]
 
@@ -151,6 +152,10 @@ def lib():
         "cfear_odometry_replay_device_cov": (C.c_int, [vp, vp, u8p, C.c_int, vp, vp]),
         "cfear_odometry_set_cov_sampling": (C.c_int, [vp, vp, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double]),
         "cfear_odometry_cov_samples": (C.c_int, [vp, vp, C.c_int, f64p, vp]),
+        "cfear_surface_dims": (C.c_int, [C.c_double, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+        "cfear_get_surface": (C.c_int, [vp, C.POINTER(vp), C.c_int, f64p, f64p, C.c_int, C.c_double, C.c_int, f64p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+        "cfear_odometry_set_surface_recording": (C.c_int, [vp, vp, C.c_int]),
+        "cfear_odometry_surface": (C.c_int, [vp, vp, C.c_double, C.c_int, vp, vp, vp, vp]),
         "cfear_host_alloc": (C.c_int, [vp, C.c_size_t, C.POINTER(vp)]),
         "cfear_host_free": (None, [vp, vp]),
         "cfear_odometry_summary": (C.c_int, [vp, vp, C.c_int, C.POINTER(RegSummary), C.POINTER(C.c_int),
@@ -167,6 +172,16 @@ def lib():
         fn.argtypes = args
     _LIB = L
     return L
+
+
+def surface_dims(res, width, x0=0.0, y0=0.0):
+    """cfear_surface_dims (host only, no device): the GetSurface grid (n_scan_normal.cpp:46-63) -> (pixels, values visited along x,
+    values visited along y). Raises CfearError for an invalid (rc -1) or too large (rc -3) grid."""
+    p, nx, ny = C.c_int(), C.c_int(), C.c_int()
+    rc = lib().cfear_surface_dims(float(res), int(width), float(x0), float(y0), C.byref(p), C.byref(nx), C.byref(ny))
+    if rc != 0:
+        raise CfearError("cfear_surface_dims failed rc=%d" % rc)
+    return p.value, nx.value, ny.value
 
 
 def default_params(**kw):
@@ -200,6 +215,7 @@ class Context:
         self._h = C.c_void_p()
         self.params = params
         self.A, self.R = int(A), int(R)
+        self.device = int(device)
         self._tuned = {}
         rc = self._L.cfear_create(C.byref(self._h), int(device), C.c_void_p(stream or 0), C.byref(params),
                                   self.A, self.R)
@@ -371,6 +387,20 @@ class Context:
             return None
         self._check(rc, "cfear_get_cost")
         return score.value, res[:m.value].copy()
+
+    def get_surface(self, scans, poses, res, width, itr=2, prior_cov6=None):
+        """n_scan_normal_reg::GetSurface (n_scan_normal.cpp:29-65) -> (pixels, pixels) array, row i = x, column j = y; NaN in the
+        cells the reference's loops never reach. prior_cov6: reg_cov.back() with soft_constraints, None: without."""
+        n = len(scans)
+        arr = (C.c_void_p * n)(*[s._h for s in scans])
+        P = np.ascontiguousarray(poses, dtype=np.float64).reshape(n, 3).copy()
+        pixels = surface_dims(res, width, P[-1, 0], P[-1, 1])[0]
+        out = np.empty((pixels, pixels))
+        pc = None if prior_cov6 is None else np.ascontiguousarray(prior_cov6, dtype=np.float64).reshape(36).copy()
+        nx, ny = C.c_int(), C.c_int()
+        self._check(self._L.cfear_get_surface(self._h, arr, n, P.ctypes.data, None if pc is None else pc.ctypes.data, int(itr), float(res),
+                                              int(width), out.ctypes.data, C.byref(nx), C.byref(ny)), "cfear_get_surface")
+        return out
 
     def cov_by_sampling(self, scans, poses, final_cost, num_residuals, itr=2, xy_range=0.4, yaw_range=0.0043625, steps=3, cov_scaler=4.0):
         """approximateCovarianceBySampling -> (success, cov6x6, sampled costs)"""
@@ -574,6 +604,27 @@ class Odometry:
         self._ctx._check(self._ctx._L.cfear_odometry_cov_samples(self._ctx._h, self._h, int(sequence), costs.ctypes.data, C.byref(ok)),
                          "cfear_odometry_cov_samples")
         return costs, bool(ok.value)
+
+    def set_surface_recording(self, enable=True):
+        """every registration records what it used, for surface() (cfear_odometry_set_surface_recording); off by default"""
+        self._ctx._check(self._ctx._L.cfear_odometry_set_surface_recording(self._ctx._h, self._h, int(bool(enable))),
+                         "cfear_odometry_set_surface_recording")
+
+    def surface(self, res, width, details=False):
+        """GetSurface of every sequence around its last registration -> torch float64 tensor [B, pixels, pixels] on the context's device
+        (NaN where nothing was evaluated). details=True: also (n_used [B], itr_used [B], poses_used [B, 64, 3]) as numpy arrays.
+        Synchronises the context before returning, so the tensor is ready on any stream."""
+        import torch
+        pixels = surface_dims(res, width)[0]
+        out = torch.empty((self.B, pixels, pixels), dtype=torch.float64, device="cuda:%d" % self._ctx.device)
+        torch.cuda.synchronize(out.device)  # (the allocator's stream may still use the memory; the context stream writes it)
+        n_used, itr_used = np.zeros(self.B, dtype=np.int32), np.zeros(self.B, dtype=np.int32)
+        poses_used = np.zeros((self.B, 64, 3))
+        c = self._ctx
+        c._check(c._L.cfear_odometry_surface(c._h, self._h, float(res), int(width), out.data_ptr(), n_used.ctypes.data, itr_used.ctypes.data,
+                                             poses_used.ctypes.data), "cfear_odometry_surface")
+        c._check(c._L.cfear_synchronize(c._h), "cfear_synchronize")
+        return (out, n_used, itr_used, poses_used) if details else out
 
     def profile(self, enable):
         self._ctx._check(self._ctx._L.cfear_odometry_profile(self._ctx._h, self._h, int(enable)), "cfear_odometry_profile")

@@ -303,4 +303,26 @@ int cfear_time_kstrongest(cfear_ctx* ctx, const uint8_t* d_polar, int n_scans, u
   return CFEAR_OK;
 }
 
+// ---- cost surfaces: the grid of GetSurface (n_scan_normal.cpp:46-63), host only ---------------------------------
+// The values `for (v = v0 - width; v <= v0 + width; v = v + res)` visits, accumulated in double as the reference does (at most `pixels`
+// of them are kept: the reference's surface has no room for more). Returns how many.
+__attribute__((visibility("hidden"))) int cfear_surface_axis(double v0, double res, int width, int pixels, double* out) {
+  int k = 0;
+  for (double v = v0 - width; v <= v0 + width && k < pixels; v = v + res) {
+    if (out) out[k] = v;
+    k++;
+  }
+  return k;
+}
+
+int cfear_surface_dims(double res, int width, double x0, double y0, int* pixels, int* nx, int* ny) {
+  if (!pixels || !nx || !ny || !isfinite(res) || !(res > 0.0) || width < 0) return CFEAR_ERR_INVALID;
+  const double p = ceil(2.0 * width / res) + 1;  // :47
+  if (!(p <= CFEAR_SURFACE_MAX_SIDE)) return CFEAR_ERR_UNSUPPORTED;
+  *pixels = (int)p;
+  *nx = cfear_surface_axis(x0, res, width, *pixels, nullptr);
+  *ny = cfear_surface_axis(y0, res, width, *pixels, nullptr);
+  return CFEAR_OK;
+}
+
 }  // extern "C"

@@ -19,6 +19,7 @@
 #include "common.h"
 #include "odometry_step_dev.h"
 #include "cov_sampling_dev.h"
+#include "surface_dev.h"
 
 namespace {
 
@@ -143,6 +144,86 @@ __global__ __launch_bounds__(BLOCK_R, 3) void get_cost_samples_kernel(ScanDev* c
   W.red_i = reinterpret_cast<int*>(lds + RegLds::red_i);
   get_cost_block(sp, n, my_poses, P, W, reinterpret_cast<double*>(lds + RegLds::par), reinterpret_cast<RegShared*>(lds + RegLds::regsh), itr,
                  costs + b, nullptr, 0, n_res + b);
+}
+
+// ---- cost surfaces (surface_dev.h): build stage + evaluation -------------------------------------------
+// The A/B build CFEAR_SURFACE_NAIVE evaluates in the build kernel, pixel after pixel, with evaluate_partial (the blocks as the build
+// stage leaves them: memory SoA, source means rotated - so the rotation it applies is the identity) and its workgroup reduction.
+__device__ inline void surface_naive_eval(RegShared* sh, const SurfHdr* hdr, const double* coords, int nx, int ny, int pixels, double* out) {
+  LRegShared* ls = (LRegShared*)sh;
+  const int M = hdr->nblk;
+  for (int p = 0; p < pixels * pixels; p++) {
+    const int i = p / pixels, j = p - i * pixels;
+    if (i >= nx || j >= ny) { if (threadIdx.x == 0) out[p] = __builtin_nan(""); continue; }
+    const double x = coords[i], y = coords[pixels + j];
+    __syncthreads();
+    evaluate_partial(ls, M, 0, x, y, 1.0, 0.0);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      gather_partials(ls->rw.red, &ls->G);
+      double v = ls->G.cost;
+      if (hdr->prior_on) {
+        const double a = hdr->palpha;
+        const double d0 = a * (hdr->pguess[0] - x), d1 = a * (hdr->pguess[1] - y), d2 = a * (hdr->pguess[2] - hdr->yaw);
+        double r[3];
+        for (int k = 0; k < 3; k++) r[k] = hdr->pL[3 * k] * d0 + hdr->pL[3 * k + 1] * d1 + hdr->pL[3 * k + 2] * d2;
+        v += 0.5 * (r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
+      }
+      out[p] = v;
+    }
+  }
+}
+// the build stage of one problem (cfear_get_surface)
+template <bool NAIVE>
+__global__ __launch_bounds__(BLOCK_R, 3) void surface_build_kernel(ScanDev* const* scans, int n, const double* poses, RegParams P, BlockScratch B,
+                                                                int itr, const double* prior_cov6, SurfHdr* hdr, const double* coords,
+                                                                const int* nxy, int pixels, double* out) {
+  __shared__ __attribute__((aligned(16))) unsigned char lds[RegLds::total];
+  ScanDev** sp = reinterpret_cast<ScanDev**>(lds + RegLds::scanptr);
+  for (int i = threadIdx.x; i < n; i += blockDim.x) sp[i] = scans[i];
+  __syncthreads();
+  const RegScratch W = make_rscratch(B, lds);
+  RegShared* sh = reinterpret_cast<RegShared*>(lds + RegLds::regsh);
+  surface_build_block(sp, n, poses, P, W, reinterpret_cast<double*>(lds + RegLds::par), sh, itr, prior_cov6, hdr);
+  if (NAIVE) {
+    __syncthreads();
+    surface_naive_eval(sh, hdr, coords, nxy[0], nxy[1], pixels, out);
+  }
+}
+// ... of every sequence of a batched odometry object around its last registration (cfear_odometry_surface): what register_step_body
+// recorded in OP.cs.ctx; a sequence without a registration in the last step (n < 2) gets no blocks (its coordinates: none visited)
+template <bool NAIVE>
+__global__ __launch_bounds__(BLOCK_R, 3) void surface_build_step_kernel(OdoParams OP, const BlockScratch* scratch, SurfHdr* hdr, const double* coords,
+                                                                     const int* nxy, int pixels, double* out) {
+  __shared__ __attribute__((aligned(16))) unsigned char lds[RegLds::total];
+  const int q = blockIdx.x;
+  const CovSampleCtx* cx = OP.cs.ctx + q;
+  const int n = cx->n;  // (block-uniform)
+  if (n < 2) {
+    if (threadIdx.x == 0) { hdr[q].blk = nullptr; hdr[q].cap = 0; hdr[q].nblk = 0; hdr[q].prior_on = 0; hdr[q].yaw = 0; }
+    if (NAIVE) for (int p = threadIdx.x; p < pixels * pixels; p += BLOCK_R) out[(size_t)q * pixels * pixels + p] = __builtin_nan("");
+    return;
+  }
+  const int nslots = OP.submap + 1;
+  ScanDev** sp = reinterpret_cast<ScanDev**>(lds + RegLds::scanptr);
+  for (int i = threadIdx.x; i < n; i += BLOCK_R)
+    sp[i] = reinterpret_cast<ScanDev*>(OP.scans_base + OP.scan_stride * ((size_t)q * nslots + cx->slot[i]));
+  __syncthreads();
+  const RegScratch W = make_rscratch(scratch[q], lds);
+  RegShared* sh = reinterpret_cast<RegShared*>(lds + RegLds::regsh);
+  surface_build_block(sp, n, cx->pose, OP.rp, W, reinterpret_cast<double*>(lds + RegLds::par), sh, cx->itr, nullptr, hdr + q);
+  if (NAIVE) {
+    __syncthreads();
+    surface_naive_eval(sh, hdr + q, coords + (size_t)q * 2 * pixels, nxy[2 * q], nxy[2 * q + 1], pixels, out + (size_t)q * pixels * pixels);
+  }
+}
+// the evaluation (the hot path): grid (tiles of BLOCK * PPT pixels, problems)
+template <int COST, int PPT>
+__global__ __launch_bounds__(CFEAR_SURFACE_BLOCK) void surface_eval_kernel(const SurfHdr* hdr, const double* coords, const int* nxy, int pixels, int loss,
+                                                                           double loss_limit, double* out) {
+  const int q = blockIdx.y;
+  surface_eval_tile<COST, PPT>(hdr + q, coords + (size_t)q * 2 * pixels, nxy[2 * q], nxy[2 * q + 1], pixels, loss, loss_limit,
+                               out + (size_t)q * pixels * pixels, blockIdx.x);
 }
 
 // ---- batched odometry: one launch per stage and sweep (bodies: odometry_step_dev.h) ----
@@ -419,6 +500,14 @@ struct cfear_odometry {
   double* d_cov_costs = nullptr;          // [B][m] sampled costs of the last sweep
   double* d_cov_seq = nullptr;            // cfear_odometry_replay_host_cov: cov_current of every sweep ([n][B][36])
   size_t cov_seq_cap = 0;
+  // cost surfaces (cfear_odometry_set_surface_recording / cfear_odometry_surface): the registration records what it used in d_cov_ctx
+  // (as for the sampling stage, which does not run unless cov_on)
+  bool surf_on = false;
+  bool surf_ready = false;  // d_cov_ctx holds the last step's registrations (a step ran with recording since the last reset / replay)
+  SurfHdr* d_surf_hdr = nullptr;     // [B]
+  double* d_surf_coords = nullptr;   // [B][2][pixels]
+  int* d_surf_nxy = nullptr;         // [B][2]
+  int surf_px_cap = 0;               // pixels per side d_surf_coords is sized for
 };
 // a timing event from the pool, recorded on `st`
 static int odo_timed_event(cfear_ctx* ctx, cfear_odometry* o, std::vector<hipEvent_t>& list, hipStream_t st) {
@@ -480,8 +569,9 @@ static OdoParams odo_params(const cfear_ctx* ctx, const cfear_odometry* o) {
   OP.flags = o->d_flags;
   OP.order = nullptr; OP.work = o->d_work;
   OP.cs.ctx = nullptr; OP.cs.pinv = nullptr; OP.cs.offs = nullptr; OP.cs.costs = nullptr; OP.cs.cov_out = nullptr; OP.cs.scaler = 0; OP.cs.m = 0;
+  if (o->cov_on || o->surf_on) OP.cs.ctx = o->d_cov_ctx;  // (register_step_body records; the sampling stage runs only with cs.m > 0)
   if (o->cov_on) {
-    OP.cs.ctx = o->d_cov_ctx; OP.cs.pinv = o->d_cov_design; OP.cs.offs = o->d_cov_design + 10 * (size_t)o->cov_m;
+    OP.cs.pinv = o->d_cov_design; OP.cs.offs = o->d_cov_design + 10 * (size_t)o->cov_m;
     OP.cs.costs = o->d_cov_costs; OP.cs.scaler = o->cov_scaler; OP.cs.m = o->cov_m;
   }
   return OP;
@@ -526,7 +616,7 @@ static void launch_register_kernel(const OdoParams& P_in, int count, hipStream_t
 // (the replay's per-sweep covariances): before the next sweep's features kernel may reuse a slot the registration read
 static void launch_register_step(const OdoParams& P, int count, hipStream_t st, cfear_odometry* o) {
   launch_register_kernel(P, count, st, o);
-  if (!P.cs.ctx && !P.cs.cov_out) return;
+  if (!P.cs.m && !P.cs.cov_out) return;  // (cs.m: sampling on; cs.ctx alone: the surface recording only)
   if (CFEAR_COV_SAMPLING_NAIVE || P.rp.nn_tie != 0)  // (cov_sample_general)
     hipLaunchKernelGGL(cov_sample_kernel<true>, dim3(count), dim3(BLOCK_R), 0, st, P, o->d_scratch_hdr, o->d_cov_work);
   else
@@ -1037,6 +1127,92 @@ int cfear_get_cost(cfear_ctx* ctx, cfear_scan* const* scans, int n, const double
   return CFEAR_OK;
 }
 
+// ---- cost surfaces (n_scan_normal.cpp:29-65; surface_dev.h) ---------------------------------------------
+__attribute__((visibility("hidden"))) int cfear_surface_axis(double v0, double res, int width, int pixels, double* out);  // cabi.hip
+namespace {
+// the evaluation of `problems` surfaces (surface_eval_kernel): two pixels per thread, or one where that leaves fewer than two
+// workgroups per compute unit (a single surface)
+static void launch_surface_eval(const RegParams& P, int problems, const SurfHdr* d_hdr, const double* d_coords, const int* d_nxy, int pixels,
+                         double* d_out, hipStream_t st) {
+  const int np = pixels * pixels;
+  const int t2 = (np + 2 * CFEAR_SURFACE_BLOCK - 1) / (2 * CFEAR_SURFACE_BLOCK);
+  const bool two = (long long)t2 * problems >= 512;
+  const dim3 grid(two ? t2 : (np + CFEAR_SURFACE_BLOCK - 1) / CFEAR_SURFACE_BLOCK, problems);
+#define CFEAR_SURF_EVAL(C, K) hipLaunchKernelGGL((surface_eval_kernel<C, K>), grid, dim3(CFEAR_SURFACE_BLOCK), 0, st, d_hdr, d_coords, d_nxy, \
+                                                 pixels, P.loss, P.loss_limit, d_out)
+  if (P.cost == CFEAR_COST_P2L) { if (two) CFEAR_SURF_EVAL(CFEAR_COST_P2L, 2); else CFEAR_SURF_EVAL(CFEAR_COST_P2L, 1); }
+  else if (P.cost == CFEAR_COST_P2D) { if (two) CFEAR_SURF_EVAL(CFEAR_COST_P2D, 2); else CFEAR_SURF_EVAL(CFEAR_COST_P2D, 1); }
+  else { if (two) CFEAR_SURF_EVAL(CFEAR_COST_P2P, 2); else CFEAR_SURF_EVAL(CFEAR_COST_P2P, 1); }
+#undef CFEAR_SURF_EVAL
+}
+}  // namespace
+
+int cfear_get_surface(cfear_ctx* ctx, cfear_scan* const* scans, int n, const double* poses_xyt, const double* prior_cov6, int itr,
+                      double res, int width, double* surface, int* nx, int* ny) {
+  if (!ctx || !scans || !poses_xyt || !surface || n < 2) return cfear_fail(ctx, CFEAR_ERR_INVALID, "get_surface: need >= 2 scans, poses and an output");
+  if (n > MAX_SCANS) return cfear_fail(ctx, CFEAR_ERR_UNSUPPORTED, "get_surface: more than 64 scans");
+  int pixels = 0, vx = 0, vy = 0;
+  {
+    // the grid is centred on the round-tripped last pose (:44-45): Affine3dToVectorXYeZ keeps x and y as they are
+    const int rc = cfear_surface_dims(res, width, poses_xyt[3 * (n - 1)], poses_xyt[3 * (n - 1) + 1], &pixels, &vx, &vy);
+    if (rc == CFEAR_ERR_INVALID) return cfear_fail(ctx, rc, "get_surface: res must be finite and > 0, width >= 0");
+    if (rc != CFEAR_OK) return cfear_fail(ctx, rc, "get_surface: more than CFEAR_SURFACE_MAX_SIDE pixels per side");
+  }
+  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  int capmax = ctx->A * ctx->par.k_strongest;
+  for (int i = 0; i < n; i++) {
+    if (!scans[i]) return cfear_fail(ctx, CFEAR_ERR_INVALID, "get_surface: null scan");
+    if (scans[i]->cap_points > capmax) capmax = scans[i]->cap_points;
+  }
+  int rc = check_tie_rule_scans(ctx, scans, n, "get_surface");
+  if (rc != CFEAR_OK) return rc;
+  rc = ensure_ctx_scratch(ctx, capmax, (MAX_SCANS - 1) * capmax);
+  if (rc != CFEAR_OK) return rc;
+  const ScratchLayout L = scratch_layout(capmax, (MAX_SCANS - 1) * capmax);
+  unsigned char* base = static_cast<unsigned char*>(ctx->d_scratch);
+  const BlockScratch B = scratch_header(base, capmax, (MAX_SCANS - 1) * capmax);
+  unsigned char* tail = base + L.total;
+  double* d_poses = reinterpret_cast<double*>(tail);
+  double* d_prior = d_poses + 3 * MAX_SCANS;  // the covariance slot of cfear_register
+  ScanDev** d_ptrs = reinterpret_cast<ScanDev**>(d_prior + 36);
+  // header, coordinates, their counts and the surface: one allocation per call
+  const size_t np = (size_t)pixels * pixels;
+  const size_t hdr_b = (sizeof(SurfHdr) + 255) / 256 * 256, crd_b = (sizeof(double) * 2 * pixels + 255) / 256 * 256;
+  unsigned char* d_buf = nullptr;
+  if (hipMalloc(&d_buf, hdr_b + crd_b + 256 + sizeof(double) * np) != hipSuccess) return cfear_fail(ctx, CFEAR_ERR_NOMEM, "hipMalloc surface");
+  SurfHdr* d_hdr = reinterpret_cast<SurfHdr*>(d_buf);
+  double* d_coords = reinterpret_cast<double*>(d_buf + hdr_b);
+  int* d_nxy = reinterpret_cast<int*>(d_buf + hdr_b + crd_b);
+  double* d_out = reinterpret_cast<double*>(d_buf + hdr_b + crd_b + 256);
+  std::vector<double> coords(2 * (size_t)pixels, 0.0);
+  const int nxy[2] = {cfear_surface_axis(poses_xyt[3 * (n - 1)], res, width, pixels, coords.data()),
+                      cfear_surface_axis(poses_xyt[3 * (n - 1) + 1], res, width, pixels, coords.data() + pixels)};
+  ScanDev* h_ptrs[MAX_SCANS];
+  for (int i = 0; i < n; i++) h_ptrs[i] = reinterpret_cast<ScanDev*>(scans[i]->d_block);
+  hipError_t e = hipMemcpyAsync(d_ptrs, h_ptrs, sizeof(void*) * n, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_poses, poses_xyt, sizeof(double) * 3 * n, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess && prior_cov6) e = hipMemcpyAsync(d_prior, prior_cov6, sizeof(double) * 36, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_coords, coords.data(), sizeof(double) * 2 * pixels, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_nxy, nxy, sizeof(nxy), hipMemcpyHostToDevice, ctx->stream);
+  const RegParams P = reg_params(ctx);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(surface_build_kernel<CFEAR_SURFACE_NAIVE != 0>, dim3(1), dim3(BLOCK_R), 0, ctx->stream, d_ptrs, n, d_poses, P, B, itr,
+                       prior_cov6 ? d_prior : nullptr, d_hdr, d_coords, d_nxy, pixels, d_out);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess && !CFEAR_SURFACE_NAIVE) {
+    launch_surface_eval(P, 1, d_hdr, d_coords, d_nxy, pixels, d_out, ctx->stream);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(surface, d_out, sizeof(double) * np, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  (void)hipFree(d_buf);
+  if (e != hipSuccess) return cfear_fail(ctx, CFEAR_ERR_HIP, "get_surface", e);
+  if (nx) *nx = nxy[0];
+  if (ny) *ny = nxy[1];
+  return CFEAR_OK;
+}
+
 // ---- cost-sampling covariance (odometrykeyframefuser.cpp:261-380) ------------------------------------
 namespace {
 // Minimum-norm least squares of A c = b (A: m x 10), what Eigen's bdcSvd().solve() returns (odometrykeyframefuser.cpp:337), by a
@@ -1232,7 +1408,7 @@ void cfear_odometry_destroy(cfear_ctx* ctx, cfear_odometry* o) {
                   o->d_summaries, o->d_poses_out, o->d_slots[0], o->d_slots[1], o->d_polar, o->d_phase_times,
                   o->rp_polar[0], o->rp_polar[1], o->rp_slots[0], o->rp_slots[1], o->d_records, o->d_flags, o->d_order, o->d_work,
                   o->d_cloud, o->d_cloud_n, o->d_cfar_rows, o->rp_cloud[0], o->rp_cloud[1], o->rp_cloud_n[0], o->rp_cloud_n[1], o->rp_cfar_rows,
-                  o->d_cov_ctx, o->d_cov_design, o->d_cov_costs, o->d_cov_seq};
+                  o->d_cov_ctx, o->d_cov_design, o->d_cov_costs, o->d_cov_seq, o->d_surf_hdr, o->d_surf_coords, o->d_surf_nxy};
   for (hipEvent_t e : {o->rp_filt[0], o->rp_filt[1], o->rp_used[0], o->rp_used[1], o->rp_in}) if (e) (void)hipEventDestroy(e);
   if (o->rp_stream) (void)hipStreamDestroy(o->rp_stream);
   for (void* p : ptrs) if (p) (void)hipFree(p);
@@ -1259,6 +1435,7 @@ int cfear_odometry_reset(cfear_ctx* ctx, cfear_odometry* o) {
   CFEAR_HIP_CHECK(ctx, hipMemsetAsync(o->d_cov_work, 0, sizeof(double) * 36 * (size_t)o->B, ctx->stream));
   if (o->d_flags) CFEAR_HIP_CHECK(ctx, hipMemsetAsync(o->d_flags, 0, sizeof(int) * ((size_t)o->B + 1), ctx->stream));
   o->order_ready = false;
+  o->surf_ready = false;
   CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   return CFEAR_OK;
 }
@@ -1409,6 +1586,7 @@ static int odo_step_clouds(cfear_ctx* ctx, cfear_odometry* o, const float* d_xyi
   if (o->profile && (rc = odo_timed_event(ctx, o, o->stage_events, ctx->stream)) != CFEAR_OK) return rc;
   launch_register_step(OP, o->B, ctx->stream, o);
   if (o->profile && (rc = odo_timed_event(ctx, o, o->stage_events, ctx->stream)) != CFEAR_OK) return rc;
+  o->surf_ready = OP.cs.ctx != nullptr;
   o->step_no++;
   CFEAR_HIP_CHECK(ctx, hipGetLastError());
   return CFEAR_OK;
@@ -1488,6 +1666,7 @@ int cfear_odometry_step_device(cfear_ctx* ctx, cfear_odometry* o, const uint8_t*
     if (o->profile && (rc = odo_timed_event(ctx, o, o->stage_events, so)) != CFEAR_OK) return rc;
   }
   if (o->overlap) o->filt_pending[buf] = true;
+  o->surf_ready = OP.cs.ctx != nullptr;
   o->step_no++;
   CFEAR_HIP_CHECK(ctx, hipGetLastError());
   return CFEAR_OK;
@@ -1682,6 +1861,8 @@ static int replay_impl_queue(cfear_ctx* ctx, cfear_odometry* o, const uint8_t* f
   if (rc != CFEAR_OK) return rc;
   const int nchunks = (n_sweeps + chunk - 1) / chunk;
   OdoParams OP = odo_params(ctx, o);
+  if (!o->cov_on) OP.cs.ctx = nullptr;  // the replay routes do not record for cost surfaces
+  o->surf_ready = false;
   const bool persistent = o->B <= ctx->tune_replay_persistent_max && !OP.phase_times && !OP.wg_times;
   if (on_device) {  // the sweeps are ready at this point of the context stream: the replay stream (which reads them) starts there
     CFEAR_HIP_CHECK(ctx, hipEventRecord(o->rp_in, ctx->stream));
@@ -1826,6 +2007,86 @@ int cfear_odometry_set_cov_sampling(cfear_ctx* ctx, cfear_odometry* o, int enabl
   CFEAR_HIP_CHECK(ctx, hipMemset(o->d_cov_ctx, 0, sizeof(CovSampleCtx) * (size_t)o->B));
   o->cov_m = m; o->cov_scaler = covariance_scaler; o->cov_on = true;
   return CFEAR_OK;
+}
+
+// ---- cost surfaces on the batched step (surface_dev.h) ---------------------------------------------------------------
+int cfear_odometry_set_surface_recording(cfear_ctx* ctx, cfear_odometry* o, int enable) {
+  if (!ctx || !o) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_set_surface_recording: bad argument");
+  if (!enable) { o->surf_on = false; return CFEAR_OK; }
+  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  if (!o->d_cov_ctx) {
+    { const int jrc = odo_join(ctx, o); if (jrc != CFEAR_OK) return jrc; }
+    CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    if (hipMalloc(&o->d_cov_ctx, sizeof(CovSampleCtx) * (size_t)o->B) != hipSuccess) return cfear_fail(ctx, CFEAR_ERR_NOMEM, "hipMalloc surface records");
+    CFEAR_HIP_CHECK(ctx, hipMemset(o->d_cov_ctx, 0, sizeof(CovSampleCtx) * (size_t)o->B));
+  }
+  o->surf_on = true;
+  return CFEAR_OK;
+}
+
+int cfear_odometry_surface(cfear_ctx* ctx, cfear_odometry* o, double res, int width, double* d_surface, int* n_used, int* itr_used,
+                           double* poses_used) {
+  if (!ctx || !o || !d_surface) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_surface: bad argument");
+  if (!o->surf_on && !o->cov_on)
+    return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_surface: nothing is recorded (cfear_odometry_set_surface_recording)");
+  int pixels = 0, vx = 0, vy = 0;
+  {
+    const int rc = cfear_surface_dims(res, width, 0.0, 0.0, &pixels, &vx, &vy);
+    if (rc == CFEAR_ERR_INVALID) return cfear_fail(ctx, rc, "odometry_surface: res must be finite and > 0, width >= 0");
+    if (rc != CFEAR_OK) return cfear_fail(ctx, rc, "odometry_surface: more than CFEAR_SURFACE_MAX_SIDE pixels per side");
+  }
+  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  { const int jrc = odo_join(ctx, o); if (jrc != CFEAR_OK) return jrc; }
+  const int B = o->B;
+  // what the last step's registrations used: the grid of each is centred on its recorded pose (computed here, on the host)
+  std::vector<CovSampleCtx> rec;
+  if (o->surf_ready) {
+    rec.resize((size_t)B);
+    CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(rec.data(), o->d_cov_ctx, sizeof(CovSampleCtx) * (size_t)B, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  const int cap_rc = odo_capacity_check(ctx, o, "odometry_surface");  // (the stream is idle: the surfaces are computed all the same)
+  if (pixels > o->surf_px_cap) {
+    for (void** p : {(void**)&o->d_surf_hdr, (void**)&o->d_surf_coords, (void**)&o->d_surf_nxy}) { if (*p) (void)hipFree(*p); *p = nullptr; }
+    o->surf_px_cap = 0;
+    if (hipMalloc(&o->d_surf_hdr, sizeof(SurfHdr) * (size_t)B) != hipSuccess ||
+        hipMalloc(&o->d_surf_coords, sizeof(double) * 2 * (size_t)pixels * B) != hipSuccess ||
+        hipMalloc(&o->d_surf_nxy, sizeof(int) * 2 * (size_t)B) != hipSuccess)
+      return cfear_fail(ctx, CFEAR_ERR_NOMEM, "hipMalloc surface buffers");
+    o->surf_px_cap = pixels;
+  }
+  std::vector<double> coords(2 * (size_t)pixels * B, 0.0);
+  std::vector<int> nxy(2 * (size_t)B, 0);
+  for (int q = 0; q < B; q++) {
+    const int n = o->surf_ready ? rec[q].n : 0;
+    if (n >= 2) {
+      const double* last = rec[q].pose + 3 * (n - 1);
+      nxy[2 * q] = cfear_surface_axis(last[0], res, width, pixels, coords.data() + (size_t)q * 2 * pixels);
+      nxy[2 * q + 1] = cfear_surface_axis(last[1], res, width, pixels, coords.data() + (size_t)q * 2 * pixels + pixels);
+    }
+    if (n_used) n_used[q] = n >= 2 ? n : 0;
+    if (itr_used) itr_used[q] = n >= 2 ? rec[q].itr : 0;
+    if (poses_used) {
+      double* d = poses_used + (size_t)q * 3 * MAX_SCANS;
+      for (int i = 0; i < 3 * MAX_SCANS; i++) d[i] = (n >= 2 && i < 3 * n) ? rec[q].pose[i] : 0.0;
+    }
+  }
+  CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(o->d_surf_coords, coords.data(), sizeof(double) * coords.size(), hipMemcpyHostToDevice, ctx->stream));
+  CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(o->d_surf_nxy, nxy.data(), sizeof(int) * nxy.size(), hipMemcpyHostToDevice, ctx->stream));
+  OdoParams OP = odo_params(ctx, o);
+  OP.cs.ctx = o->d_cov_ctx;
+  if (o->surf_ready) {
+    hipLaunchKernelGGL(surface_build_step_kernel<CFEAR_SURFACE_NAIVE != 0>, dim3(B), dim3(BLOCK_R), 0, ctx->stream, OP, o->d_scratch_hdr, o->d_surf_hdr,
+                       o->d_surf_coords, o->d_surf_nxy, pixels, d_surface);
+    CFEAR_HIP_CHECK(ctx, hipGetLastError());
+  } else {  // no step since the last reset / replay: no blocks, no visited cells (all NaN)
+    CFEAR_HIP_CHECK(ctx, hipMemsetAsync(o->d_surf_hdr, 0, sizeof(SurfHdr) * (size_t)B, ctx->stream));
+  }
+  if (!CFEAR_SURFACE_NAIVE || !o->surf_ready) {
+    launch_surface_eval(OP.rp, B, o->d_surf_hdr, o->d_surf_coords, o->d_surf_nxy, pixels, d_surface, ctx->stream);
+    CFEAR_HIP_CHECK(ctx, hipGetLastError());
+  }
+  return cap_rc;
 }
 
 int cfear_odometry_cov_samples(cfear_ctx* ctx, cfear_odometry* o, int sequence, double* costs, int* sampled) {

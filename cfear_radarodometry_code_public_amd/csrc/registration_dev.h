@@ -1346,6 +1346,18 @@ __device__ __forceinline__ int ctl_lm_next_body(LRegShared* sh) {
   }
 }
 
+// guess_inf_sqrt = Cov6to3(cov).inverse().llt().matrixL() (n_scan_normal.cpp:374) of a 6x6 row-major covariance: rows / columns x, y,
+// yaw (registration.cpp:123-129), the inverse by cofactors, its lower Cholesky factor row-major into pL
+__device__ __forceinline__ void prior_sqrt_info(const double* Cq, double pL[9]) {
+  const double a = Cq[0], b = Cq[1], c = Cq[5], d = Cq[6], e = Cq[7], f5 = Cq[11], g6 = Cq[30], h = Cq[31], i9 = Cq[35];  // registration.cpp:123-129
+  const double A00 = e * i9 - f5 * h, A10 = f5 * g6 - d * i9, A11 = a * i9 - c * g6, A20 = d * h - e * g6, A21 = b * g6 - a * h, A22 = a * e - b * d;
+  const double det = a * A00 + b * A10 + c * A20;
+  const double i00 = A00 / det, i10 = A10 / det, i11 = A11 / det, i20 = A20 / det, i21 = A21 / det, i22 = A22 / det;  // lower triangle of the inverse
+  const double l00 = sqrt(i00), l10 = i10 / l00, l20 = i20 / l00;
+  const double l11 = sqrt(i11 - l10 * l10), l21 = (i21 - l20 * l10) / l11;
+  const double l22 = sqrt(i22 - l20 * l20 - l21 * l21);
+  pL[0] = l00; pL[1] = 0; pL[2] = 0; pL[3] = l10; pL[4] = l11; pL[5] = 0; pL[6] = l20; pL[7] = l21; pL[8] = l22;
+}
 // mahalanobisDistanceError (n_scan_normal.h:259-290) at x: r = L (alpha (guess - x)), J = -alpha L, no loss
 // (forceinline, by value: a NormalEq handed to an out-of-line function by reference would live in per-thread scratch)
 __device__ __forceinline__ NormalEq add_prior(const LRegShared* sh, NormalEq E, double x0, double x1, double x2) {
@@ -1522,15 +1534,9 @@ __device__ inline int register_block(ScanDev* const* scans, int n, double* poses
     sh->xcur[0] = par_lds[L]; sh->xcur[1] = par_lds[L + 1]; sh->xcur[2] = par_lds[L + 2];
     sh->prior_on = 0;
     if (prior_cov6) {  // :373-376: guess_inf_sqrt = Cov6to3(cov).inverse().llt().matrixL(), alpha = sqrt(#source cells)
-      const double* Cq = prior_cov6;
-      const double a = Cq[0], b = Cq[1], c = Cq[5], d = Cq[6], e = Cq[7], f5 = Cq[11], g6 = Cq[30], h = Cq[31], i9 = Cq[35];  // registration.cpp:123-129
-      const double A00 = e * i9 - f5 * h, A10 = f5 * g6 - d * i9, A11 = a * i9 - c * g6, A20 = d * h - e * g6, A21 = b * g6 - a * h, A22 = a * e - b * d;
-      const double det = a * A00 + b * A10 + c * A20;
-      const double i00 = A00 / det, i10 = A10 / det, i11 = A11 / det, i20 = A20 / det, i21 = A21 / det, i22 = A22 / det;  // lower triangle of the inverse
-      const double l00 = sqrt(i00), l10 = i10 / l00, l20 = i20 / l00;
-      const double l11 = sqrt(i11 - l10 * l10), l21 = (i21 - l20 * l10) / l11;
-      const double l22 = sqrt(i22 - l20 * l20 - l21 * l21);
-      sh->pL[0] = l00; sh->pL[1] = 0; sh->pL[2] = 0; sh->pL[3] = l10; sh->pL[4] = l11; sh->pL[5] = 0; sh->pL[6] = l20; sh->pL[7] = l21; sh->pL[8] = l22;
+      double pL[9];
+      prior_sqrt_info(prior_cov6, pL);
+      for (int k = 0; k < 9; k++) sh->pL[k] = pL[k];
       sh->pguess[0] = par_lds[L]; sh->pguess[1] = par_lds[L + 1]; sh->pguess[2] = par_lds[L + 2];  // Affine3dToEigVectorXYeZ(Tsrc.back()) (:93-94)
       sh->palpha = sqrt((double)scans[n - 1]->n_cells);
       sh->prior_on = 1;

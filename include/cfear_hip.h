@@ -281,6 +281,25 @@ int cfear_cov_by_sampling(cfear_ctx* ctx, cfear_scan* const* scans, int n, const
                           double yaw_range, int samples_per_axis, double covariance_scaler, double final_cost,
                           int num_residuals, double* cov6, int* success, double* sample_costs);
 
+/* void GetSurface(std::vector<MapNormalPtr>& scans, std::vector<Eigen::Affine3d>& Tsrc, std::vector<Matrix6d>& reg_cov,
+ *                 bool soft_constraints, Eigen::MatrixXd& surface, double res, int width) (n_scan_normal.cpp:29-65).
+ * The grid: pixels = ceil(2.0 * width / res) + 1 per side (:47); row i walks x, column j walks y, both by the reference's loop
+ * `for (v = v0 - width; v <= v0 + width; v = v + res)` accumulated in double from the last pose (x0, y0), so each axis visits
+ * pixels or pixels - 1 values depending on the estimate. cfear_surface_dims: pixels and the values visited along x (*nx) and y (*ny);
+ * host only (no context, no device). CFEAR_ERR_INVALID for a res that is not finite or <= 0 or a width < 0, CFEAR_ERR_UNSUPPORTED
+ * above CFEAR_SURFACE_MAX_SIDE pixels per side. */
+#define CFEAR_SURFACE_MAX_SIDE 2048
+int cfear_surface_dims(double res, int width, double x0, double y0, int* pixels, int* nx, int* ny);
+/* GetSurface itself: every scan fixed but the last (InitFixedBlocks, :32), the problem built ONCE at the round-tripped poses
+ * (Affine3dToVectorXYeZ, :35-38) with the object's itr_ (1 = double association radius, :222) - the associations are not rebuilt
+ * per pixel, unlike GetCost - then ceres::Problem::Evaluate at every pixel (x, y, yaw of the estimate): 1/2 sum w rho(|r|^2), plus
+ * with prior_cov6 (= reg_cov.back(), 36 doubles row-major; NULL = soft_constraints false) the Mahalanobis prior of
+ * cfear_register_soft when the problem has more than one residual (:370-377). Nothing is refused for too few residuals (a problem
+ * without blocks gives zeros). surface: pixels * pixels doubles, row-major, host memory; cells the reference's loops never reach
+ * (which it leaves uninitialised) are NaN. nx, ny (optional): as cfear_surface_dims. Synchronises. */
+int cfear_get_surface(cfear_ctx* ctx, cfear_scan* const* scans, int n, const double* poses_xyt, const double* prior_cov6, int itr,
+                      double res, int width, double* surface, int* nx, int* ny);
+
 /* ---- Batched odometry: OdometryKeyframeFuser::pointcloudCallback for B independent sequences ---
  * (odometrykeyframefuser.cpp:143-259, :397-411) with the filter of radar_driver.cpp:48-70 in front: k-strongest, or - with
  * cfear_params.filter_type = CFEAR_FILTER_CACFAR at creation - azimuth CA-CFAR (radar_driver.cpp:52-56; the peaks cloud stays empty
@@ -330,6 +349,22 @@ int cfear_odometry_set_cov_sampling(cfear_ctx* ctx, cfear_odometry* odo, int ena
  * cov_samples_to_file_as_well would dump) and whether the sampled covariance was used (cov_sampled_success; 0 on a sequence's first
  * sweep, which samples nothing). Either pointer may be NULL. CFEAR_ERR_INVALID while sampling is off. Synchronises. */
 int cfear_odometry_cov_samples(cfear_ctx* ctx, cfear_odometry* odo, int sequence, double* costs, int* sampled);
+/* Cost surfaces of the batched step (GetSurface, n_scan_normal.cpp:29-65, as cfear_get_surface). enable = 1: from the next step on,
+ * every registration records the scans, poses and itr_ it used (the record the cost-sampling covariance keeps; the sampling stage
+ * itself does not run unless cfear_odometry_set_cov_sampling is on). Off by default; poses, covariances and summaries do not change;
+ * cfear_odometry_reset keeps the setting. The replay routes do not record. */
+int cfear_odometry_set_surface_recording(cfear_ctx* ctx, cfear_odometry* odo, int enable);
+/* One surface per sequence around its last registration: the recorded scans, poses and itr_, no soft prior (the batched route has
+ * none), with one build launch and one evaluation launch for all sequences. d_surface: caller-owned device buffer of n_sequences *
+ * pixels * pixels doubles (pixels: cfear_surface_dims), sequence q's surface row-major at q * pixels * pixels; unvisited cells NaN,
+ * and a sequence without a registration in the last step (its first sweep) or no step since the last reset / replay: all NaN.
+ * Optional host outputs of what was evaluated: n_used (n_sequences: scans of the problem, 0 = none), itr_used (n_sequences),
+ * poses_used (n_sequences * 192 doubles: the (x, y, theta) of up to 64 scans, keyframes then the registered pose) - with
+ * cfear_get_surface on the same scans they give the same surface. Reads the records after joining the step (synchronises the
+ * context stream once); the launches are stream-ordered on the context stream, the result is valid until the next step or reset.
+ * CFEAR_ERR_INVALID while neither the recording nor the cost sampling is on. */
+int cfear_odometry_surface(cfear_ctx* ctx, cfear_odometry* odo, double res, int width, double* d_surface, int* n_used, int* itr_used,
+                           double* poses_used);
 /* Has any scan of this object been truncated - more oriented surface points than CFEAR_TUNE_MAX_CELLS, or a cloud with more points than the object
  * holds? Synchronises the context stream; returns CFEAR_OK or CFEAR_ERR_CAPACITY (with the message the reading calls give). For callers of the
  * asynchronous cfear_odometry_replay_device, which read their records on the device and never pass through poses / summary / replay_host.

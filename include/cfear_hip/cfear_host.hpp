@@ -19,6 +19,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <fstream>
 #include <map>
 #include <memory>
 #include <stdexcept>
@@ -636,6 +637,27 @@ class n_scan_normal_reg {
     score_ = score / (double)(nres > 1 ? nres : 1);  // :211
     return true;
   }
+  // void GetSurface(scans, Tsrc, reg_cov, soft_constraints, surface, res, width) (n_scan_normal.cpp:29-65): the cost of the problem built
+  // once at Tsrc (this object's itr_, :222) at every (x, y) of the grid around Tsrc.back(), yaw fixed; cells the reference's loops
+  // never reach (it leaves them uninitialised) are NaN here
+  void GetSurface(std::vector<MapNormalPtr>& scans, std::vector<Affine3d>& Tsrc, std::vector<Matrix6d>& reg_cov, bool soft_constraints, MatrixXd& surface,
+                  double res, int width) {
+    const size_t n = scans.size();
+    if (Tsrc.size() != n || reg_cov.size() != n || n < 2) throw std::runtime_error("GetSurface: scans/Tsrc/reg_cov size mismatch");  // assert at :31
+    const DevicePtr dev = device(scans);
+    ScopedParams sp(dev, my_params(dev));
+    std::vector<cfear_scan*> h(n); std::vector<double> poses(3 * n);
+    for (size_t i = 0; i < n; i++) { h[i] = scans[i]->handle(); poses[3 * i] = cfear_tx(Tsrc[i]); poses[3 * i + 1] = cfear_ty(Tsrc[i]); poses[3 * i + 2] = cfear_yaw(Tsrc[i]); }
+    int pixels = 0, nx = 0, ny = 0;
+    dev->check(cfear_surface_dims(res, width, poses[3 * (n - 1)], poses[3 * (n - 1) + 1], &pixels, &nx, &ny), "cfear_surface_dims");
+    double prior[36];
+    if (soft_constraints) for (int a = 0; a < 6; a++) for (int b = 0; b < 6; b++) prior[6 * a + b] = reg_cov.back()(a, b);
+    std::vector<double> out((size_t)pixels * pixels);
+    dev->check(cfear_get_surface(dev->ctx(), h.data(), (int)n, poses.data(), soft_constraints ? prior : nullptr, (int)itr_, res, width, out.data(), &nx, &ny),
+               "cfear_get_surface");
+    surface.resize(pixels, pixels);
+    for (int i = 0; i < pixels; i++) for (int j = 0; j < pixels; j++) surface(i, j) = out[(size_t)i * pixels + j];
+  }
   double getScore() { return score_; }
   void getScore(double& score, int& num_residuals) { score = score_; num_residuals = summary_.num_residuals; }  // n_scan_normal.h:51
   bool GetCovarianceScaler(double& cov_scale) {  // n_scan_normal.cpp:435-441
@@ -672,6 +694,17 @@ class OdometryKeyframeFuser {
   };
   OdometryKeyframeFuser(const Parameters& pars, bool disable_callback = false) : par(pars) { Init(disable_callback); }  // odometrykeyframefuser.h:187
   OdometryKeyframeFuser(const DevicePtr& dev, const Parameters& pars, bool disable_callback = true) : dev_(dev), par(pars) { Init(disable_callback); }
+  // void PrintSurface(path, surface) (odometrykeyframefuser.cpp:414-426): one line per row, values in std::ofstream's default format
+  void PrintSurface(const std::string& path, const MatrixXd& surface) {
+    std::ofstream myfile;
+    myfile.open(path);
+    for (int i = 0; i < surface.rows(); i++)
+      for (int j = 0; j < surface.cols(); j++) {
+        if (j == surface.cols() - 1) myfile << surface(i, j) << std::endl;
+        else myfile << surface(i, j) << " ";
+      }
+    myfile.close();
+  }
   // void pointcloudCallback(cloud_filtered, cloud_filtered_peaks, Tcurr, t [, cov]) (odometrykeyframefuser.cpp:397-411).
   // cloud / cloud_peaks are compensated in place like the reference does (:147-150).
   void pointcloudCallback(CloudPtr& cloud_filtered, CloudPtr& cloud_filtered_peaks, Affine3d& Tcurr, uint64_t t, Matrix6d* cov_curr = nullptr) {

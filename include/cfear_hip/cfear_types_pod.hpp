@@ -31,6 +31,14 @@ typedef struct Matrix6dT {
   double operator()(int r, int c) const { return m[r][c]; }
   double& operator()(int r, int c) { return m[r][c]; }
 } Matrix6d;
+struct MatrixXd {  // Eigen::MatrixXd restricted to what GetSurface / PrintSurface use: column-major storage, (i, j) access
+  std::vector<double> v; long r = 0, c = 0;
+  void resize(long rows, long cols) { r = rows; c = cols; v.assign((size_t)(rows * cols), 0.0); }
+  long rows() const { return r; }
+  long cols() const { return c; }
+  double operator()(long i, long j) const { return v[(size_t)(i + j * r)]; }
+  double& operator()(long i, long j) { return v[(size_t)(i + j * r)]; }
+};
 
 // Eigen::Affine3d restricted to what the path uses: planar rigid motions (vectorToAffine3d, registration.cpp:130-136)
 struct Affine3d {

@@ -41,6 +41,7 @@ typedef cv_bridge::CvImagePtr CvImagePtr;
 typedef Eigen::Vector2d Vector2d;
 typedef Eigen::Matrix2d Matrix2d;
 typedef Eigen::Matrix<double, 6, 6> Matrix6d;  // registration.h:41
+typedef Eigen::MatrixXd MatrixXd;               // GetSurface / PrintSurface (n_scan_normal.h:43, odometrykeyframefuser.h:236)
 typedef Eigen::Affine3d Affine3d;
 
 inline CloudPtr cfear_make_cloud() { return CloudPtr(new PointCloudXYZI()); }
