@@ -115,3 +115,68 @@ def surface(oracle, scans, poses, p, itr, res, width, prior_cov6=None):
         for j, y in enumerate(ys):
             out[i, j] = evaluate(oracle, blocks, p, (x, y, par[-1][2]), prior)[0]
     return out
+
+
+def loss_rho(loss, a, s):
+    """rho(s) of the registration's losses (registration.cpp:78-97) on an array of squared norms: the Ceres 2.0 closed forms that
+    test_oracle_cpu.py pins for oracle.loss_eval, operation for operation (0 none, 1 Huber, 2 Cauchy, 3 SoftLOne, 4 Huber(1) of
+    Cauchy(1), 5 Tukey)"""
+    s = np.asarray(s, dtype=np.float64)
+    b = a * a
+    if loss == 1:
+        return np.where(s > b, 2.0 * a * np.sqrt(s) - b, s)
+    if loss == 2:
+        return b * np.log(1.0 + s * (1.0 / b))
+    if loss == 3:
+        return 2.0 * b * (np.sqrt(1.0 + s * (1.0 / b)) - 1.0)
+    if loss == 5:
+        v = 1.0 - s / b
+        return np.where(s <= b, b / 3.0 * (1.0 - (v * v) * v), b / 3.0)
+    if loss == 4:
+        return loss_rho(1, 1.0, loss_rho(2, 1.0, s))
+    return s.copy()
+
+
+def evaluate_grid(blocks, p, xs, ys, yaw, prior=None):
+    """evaluate()'s cost at every (x, y) of xs x ys, yaw fixed: vectorised over the pixels, the blocks summed one after the other in
+    residual-block order (the summation order of every pixel is evaluate()'s)"""
+    X = np.asarray(xs, dtype=np.float64)[:, None]
+    Y = np.asarray(ys, dtype=np.float64)[None, :]
+    R, _ = aff(0.0, 0.0, yaw)
+    cost = np.zeros((X.shape[0], Y.shape[1]))
+    for tm, extra, sm, w in blocks:
+        rs = R @ sm
+        px, py = rs[0] + X, rs[1] + Y
+        if p.cost == P2L:
+            r0 = (px - tm[0]) * extra[0] + (py - tm[1]) * extra[1]
+            sq = r0 * r0
+        elif p.cost == P2D:
+            dx, dy = px - tm[0], py - tm[1]
+            r0, r1 = extra[0] * dx, extra[1] * dx + extra[2] * dy
+            sq = r0 * r0 + r1 * r1
+        else:
+            r0, r1 = tm[0] - px, tm[1] - py
+            sq = r0 * r0 + r1 * r1
+        cost += 0.5 * w * loss_rho(p.loss, p.loss_limit, sq)
+    if prior is not None:
+        L, guess, alpha = prior
+        d0, d1, d2 = alpha * (guess[0] - X), alpha * (guess[1] - Y), alpha * (guess[2] - yaw)
+        acc = 0.0
+        for i in range(3):
+            r = (L[i, 0] * d0 + L[i, 1] * d1) + L[i, 2] * d2
+            acc = acc + r * r
+        cost += 0.5 * acc
+    return cost
+
+
+def surface_grid(oracle, scans, poses, p, itr, res, width, prior_cov6=None, with_blocks=False):
+    """surface() for large grids: the same problem, the same result, the pixels vectorised (evaluate_grid). with_blocks: also the
+    number of residual blocks, for tests that assert which regime they are in"""
+    par, blocks = build_blocks(scans, poses, p, itr)
+    nres = len(blocks) * (1 if p.cost == P2L else 2)
+    prior = prior_terms(scans, par, prior_cov6) if (prior_cov6 is not None and nres > 1) else None
+    pixels = int(math.ceil(2.0 * width / res)) + 1
+    xs, ys = axis(par[-1][0], res, width, pixels), axis(par[-1][1], res, width, pixels)
+    out = np.full((pixels, pixels), np.nan)
+    out[:len(xs), :len(ys)] = evaluate_grid(blocks, p, xs, ys, par[-1][2], prior)
+    return (out, len(blocks)) if with_blocks else out

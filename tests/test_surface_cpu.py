@@ -82,3 +82,54 @@ def test_surface_dims_refuses(hip_lib, res, width, rc):
 
 def test_surface_dims_cap_is_inclusive(hip_lib):
     assert capi.surface_dims(2.0 / 2047, 1)[0] == 2048  # ceil(2047) + 1: CFEAR_SURFACE_MAX_SIDE itself is allowed
+
+
+# ---- surface_grid: the vectorised restatement the large-grid GPU tests compare with ---------------------------------------------
+PRIOR = np.diag([0.05 ** 2, 0.04 ** 2, 1.0, 1.0, 1.0, 0.01 ** 2])
+
+
+@pytest.mark.parametrize("cost,loss,wopt,itr,n,soft,res,width", [
+    (1, 1, 4, 2, 3, False, 0.3, 1),   # (test_surface_gpu.py's parametrisation) 8 pixels, 7 visited: a NaN row and column
+    (1, 2, 0, 1, 2, True, 0.25, 1),
+    (2, 1, 1, 2, 4, False, 0.5, 2),
+    (2, 3, 4, 1, 5, True, 0.3, 1),
+    (0, 5, 0, 2, 3, True, 0.25, 1),
+    (0, 4, 1, 1, 4, False, 0.5, 1),
+    (1, 3, 1, 2, 5, False, 0.5, 1),
+    (2, 2, 0, 2, 2, False, 0.3, 1),
+    (0, 0, 4, 2, 3, True, 0.3, 1),    # no loss at all
+])
+def test_surface_grid_is_surface(oracle, cost, loss, wopt, itr, n, soft, res, width):
+    """both sum the same terms in the same order per pixel: what is left is the ulps between numpy's and the oracle's log / sqrt and
+    between numpy's matrix products and the scalar ones"""
+    p = oracle.default_params(range_res=RR, k_strongest=12, z_min=60.0, res=3.0, weight_intensity=1, loss_limit=0.1, cost=cost, loss=loss,
+                              weight_opt=wopt)
+    scans, gt = scans_of(oracle, n, p, seed=29)
+    poses = gt[:n].copy()
+    poses[-1] += [0.11, -0.06, 0.004]
+    prior = PRIOR if soft else None
+    exp = surface_ref.surface(oracle, scans, poses, p, itr, res, width, prior)
+    got, nblk = surface_ref.surface_grid(oracle, scans, poses, p, itr, res, width, prior, with_blocks=True)
+    assert nblk == len(surface_ref.build_blocks(scans, poses, p, itr)[1]) > 0
+    assert got.shape == exp.shape and np.array_equal(np.isnan(got), np.isnan(exp))
+    if (res, width) == (0.3, 1):
+        assert np.all(np.isnan(exp[7])) and np.all(np.isnan(exp[:, 7])) and np.all(np.isfinite(exp[:7, :7]))
+    m = ~np.isnan(exp)
+    rel = np.max(np.abs(got[m] - exp[m]) / np.abs(exp[m]))
+    assert rel <= 3.9e-15, rel  # ten times the largest measured over these cases, 3.81e-16 (cost 1, SoftLOne); the GPU bar is 1e-9
+
+
+@pytest.mark.parametrize("loss,a", [(0, 0.1), (1, 0.1), (2, 0.1), (3, 0.1), (4, 0.1), (5, 0.1), (1, 0.5), (2, 0.2), (3, 0.3), (5, 0.5), (4, 1.0)])
+def test_numpy_losses_are_the_oracle_losses(oracle, loss, a):
+    """surface_ref.loss_rho against oracle.loss_eval from 0 to 10^4 times loss_limit^2 (and past 1, where loss 4's inner Huber
+    switches), with the branch points and their neighbours"""
+    b = a * a
+    s = np.concatenate([[0.0, b, np.nextafter(b, 0), np.nextafter(b, 1), 1.0, np.nextafter(1.0, 0), np.nextafter(1.0, 2), math.e - 1,
+                         np.nextafter(math.e - 1, 0), np.nextafter(math.e - 1, 3)],
+                        np.linspace(0, 3 * b, 301), np.geomspace(1e-12, 1e4 * max(b, 1.0), 400)])
+    got = surface_ref.loss_rho(loss, a, s)
+    exp = np.array([oracle.loss_eval(loss, a, float(v))[0] for v in s])
+    assert got.shape == exp.shape and np.all(np.isfinite(got))
+    # measured: bit-identical for 0, 1, 3, 5 (IEEE sqrt and arithmetic), 2.5e-16 for the two with a log; ten times that
+    assert np.all(np.abs(got - exp) <= 2.5e-15 * np.abs(exp)), np.max(np.abs(got - exp) / np.maximum(np.abs(exp), 1e-300))
+    assert got[0] == 0.0 and exp[0] == 0.0
