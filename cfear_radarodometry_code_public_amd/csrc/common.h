@@ -82,6 +82,13 @@ static inline int cfear_fail(cfear_ctx* c, int code, const char* what, hipError_
     if (_e != hipSuccess) return cfear_fail((ctx), CFEAR_ERR_HIP, #call, _e); \
   } while (0)
 
+// a step that reports through cfear_fail itself: hand its code on
+#define CFEAR_TRY(expr)                   \
+  do {                                    \
+    const int _rc = (expr);               \
+    if (_rc != CFEAR_OK) return _rc;      \
+  } while (0)
+
 struct cfear_cloud {  // pcl::PointCloud<pcl::PointXYZI> on the device: one block, the count in its first 16 bytes
   int cap = 0;
   float* d_xyi = nullptr;  // [cap][3] x, y, intensity (= block + 16)

@@ -1,35 +1,20 @@
 // odometry_step_dev.h -- one sweep of one sequence of the batched odometry (OdometryKeyframeFuser::processFrame,
-// odometrykeyframefuser.cpp:143-259, split after the feature build :161): the device-side state, the kernel parameter block
-// and the two step bodies, shared by pipeline.hip (one launch per stage and sweep) and replay.hip (a persistent workgroup per
-// sequence that walks a whole chunk of sweeps).
+// odometrykeyframefuser.cpp:143-259, split after the feature build :161): the device-side state, the kernel parameter block,
+// the launchers of the translation units that compile it and the two step bodies, shared by pipeline.hip (one launch per stage
+// and sweep), register_step.hip / register_step_large.hip (the registration stage in other shapes) and replay.hip (a persistent
+// workgroup per sequence that walks a whole chunk of sweeps).
 #pragma once
 #include "registration_dev.h"
 #include "features_compact_dev.h"
 
+#include <type_traits>
+
 using namespace cfear_dev;
 
-namespace {
-
-constexpr int BLOCK_F = CFEAR_FEAT_BLOCK;   // features / cloud kernels: two workgroups per compute unit (features_compact_dev.h)
-constexpr int BLOCK_R = CFEAR_REG_BLOCK;   // registration kernels: 256 threads (4 waves = one per SIMD) in pipeline.hip
-static_assert(BLOCK_R >= 64 * CFEAR_EVAL_WAVES, "the controller sums the partial results of CFEAR_EVAL_WAVES waves unconditionally");
-constexpr int MAX_SCANS = 64;  // keyframes + current: the layout of SeqState in memory (the same in every translation unit, whatever CFEAR_REG_MAX_SCANS)
-static_assert(CFEAR_REG_MAX_SCANS <= MAX_SCANS, "a registration cannot have more scans than a sequence keeps");
-static_assert(FeatLdsC::total <= 80384, "two feature workgroups per compute unit");
-struct RegLds {  // registration kernels
-  static constexpr size_t red_d = 0;                                  // 10 sums x CFEAR_RED_STRIDE waves
-  static constexpr size_t par = red_d + 10 * CFEAR_RED_STRIDE * sizeof(double);        // 3*CFEAR_REG_MAX_SCANS doubles
-  static constexpr size_t red_i = par + 3 * CFEAR_REG_MAX_SCANS * sizeof(double);  // 64 ints
-  static constexpr size_t scanptr = red_i + 64 * sizeof(int);        // CFEAR_REG_MAX_SCANS pointers
-  static constexpr size_t regsh = scanptr + CFEAR_REG_MAX_SCANS * sizeof(void*);  // RegShared
-  static constexpr size_t total = (regsh + sizeof(RegShared) + 15) / 16 * 16;
-};
-
-#ifndef CFEAR_REG_LDS_BUDGET
-#define CFEAR_REG_LDS_BUDGET 53760  // three registration workgroups per compute unit (replay.hip: one, with the whole unit's LDS)
-#endif
-static_assert(RegLds::total + sizeof(double) * CFEAR_MATCH_LDS_DOUBLES <= CFEAR_REG_LDS_BUDGET,
-              "registration kernels: more than 53,760 B of LDS costs the third workgroup per compute unit");
+// ---- what the host and every translation unit see alike: the kernels' parameter blocks and the launchers -----------------------------
+// Nothing here depends on a per-unit macro (CFEAR_REG_MAX_SCANS, CFEAR_REG_BLOCK, CFEAR_MATCH_LDS_CAP, ...): one definition, one layout.
+namespace cfear_dev {
+constexpr int MAX_SCANS = 64;  // keyframes + current: the layout of SeqState in memory (whatever CFEAR_REG_MAX_SCANS a unit compiles its registration for)
 
 // Global per-sequence working memory (also one per context for the per-call API).
 struct BlockScratch {
@@ -97,6 +82,59 @@ struct OdoParams {
   int* flags;  // word 0 for the odometry object, word 1 + q for sequence q: bit 0 = some scan had more cells than its block holds, bit 1 = some cloud had more points
                // than the object is sized for (both CFEAR_ERR_CAPACITY); null: cannot happen
 };
+
+static_assert(sizeof(SeqState) == 3 * sizeof(Aff2) + 4 * sizeof(int) + MAX_SCANS * (sizeof(int) + sizeof(Aff2)), "SeqState is sized by the fixed MAX_SCANS");
+static_assert(sizeof(CovSampleCtx) == 4 * sizeof(int) + sizeof(double) + MAX_SCANS * (sizeof(int) + 3 * sizeof(double)), "CovSampleCtx is sized by the fixed MAX_SCANS");
+static_assert(std::is_trivially_copyable<OdoParams>::value && std::is_trivially_copyable<BlockScratch>::value && std::is_trivially_copyable<SeqState>::value,
+              "kernel arguments and device state are copied byte for byte");
+}  // namespace cfear_dev
+
+// The launchers that cross translation units (each unit compiles the step bodies below for its own workgroup shape), called by pipeline.hip.
+// register_step.hip: the batched registration step kernel for registrations of up to CFEAR_STEP_SMALL_SCANS scans
+__attribute__((visibility("hidden"))) void cfear_launch_register_step_small(const OdoParams& P, int count, hipStream_t st, SeqState* states, const BlockScratch* scratch,
+                                                                           double* cov_work, cfear_reg_summary* summaries, double* poses_out);
+// register_step_large.hip: ... of more scans (submap_scan_size 8 .. 63), a compute unit per registration
+__attribute__((visibility("hidden"))) void cfear_launch_register_step_large(const OdoParams& P, int count, hipStream_t st, SeqState* states, const BlockScratch* scratch,
+                                                                           double* cov_work, cfear_reg_summary* summaries, double* poses_out);
+// replay.hip: features -> registration of `cnt` consecutive sweeps of every sequence in one launch (a persistent workgroup per sequence)
+__attribute__((visibility("hidden"))) void cfear_launch_replay_chunk(const uint32_t* d_slots, int cnt, int B, const double* d_trig, const OdoParams& OP, SeqState* states,
+                                                                    const BlockScratch* scratch, double* cov_work, cfear_reg_summary* summaries, double* poses_out,
+                                                                    cfear_sweep_record* records, hipStream_t stream);
+// ... from the clouds of a chunk ([cnt][B][cap][3] floats, [cnt][B] counts) instead of slots
+__attribute__((visibility("hidden"))) void cfear_launch_replay_chunk_cloud(const float* d_xyi, int cap, const int* d_counts, int cnt, int B, const OdoParams& OP,
+                                                                          SeqState* states, const BlockScratch* scratch, double* cov_work,
+                                                                          cfear_reg_summary* summaries, double* poses_out, cfear_sweep_record* records, hipStream_t stream);
+// A registration step kernel KERNEL<TIMED, KCOST> of this unit on `st`: one instantiation per cost metric (the evaluation inline, no run-time
+// dispatch), the per-phase timers with the cost read at run time. The arguments after `st` are the kernel's, behind the OdoParams P.
+#define CFEAR_LAUNCH_REG_BY_COST(KERNEL, P, count, st, ...)                                                                                          \
+  do {                                                                                                                                               \
+    if ((P).phase_times) hipLaunchKernelGGL((KERNEL<true, -1>), dim3(count), dim3(BLOCK_R), 0, st, P, __VA_ARGS__);                                   \
+    else if ((P).rp.cost == CFEAR_COST_P2L) hipLaunchKernelGGL((KERNEL<false, CFEAR_COST_P2L>), dim3(count), dim3(BLOCK_R), 0, st, P, __VA_ARGS__);  \
+    else if ((P).rp.cost == CFEAR_COST_P2D) hipLaunchKernelGGL((KERNEL<false, CFEAR_COST_P2D>), dim3(count), dim3(BLOCK_R), 0, st, P, __VA_ARGS__);  \
+    else hipLaunchKernelGGL((KERNEL<false, CFEAR_COST_P2P>), dim3(count), dim3(BLOCK_R), 0, st, P, __VA_ARGS__);                                     \
+  } while (0)
+
+namespace {
+
+constexpr int BLOCK_F = CFEAR_FEAT_BLOCK;   // features / cloud kernels: two workgroups per compute unit (features_compact_dev.h)
+constexpr int BLOCK_R = CFEAR_REG_BLOCK;   // registration kernels: 256 threads (4 waves = one per SIMD) in pipeline.hip
+static_assert(BLOCK_R >= 64 * CFEAR_EVAL_WAVES, "the controller sums the partial results of CFEAR_EVAL_WAVES waves unconditionally");
+static_assert(CFEAR_REG_MAX_SCANS <= MAX_SCANS, "a registration cannot have more scans than a sequence keeps");
+static_assert(FeatLdsC::total <= 80384, "two feature workgroups per compute unit");
+struct RegLds {  // registration kernels
+  static constexpr size_t red_d = 0;                                  // 10 sums x CFEAR_RED_STRIDE waves
+  static constexpr size_t par = red_d + 10 * CFEAR_RED_STRIDE * sizeof(double);        // 3*CFEAR_REG_MAX_SCANS doubles
+  static constexpr size_t red_i = par + 3 * CFEAR_REG_MAX_SCANS * sizeof(double);  // 64 ints
+  static constexpr size_t scanptr = red_i + 64 * sizeof(int);        // CFEAR_REG_MAX_SCANS pointers
+  static constexpr size_t regsh = scanptr + CFEAR_REG_MAX_SCANS * sizeof(void*);  // RegShared
+  static constexpr size_t total = (regsh + sizeof(RegShared) + 15) / 16 * 16;
+};
+
+#ifndef CFEAR_REG_LDS_BUDGET
+#define CFEAR_REG_LDS_BUDGET 53760  // three registration workgroups per compute unit (replay.hip: one, with the whole unit's LDS)
+#endif
+static_assert(RegLds::total + sizeof(double) * CFEAR_MATCH_LDS_DOUBLES <= CFEAR_REG_LDS_BUDGET,
+              "registration kernels: more than 53,760 B of LDS costs the third workgroup per compute unit");
 
 __device__ inline int next_pow2(int n) { int p = 1; while (p < n) p <<= 1; return p; }
 
@@ -351,7 +389,6 @@ __device__ __forceinline__ void register_step_body(unsigned char* lds /* RegLds:
 }
 
 
-
 #ifndef CFEAR_REG_MIN_WG
 #define CFEAR_REG_MIN_WG 3  // workgroups per compute unit the registration step kernel is compiled for (tools: A/B builds)
 #endif
@@ -361,14 +398,14 @@ __device__ __forceinline__ void register_step_body(unsigned char* lds /* RegLds:
 #else
 #define CFEAR_REG_VGPR_ATTR
 #endif
+// (the two unused parameters are launched as null: dropping them changes the kernarg layout and with it the code generated for this kernel)
 template <bool TIMED, int KCOST>
-__global__ __launch_bounds__(BLOCK_R, CFEAR_REG_MIN_WG) CFEAR_REG_VGPR_ATTR void register_step_kernel(OdoParams OP, SeqState* states, ScanDev* const* scan_slots,
-                                                                const BlockScratch* scratch, double* poses_work /*[B][MAX_SCANS*3]*/,
+__global__ __launch_bounds__(BLOCK_R, CFEAR_REG_MIN_WG) CFEAR_REG_VGPR_ATTR void register_step_kernel(OdoParams OP, SeqState* states, ScanDev* const* /*unused*/,
+                                                                const BlockScratch* scratch, double* /*unused*/,
                                                                 double* cov_work /*[B][36]*/, cfear_reg_summary* summaries,
                                                                 double* poses_out /*[B][3]*/) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[RegLds::total];
   register_step_body<TIMED, KCOST>(lds, OP.order ? OP.order[blockIdx.x] : OP.seq0 + (int)blockIdx.x, OP, states, scratch, cov_work, summaries, poses_out);
 }
-
 
 }  // namespace

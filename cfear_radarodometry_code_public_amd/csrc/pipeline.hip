@@ -230,7 +230,7 @@ __global__ __launch_bounds__(CFEAR_SURFACE_BLOCK) void surface_eval_kernel(const
 // TIMED: per-phase timestamps (tools/); the production instantiation carries no timer at all
 template <bool TIMED>
 __global__ __launch_bounds__(BLOCK_F, 4) void features_step_kernel(const uint32_t* slots_all, const double* trig, OdoParams OP,
-                                                                   const SeqState* states, ScanDev* const* scan_slots,
+                                                                   const SeqState* states, ScanDev* const* /*unused: launched as null, kept for the kernarg layout*/,
                                                                    const BlockScratch* scratch) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[FeatLdsC::total];
   features_step_body<TIMED>(lds, OP.seq0 + (int)blockIdx.x, slots_all, trig, OP, states, scratch);
@@ -400,8 +400,6 @@ BlockScratch scratch_header(unsigned char* d_base, int cap_points, int pair_cap)
   return B;
 }
 
-int set_kernel_attributes(cfear_ctx*) { return CFEAR_OK; }  // LDS is static (up to 160 KiB per workgroup on gfx950)
-
 }  // namespace
 
 struct cfear_scan {
@@ -430,12 +428,10 @@ struct cfear_odometry {
   int large_kernel = 0, n_cus = 256;  // cfear_tune LARGE_SUBMAP_KERNEL at creation; compute units of the device
   int* d_flags = nullptr;  // bit 0: a scan had more cells than cap_cells, bit 1: a cloud had more points than cap_points (only allocated when either can happen)
   unsigned char* d_scans = nullptr;    // B * nslots flat scan blocks
-  ScanDev** d_scan_ptrs = nullptr;     // [B * nslots]
   size_t scan_stride = 0;              // bytes between consecutive scan slots of d_scans
   unsigned char* d_scratch = nullptr;  // B scratch blocks
   BlockScratch* d_scratch_hdr = nullptr;
   SeqState* d_states = nullptr;
-  double* d_poses_work = nullptr;
   double* d_cov_work = nullptr;
   cfear_reg_summary* d_summaries = nullptr;
   double* d_poses_out = nullptr;
@@ -510,14 +506,16 @@ struct cfear_odometry {
   int surf_px_cap = 0;               // pixels per side d_surf_coords is sized for
 };
 // a timing event from the pool, recorded on `st`
-static int odo_timed_event(cfear_ctx* ctx, cfear_odometry* o, std::vector<hipEvent_t>& list, hipStream_t st) {
-  if (o->pool_used == o->pool.size()) {
-    for (int i = 0; i < 1024; i++) {
-      hipEvent_t e = nullptr;
-      CFEAR_HIP_CHECK(ctx, hipEventCreate(&e));
-      o->pool.push_back(e);
-    }
+static int odo_grow_pool(cfear_ctx* ctx, cfear_odometry* o) {
+  for (int i = 0; i < 1024; i++) {
+    hipEvent_t e = nullptr;
+    CFEAR_HIP_CHECK(ctx, hipEventCreate(&e));
+    o->pool.push_back(e);
   }
+  return CFEAR_OK;
+}
+static int odo_timed_event(cfear_ctx* ctx, cfear_odometry* o, std::vector<hipEvent_t>& list, hipStream_t st) {
+  if (o->pool_used == o->pool.size()) CFEAR_TRY(odo_grow_pool(ctx, o));
   hipEvent_t e = o->pool[o->pool_used++];
   list.push_back(e);
   CFEAR_HIP_CHECK(ctx, hipEventRecord(e, st));
@@ -535,24 +533,8 @@ static int odo_join(cfear_ctx* ctx, cfear_odometry* o) {
   return CFEAR_OK;
 }
 
-// replay.hip: features -> registration of `cnt` consecutive sweeps of every sequence in one launch (a persistent workgroup per
-// sequence); odo_params points at an OdoParams (the struct is local to each translation unit, same definition)
-// register_step.hip: the batched registration step kernel for registrations of up to CFEAR_STEP_SMALL_SCANS scans
-__attribute__((visibility("hidden"))) void cfear_launch_register_step_small(const void* odo_params, int count, hipStream_t st, void* states, void* const* scan_slots,
-                                                                           const void* scratch, double* poses_work, double* cov_work,
-                                                                           cfear_reg_summary* summaries, double* poses_out);
-// register_step_large.hip: ... of more scans (submap_scan_size 8 .. 63)
-__attribute__((visibility("hidden"))) void cfear_launch_register_step_large(const void* odo_params, int count, hipStream_t st, void* states, const void* scratch,
-                                                                           double* cov_work, cfear_reg_summary* summaries, double* poses_out);
-__attribute__((visibility("hidden"))) void cfear_launch_replay_chunk(const uint32_t* d_slots, int cnt, int B, const double* d_trig, const void* odo_params,
-                                                                    void* states, const void* scratch, double* cov_work, cfear_reg_summary* summaries,
-                                                                    double* poses_out, cfear_sweep_record* records, hipStream_t stream);
-// ... from the clouds of a chunk ([cnt][B][cap][3] floats, [cnt][B] counts) instead of slots
-__attribute__((visibility("hidden"))) void cfear_launch_replay_chunk_cloud(const float* d_xyi, int cap, const int* d_counts, int cnt, int B, const void* odo_params,
-                                                                          void* states, const void* scratch, double* cov_work, cfear_reg_summary* summaries,
-                                                                          double* poses_out, cfear_sweep_record* records, hipStream_t stream);
 // has the object the shape the context's parameters ask for? (k_strongest / submap_scan_size / the filter cannot change under an object)
-static bool odo_shape_ok(const cfear_ctx* ctx, const cfear_odometry* o);
+static int odo_shape_check(cfear_ctx* ctx, const cfear_odometry* o, const char* what);
 
 // the kernel parameters of one odometry step of `o` under the context's current settings
 static OdoParams odo_params(const cfear_ctx* ctx, const cfear_odometry* o) {
@@ -576,7 +558,6 @@ static OdoParams odo_params(const cfear_ctx* ctx, const cfear_odometry* o) {
   }
   return OP;
 }
-// features -> registration of one sweep of every sequence on `st`, from the filter's slots
 // the registration step kernel of a sweep. register_step.hip holds the production instantiations (one per cost metric, registrations of
 // up to CFEAR_STEP_SMALL_SCANS scans: a bigger LDS match array); a larger submap runs the instantiation of this file (any cost, 64 scans)
 static void launch_register_kernel(const OdoParams& P_in, int count, hipStream_t st, cfear_odometry* o) {
@@ -589,7 +570,7 @@ static void launch_register_kernel(const OdoParams& P_in, int count, hipStream_t
     o->order_ready = true;  // this launch records the keys of the next one
   }
   if (P.submap + 1 <= CFEAR_STEP_SMALL_SCANS) {
-    cfear_launch_register_step_small(&P, count, st, o->d_states, reinterpret_cast<void* const*>(o->d_scan_ptrs), o->d_scratch_hdr, o->d_poses_work, o->d_cov_work, o->d_summaries, o->d_poses_out);
+    cfear_launch_register_step_small(P, count, st, o->d_states, o->d_scratch_hdr, o->d_cov_work, o->d_summaries, o->d_poses_out);
     return;
   }
   // a larger submap (8 .. 63 keyframes). Few sequences - at most one per compute unit - or a very large submap (>= 24 keyframes):
@@ -599,18 +580,11 @@ static void launch_register_kernel(const OdoParams& P_in, int count, hipStream_t
   // < 10 % at 768 sequences and the small shape is the better one at ten keyframes. cfear_tune LARGE_SUBMAP_KERNEL forces either.
   const bool large = o->large_kernel == 2 || (o->large_kernel == 0 && (count <= o->n_cus || P.submap >= 24));
   if (large) {
-    cfear_launch_register_step_large(&P, count, st, o->d_states, o->d_scratch_hdr, o->d_cov_work, o->d_summaries, o->d_poses_out);
+    cfear_launch_register_step_large(P, count, st, o->d_states, o->d_scratch_hdr, o->d_cov_work, o->d_summaries, o->d_poses_out);
     return;
   }
-#define CFEAR_LAUNCH_REG(T, C) hipLaunchKernelGGL((register_step64_kernel<T, C>), dim3(count), dim3(BLOCK_R), 0, st, P, o->d_states, o->d_scratch_hdr, \
-                                                  o->d_cov_work, o->d_summaries, o->d_poses_out)
-  // one instantiation per cost metric here too (the evaluation inline, no run-time dispatch): a ten- or fifty-keyframe submap
-  // evaluates thousands of residual blocks 30-80 times per registration
-  if (P.phase_times) CFEAR_LAUNCH_REG(true, -1);
-  else if (P.rp.cost == CFEAR_COST_P2L) CFEAR_LAUNCH_REG(false, CFEAR_COST_P2L);
-  else if (P.rp.cost == CFEAR_COST_P2D) CFEAR_LAUNCH_REG(false, CFEAR_COST_P2D);
-  else CFEAR_LAUNCH_REG(false, CFEAR_COST_P2P);
-#undef CFEAR_LAUNCH_REG
+  // one instantiation per cost metric here too: a ten- or fifty-keyframe submap evaluates thousands of residual blocks 30-80 times per registration
+  CFEAR_LAUNCH_REG_BY_COST(register_step64_kernel, P, count, st, o->d_states, o->d_scratch_hdr, o->d_cov_work, o->d_summaries, o->d_poses_out);
 }
 // ... and behind it, on the same stream, the cost-sampling stage (estimate_cov_by_sampling) and / or the copy of every sequence's cov_current
 // (the replay's per-sweep covariances): before the next sweep's features kernel may reuse a slot the registration read
@@ -622,26 +596,35 @@ static void launch_register_step(const OdoParams& P, int count, hipStream_t st, 
   else
     hipLaunchKernelGGL(cov_sample_kernel<false>, dim3(count), dim3(BLOCK_R), 0, st, P, o->d_scratch_hdr, o->d_cov_work);
 }
-static void odo_launch_sweep(const cfear_ctx* ctx, cfear_odometry* o, const OdoParams& P, const uint32_t* d_slots, int seq_count, hipStream_t st) {
+// the features stage of a sweep: `count` sequences from P.seq0 on, from the filter's slots ...
+static void launch_features_step(const cfear_ctx* ctx, const cfear_odometry* o, const OdoParams& P, const uint32_t* d_slots, int count, hipStream_t st) {
   if (P.phase_times)
-    hipLaunchKernelGGL(features_step_kernel<true>, dim3(seq_count), dim3(BLOCK_F), 0, st, d_slots, ctx->d_trig, P, o->d_states,
-                       o->d_scan_ptrs, o->d_scratch_hdr);
+    hipLaunchKernelGGL(features_step_kernel<true>, dim3(count), dim3(BLOCK_F), 0, st, d_slots, ctx->d_trig, P, o->d_states, nullptr, o->d_scratch_hdr);
   else
-    hipLaunchKernelGGL(features_step_kernel<false>, dim3(seq_count), dim3(BLOCK_F), 0, st, d_slots, ctx->d_trig, P, o->d_states,
-                       o->d_scan_ptrs, o->d_scratch_hdr);
+    hipLaunchKernelGGL(features_step_kernel<false>, dim3(count), dim3(BLOCK_F), 0, st, d_slots, ctx->d_trig, P, o->d_states, nullptr, o->d_scratch_hdr);
+}
+// ... or from clouds on the device
+static void launch_features_cloud_step(const cfear_odometry* o, const OdoParams& P, const float* d_xyi, int cap, const int* d_counts, int count, hipStream_t st) {
+  hipLaunchKernelGGL(features_cloud_step_kernel, dim3(count), dim3(BLOCK_F), 0, st, d_xyi, cap, d_counts, P, o->d_states, o->d_scratch_hdr);
+}
+// features -> registration of one sweep of every sequence on `st` (the replay's non-persistent route)
+static void odo_launch_sweep(const cfear_ctx* ctx, cfear_odometry* o, const OdoParams& P, const uint32_t* d_slots, int seq_count, hipStream_t st) {
+  launch_features_step(ctx, o, P, d_slots, seq_count, st);
   launch_register_step(P, seq_count, st, o);
 }
-
 static void odo_launch_sweep_cloud(cfear_odometry* o, const OdoParams& P, const float* d_xyi, int cap, const int* d_counts, int seq_count, hipStream_t st) {
-  hipLaunchKernelGGL(features_cloud_step_kernel, dim3(seq_count), dim3(BLOCK_F), 0, st, d_xyi, cap, d_counts, P, o->d_states, o->d_scratch_hdr);
+  launch_features_cloud_step(o, P, d_xyi, cap, d_counts, seq_count, st);
   launch_register_step(P, seq_count, st, o);
 }
 static int odo_cfar_points(const cfear_ctx* ctx) { return ctx->par.cfar_max_points > 0 ? ctx->par.cfar_max_points : 32768; }
-static bool odo_shape_ok(const cfear_ctx* ctx, const cfear_odometry* o) {
-  if (o->nslots != ctx->par.submap_scan_size + 1 || o->filter != ctx->par.filter_type) return false;
-  if ((ctx->tune_nn_tie == 2 && !o->with_kd) || (ctx->tune_nn_tie != 0 && o->pair_cap < 8192)) return false;  // the tie rule was switched after the object was created
-  if (ctx->tune_voxel_order != 0) return false;  // per-call scans only (cfear_odometry_create refuses it too)
-  return o->cap_points == (o->filter == CFEAR_FILTER_CACFAR ? odo_cfar_points(ctx) : ctx->A * ctx->par.k_strongest);
+static int odo_shape_check(cfear_ctx* ctx, const cfear_odometry* o, const char* what) {
+  bool ok = o->nslots == ctx->par.submap_scan_size + 1 && o->filter == ctx->par.filter_type;
+  if ((ctx->tune_nn_tie == 2 && !o->with_kd) || (ctx->tune_nn_tie != 0 && o->pair_cap < 8192)) ok = false;  // the tie rule was switched after the object was created
+  if (ctx->tune_voxel_order != 0) ok = false;  // per-call scans only (cfear_odometry_create refuses it too)
+  if (ok && o->cap_points == (o->filter == CFEAR_FILTER_CACFAR ? odo_cfar_points(ctx) : ctx->A * ctx->par.k_strongest)) return CFEAR_OK;
+  char msg[320];
+  snprintf(msg, sizeof(msg), "%s: submap_scan_size / k_strongest / filter_type changed after odometry_create, or a parity mode (cfear_tune NN_TIE_RULE / VOXEL_ORDER) was switched under the object", what);
+  return cfear_fail(ctx, CFEAR_ERR_INVALID, msg);
 }
 // the CA-CFAR stage of n_scans sweeps (radar_driver.cpp:52-56) into clouds of o->cap_points points each
 static int odo_launch_cfar(cfear_ctx* ctx, cfear_odometry* o, const uint8_t* d_polar, int n_scans, float* d_xyi, int* d_counts, int* d_rows, hipStream_t st) {
@@ -649,11 +632,20 @@ static int odo_launch_cfar(cfear_ctx* ctx, cfear_odometry* o, const uint8_t* d_p
                                  ctx->par.cfar_max_distance, d_xyi, o->cap_points, d_counts, d_rows, st);
 }
 
-// per-context scratch of the per-call API, sized for up to MAX_SCANS-1 keyframes
-static int ensure_ctx_scratch(cfear_ctx* ctx, int cap_points, int pair_cap) {
+// What a per-call problem (Register / GetCost / GetSurface) keeps on the device behind the working arrays of the context scratch
+struct CallTail {
+  double poses[3 * MAX_SCANS];
+  double cov[36];  // cfear_register: the covariance, in and out; cfear_get_cost: the score, then the residual count; cfear_get_surface: the prior
+  ScanDev* ptrs[MAX_SCANS];
+  alignas(16) cfear_reg_summary sum;  // (up to here cfear_register copies in one piece, each way)
+  alignas(16) double prior[36];       // cfear_register_soft
+};
+static_assert(offsetof(CallTail, sum) == sizeof(double) * (3 * MAX_SCANS + 36) + sizeof(void*) * MAX_SCANS, "the arrays that travel as one copy lie back to back");
+// per-context scratch of the per-call API for scans of up to cap_points points and up to MAX_SCANS - 1 keyframes: the working arrays (B), then a CallTail
+static int ensure_ctx_scratch(cfear_ctx* ctx, int cap_points, BlockScratch* B, CallTail** tail = nullptr) {
+  const int pair_cap = (MAX_SCANS - 1) * cap_points;
   const ScratchLayout L = scratch_layout(cap_points, pair_cap);
-  const size_t extra = 4096;  // summary + poses + cov + scan pointer table + closest buffers live after the layout
-  const size_t need = L.total + extra + sizeof(double) * (3 * MAX_SCANS + 36) + sizeof(void*) * MAX_SCANS + sizeof(cfear_reg_summary);
+  const size_t need = L.total + sizeof(CallTail) + 4096;  // (and some headroom)
   if (need > ctx->scratch_bytes) {
     if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
     ctx->d_scratch = nullptr; ctx->scratch_bytes = 0;
@@ -661,7 +653,31 @@ static int ensure_ctx_scratch(cfear_ctx* ctx, int cap_points, int pair_cap) {
     if (hipMemset(ctx->d_scratch, 0, need) != hipSuccess) return cfear_fail(ctx, CFEAR_ERR_HIP, "hipMemset context scratch");  // dense voxel table starts all-zero
     ctx->scratch_bytes = need;
   }
+  unsigned char* base = static_cast<unsigned char*>(ctx->d_scratch);
+  *B = scratch_header(base, cap_points, pair_cap);
+  if (tail) *tail = reinterpret_cast<CallTail*>(base + L.total);
   return CFEAR_OK;
+}
+// the scans of a per-call problem: all there and built under the current tie rule; their device blocks and the largest point capacity among them
+static int problem_scans(cfear_ctx* ctx, cfear_scan* const* scans, int n, const char* what, ScanDev** ptrs, int* capmax) {
+  *capmax = ctx->A * ctx->par.k_strongest;
+  for (int i = 0; i < n; i++) {
+    if (!scans[i]) {
+      char msg[64];
+      snprintf(msg, sizeof(msg), "%s: null scan", what);
+      return cfear_fail(ctx, CFEAR_ERR_INVALID, msg);
+    }
+    if (scans[i]->cap_points > *capmax) *capmax = scans[i]->cap_points;
+    ptrs[i] = reinterpret_cast<ScanDev*>(scans[i]->d_block);
+  }
+  return check_tie_rule_scans(ctx, scans, n, what);
+}
+// ... with the context scratch sized for them: the kernels' working memory, the device tail (d) and the scan pointer table to upload into it
+struct CallProblem { BlockScratch B; CallTail* d; ScanDev* ptrs[MAX_SCANS]; };
+static int call_problem(cfear_ctx* ctx, cfear_scan* const* scans, int n, const char* what, CallProblem* pb) {
+  int capmax = 0;
+  CFEAR_TRY(problem_scans(ctx, scans, n, what, pb->ptrs, &capmax));
+  return ensure_ctx_scratch(ctx, capmax, &pb->B, &pb->d);
 }
 
 extern "C" {
@@ -870,12 +886,10 @@ int cfear_scan_create(cfear_ctx* ctx, const cfear_cloud* cloud, cfear_scan** sca
   if (!ctx || !cloud || !scan) return cfear_fail(ctx, CFEAR_ERR_INVALID, "scan_create: bad argument");
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   *scan = nullptr;
-  int rc = set_kernel_attributes(ctx);
-  if (rc != CFEAR_OK) return rc;
   const int cap = cloud->cap;
   if (cap >= (1 << 24)) return cfear_fail(ctx, CFEAR_ERR_UNSUPPORTED, "scan_create: more than 2^24 points");
-  rc = ensure_ctx_scratch(ctx, cap > ctx->A * ctx->par.k_strongest ? cap : ctx->A * ctx->par.k_strongest,
-                          (MAX_SCANS - 1) * (cap > ctx->A * ctx->par.k_strongest ? cap : ctx->A * ctx->par.k_strongest));
+  BlockScratch B;
+  int rc = ensure_ctx_scratch(ctx, std::max(cap, ctx->A * ctx->par.k_strongest), &B);
   if (rc != CFEAR_OK) return rc;
   cfear_scan* s = new (std::nothrow) cfear_scan();
   if (!s) return cfear_fail(ctx, CFEAR_ERR_NOMEM, "scan alloc");
@@ -893,8 +907,6 @@ int cfear_scan_create(cfear_ctx* ctx, const cfear_cloud* cloud, cfear_scan** sca
   memcpy(ctx->h_stage, &h, sizeof(h));
   hipError_t e = hipMemcpyAsync(s->d_block, ctx->h_stage, sizeof(h), hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess) {
-    const int capmax = cap > ctx->A * ctx->par.k_strongest ? cap : ctx->A * ctx->par.k_strongest;
-    BlockScratch B = scratch_header(static_cast<unsigned char*>(ctx->d_scratch), capmax, (MAX_SCANS - 1) * capmax);
     if (ctx->tune_voxel_order == 1) {  // PCL <= 1.9's intra-voxel order (parity mode): ranks from a host std::sort
       const int nv = voxel_order_stdsort(ctx, cloud, cap, &d_vorder);
       if (nv < 0) { cfear_pool_free(ctx, s->d_block, s->bytes); delete s; return nv; }
@@ -931,8 +943,8 @@ int cfear_scan_from_cells(cfear_ctx* ctx, const cfear_cell* cells, int n, cfear_
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   *scan = nullptr;
   if (n == 0) return cfear_fail(ctx, CFEAR_ERR_EMPTY, "scan_from_cells: no cells (reference: 'error, cloud empty' + exit)");
-  const int base = ctx->A * ctx->par.k_strongest, capmax = n > base ? n : base;
-  int rc = ensure_ctx_scratch(ctx, capmax, (MAX_SCANS - 1) * capmax);
+  BlockScratch B;
+  int rc = ensure_ctx_scratch(ctx, std::max(n, ctx->A * ctx->par.k_strongest), &B);
   if (rc != CFEAR_OK) return rc;
   cfear_scan* s = new (std::nothrow) cfear_scan();
   if (!s) return cfear_fail(ctx, CFEAR_ERR_NOMEM, "scan alloc");
@@ -943,7 +955,6 @@ int cfear_scan_from_cells(cfear_ctx* ctx, const cfear_cell* cells, int n, cfear_
   hipError_t e = hipMemcpyAsync(s->d_block, &h, sizeof(h), hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(s->d_block + L.cells, cells, sizeof(cfear_cell) * (size_t)n, hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess) {
-    const BlockScratch B = scratch_header(static_cast<unsigned char*>(ctx->d_scratch), capmax, (MAX_SCANS - 1) * capmax);
     hipLaunchKernelGGL(scan_from_cells_kernel, dim3(1), dim3(BLOCK_F), 0, ctx->stream, reinterpret_cast<ScanDev*>(s->d_block), n, feature_params(ctx), B);
     e = hipGetLastError();
   }
@@ -1015,56 +1026,34 @@ static int register_impl(cfear_ctx* ctx, cfear_scan* const* scans, int n, double
   if (!ctx || !scans || !poses_xyt || n < 2) return cfear_fail(ctx, CFEAR_ERR_INVALID, "register: need >= 2 scans and poses");
   if (n > MAX_SCANS) return cfear_fail(ctx, CFEAR_ERR_UNSUPPORTED, "register: more than 64 scans");
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  int rc = set_kernel_attributes(ctx);
-  if (rc != CFEAR_OK) return rc;
-  int capmax = ctx->A * ctx->par.k_strongest;
-  for (int i = 0; i < n; i++) {
-    if (!scans[i]) return cfear_fail(ctx, CFEAR_ERR_INVALID, "register: null scan");
-    if (scans[i]->cap_points > capmax) capmax = scans[i]->cap_points;
-  }
-  if ((rc = check_tie_rule_scans(ctx, scans, n, "register")) != CFEAR_OK) return rc;
-  rc = ensure_ctx_scratch(ctx, capmax, (MAX_SCANS - 1) * capmax);
-  if (rc != CFEAR_OK) return rc;
-  const ScratchLayout L = scratch_layout(capmax, (MAX_SCANS - 1) * capmax);
-  unsigned char* base = static_cast<unsigned char*>(ctx->d_scratch);
-  const BlockScratch B = scratch_header(base, capmax, (MAX_SCANS - 1) * capmax);
-  unsigned char* tail = base + L.total;
-  double* d_poses = reinterpret_cast<double*>(tail);
-  double* d_cov = d_poses + 3 * MAX_SCANS;
-  ScanDev** d_ptrs = reinterpret_cast<ScanDev**>(d_cov + 36);
-  cfear_reg_summary* d_sum = reinterpret_cast<cfear_reg_summary*>(reinterpret_cast<unsigned char*>(d_ptrs) + sizeof(void*) * MAX_SCANS);
-  // arguments and results travel through pinned staging: one copy each way and one synchronisation per registration (round 6; it was
-  // three small pageable copies in, three out). Device layout of the tail: poses | cov | scan pointers | summary | prior.
-  const size_t in_bytes = sizeof(double) * (3 * MAX_SCANS + 36) + sizeof(void*) * MAX_SCANS;
-  const size_t sum_bytes = ((sizeof(cfear_reg_summary) + 15) / 16) * 16;
-  rc = cfear_ensure_hstage(ctx, in_bytes + sum_bytes + sizeof(double) * 36);
-  if (rc != CFEAR_OK) return rc;
-  double* h_poses = reinterpret_cast<double*>(ctx->h_stage);
-  double* h_cov = h_poses + 3 * MAX_SCANS;
-  ScanDev** h_ptrs = reinterpret_cast<ScanDev**>(h_cov + 36);
-  memset(ctx->h_stage, 0, in_bytes);
-  for (int i = 0; i < n; i++) h_ptrs[i] = reinterpret_cast<ScanDev*>(scans[i]->d_block);
-  memcpy(h_poses, poses_xyt, sizeof(double) * 3 * n);
+  CallProblem pb;
+  CFEAR_TRY(call_problem(ctx, scans, n, "register", &pb));
+  // arguments and results travel through pinned staging laid out like the device tail: one copy each way and one synchronisation per
+  // registration (round 6; it was three small pageable copies in, three out)
+  CFEAR_TRY(cfear_ensure_hstage(ctx, sizeof(CallTail)));
+  CallTail* h = reinterpret_cast<CallTail*>(ctx->h_stage);
+  const size_t in_bytes = offsetof(CallTail, sum);
+  memset(h, 0, in_bytes);
+  memcpy(h->ptrs, pb.ptrs, sizeof(void*) * n);
+  memcpy(h->poses, poses_xyt, sizeof(double) * 3 * n);
   // a registration that fails does not touch the caller's covariance (reg_cov of n_scan_normal_reg::Register, n_scan_normal.cpp:82-187):
   // the device copy starts as the caller's matrix, so that what comes back is the caller's matrix (not the previous call's result)
-  if (cov6_last) memcpy(h_cov, cov6_last, sizeof(double) * 36);
-  CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(d_poses, ctx->h_stage, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-  const RegParams P = reg_params(ctx);
+  if (cov6_last) memcpy(h->cov, cov6_last, sizeof(double) * 36);
+  CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(pb.d, h, in_bytes, hipMemcpyHostToDevice, ctx->stream));
   double* d_prior = nullptr;
-  if (prior_cov6) {  // staged behind the summary, in the tail of the context scratch
-    d_prior = reinterpret_cast<double*>(reinterpret_cast<unsigned char*>(d_sum) + sum_bytes);
-    double* h_prior = reinterpret_cast<double*>(ctx->h_stage + in_bytes + sum_bytes);
-    memcpy(h_prior, prior_cov6, sizeof(double) * 36);
-    CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(d_prior, h_prior, sizeof(double) * 36, hipMemcpyHostToDevice, ctx->stream));
+  if (prior_cov6) {
+    d_prior = pb.d->prior;
+    memcpy(h->prior, prior_cov6, sizeof(double) * 36);
+    CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(d_prior, h->prior, sizeof(double) * 36, hipMemcpyHostToDevice, ctx->stream));
   }
-  hipLaunchKernelGGL(register_kernel, dim3(1), dim3(BLOCK_R), 0, ctx->stream, d_ptrs, n, d_poses, d_cov, P, B, d_sum, d_prior);
+  hipLaunchKernelGGL(register_kernel, dim3(1), dim3(BLOCK_R), 0, ctx->stream, pb.d->ptrs, n, pb.d->poses, pb.d->cov, reg_params(ctx), pb.B, &pb.d->sum, d_prior);
   CFEAR_HIP_CHECK(ctx, hipGetLastError());
-  CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(ctx->h_stage, d_poses, in_bytes + sizeof(cfear_reg_summary), hipMemcpyDeviceToHost, ctx->stream));
+  CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(h, pb.d, in_bytes + sizeof(cfear_reg_summary), hipMemcpyDeviceToHost, ctx->stream));
   CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  memcpy(poses_xyt, h_poses, sizeof(double) * 3 * n);
-  if (cov6_last) memcpy(cov6_last, h_cov, sizeof(double) * 36);
-  if (summary) memcpy(summary, ctx->h_stage + in_bytes, sizeof(cfear_reg_summary));
-  if (reinterpret_cast<const cfear_reg_summary*>(ctx->h_stage + in_bytes)->assoc_path < 0)  // (registration_dev.h: the kd descent's stack did not fit the match scratch)
+  memcpy(poses_xyt, h->poses, sizeof(double) * 3 * n);
+  if (cov6_last) memcpy(cov6_last, h->cov, sizeof(double) * 36);
+  if (summary) memcpy(summary, &h->sum, sizeof(cfear_reg_summary));
+  if (h->sum.assoc_path < 0)  // (registration_dev.h: the kd descent's stack did not fit the match scratch)
     return cfear_fail(ctx, CFEAR_ERR_UNSUPPORTED, "register: NN_TIE_RULE could not be honoured for this problem size (match scratch too small for the kd-tree descent); the result used the production rule");
   return CFEAR_OK;
 }
@@ -1086,31 +1075,18 @@ int cfear_get_cost(cfear_ctx* ctx, cfear_scan* const* scans, int n, const double
     return cfear_fail(ctx, CFEAR_ERR_INVALID, "get_cost: need >= 2 scans, poses and output pointers");
   if (n > MAX_SCANS) return cfear_fail(ctx, CFEAR_ERR_UNSUPPORTED, "get_cost: more than 64 scans");
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  int capmax = ctx->A * ctx->par.k_strongest;
-  for (int i = 0; i < n; i++) {
-    if (!scans[i]) return cfear_fail(ctx, CFEAR_ERR_INVALID, "get_cost: null scan");
-    if (scans[i]->cap_points > capmax) capmax = scans[i]->cap_points;
-  }
-  int rc = check_tie_rule_scans(ctx, scans, n, "get_cost");
-  if (rc != CFEAR_OK) return rc;
-  rc = ensure_ctx_scratch(ctx, capmax, (MAX_SCANS - 1) * capmax);
-  if (rc != CFEAR_OK) return rc;
-  const ScratchLayout L = scratch_layout(capmax, (MAX_SCANS - 1) * capmax);
-  unsigned char* base = static_cast<unsigned char*>(ctx->d_scratch);
-  const BlockScratch B = scratch_header(base, capmax, (MAX_SCANS - 1) * capmax);
-  unsigned char* tail = base + L.total;
-  double* d_poses = reinterpret_cast<double*>(tail);
-  double* d_score = d_poses + 3 * MAX_SCANS;  // the covariance slot of cfear_register
+  CallProblem pb;
+  CFEAR_TRY(call_problem(ctx, scans, n, "get_cost", &pb));
+  double* d_poses = pb.d->poses;
+  double* d_score = pb.d->cov;
   int* d_nres = reinterpret_cast<int*>(d_score + 1);
-  ScanDev** d_ptrs = reinterpret_cast<ScanDev**>(d_score + 36);
+  ScanDev** d_ptrs = pb.d->ptrs;
   double* d_res = nullptr;
   if (capacity > 0 && hipMalloc(&d_res, sizeof(double) * (size_t)capacity) != hipSuccess) return cfear_fail(ctx, CFEAR_ERR_NOMEM, "hipMalloc residuals");
-  ScanDev* h_ptrs[MAX_SCANS];
-  for (int i = 0; i < n; i++) h_ptrs[i] = reinterpret_cast<ScanDev*>(scans[i]->d_block);
-  hipError_t e = hipMemcpyAsync(d_ptrs, h_ptrs, sizeof(void*) * n, hipMemcpyHostToDevice, ctx->stream);
+  hipError_t e = hipMemcpyAsync(d_ptrs, pb.ptrs, sizeof(void*) * n, hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(d_poses, poses_xyt, sizeof(double) * 3 * n, hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(get_cost_kernel, dim3(1), dim3(BLOCK_R), 0, ctx->stream, d_ptrs, n, d_poses, reg_params(ctx), B, itr, d_score, d_res,
+    hipLaunchKernelGGL(get_cost_kernel, dim3(1), dim3(BLOCK_R), 0, ctx->stream, d_ptrs, n, d_poses, reg_params(ctx), pb.B, itr, d_score, d_res,
                        capacity, d_nres);
     e = hipGetLastError();
   }
@@ -1159,22 +1135,11 @@ int cfear_get_surface(cfear_ctx* ctx, cfear_scan* const* scans, int n, const dou
     if (rc != CFEAR_OK) return cfear_fail(ctx, rc, "get_surface: more than CFEAR_SURFACE_MAX_SIDE pixels per side");
   }
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  int capmax = ctx->A * ctx->par.k_strongest;
-  for (int i = 0; i < n; i++) {
-    if (!scans[i]) return cfear_fail(ctx, CFEAR_ERR_INVALID, "get_surface: null scan");
-    if (scans[i]->cap_points > capmax) capmax = scans[i]->cap_points;
-  }
-  int rc = check_tie_rule_scans(ctx, scans, n, "get_surface");
-  if (rc != CFEAR_OK) return rc;
-  rc = ensure_ctx_scratch(ctx, capmax, (MAX_SCANS - 1) * capmax);
-  if (rc != CFEAR_OK) return rc;
-  const ScratchLayout L = scratch_layout(capmax, (MAX_SCANS - 1) * capmax);
-  unsigned char* base = static_cast<unsigned char*>(ctx->d_scratch);
-  const BlockScratch B = scratch_header(base, capmax, (MAX_SCANS - 1) * capmax);
-  unsigned char* tail = base + L.total;
-  double* d_poses = reinterpret_cast<double*>(tail);
-  double* d_prior = d_poses + 3 * MAX_SCANS;  // the covariance slot of cfear_register
-  ScanDev** d_ptrs = reinterpret_cast<ScanDev**>(d_prior + 36);
+  CallProblem pb;
+  CFEAR_TRY(call_problem(ctx, scans, n, "get_surface", &pb));
+  double* d_poses = pb.d->poses;
+  double* d_prior = pb.d->cov;
+  ScanDev** d_ptrs = pb.d->ptrs;
   // header, coordinates, their counts and the surface: one allocation per call
   const size_t np = (size_t)pixels * pixels;
   const size_t hdr_b = (sizeof(SurfHdr) + 255) / 256 * 256, crd_b = (sizeof(double) * 2 * pixels + 255) / 256 * 256;
@@ -1187,16 +1152,14 @@ int cfear_get_surface(cfear_ctx* ctx, cfear_scan* const* scans, int n, const dou
   std::vector<double> coords(2 * (size_t)pixels, 0.0);
   const int nxy[2] = {cfear_surface_axis(poses_xyt[3 * (n - 1)], res, width, pixels, coords.data()),
                       cfear_surface_axis(poses_xyt[3 * (n - 1) + 1], res, width, pixels, coords.data() + pixels)};
-  ScanDev* h_ptrs[MAX_SCANS];
-  for (int i = 0; i < n; i++) h_ptrs[i] = reinterpret_cast<ScanDev*>(scans[i]->d_block);
-  hipError_t e = hipMemcpyAsync(d_ptrs, h_ptrs, sizeof(void*) * n, hipMemcpyHostToDevice, ctx->stream);
+  hipError_t e = hipMemcpyAsync(d_ptrs, pb.ptrs, sizeof(void*) * n, hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(d_poses, poses_xyt, sizeof(double) * 3 * n, hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess && prior_cov6) e = hipMemcpyAsync(d_prior, prior_cov6, sizeof(double) * 36, hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(d_coords, coords.data(), sizeof(double) * 2 * pixels, hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(d_nxy, nxy, sizeof(nxy), hipMemcpyHostToDevice, ctx->stream);
   const RegParams P = reg_params(ctx);
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(surface_build_kernel<CFEAR_SURFACE_NAIVE != 0>, dim3(1), dim3(BLOCK_R), 0, ctx->stream, d_ptrs, n, d_poses, P, B, itr,
+    hipLaunchKernelGGL(surface_build_kernel<CFEAR_SURFACE_NAIVE != 0>, dim3(1), dim3(BLOCK_R), 0, ctx->stream, d_ptrs, n, d_poses, P, pb.B, itr,
                        prior_cov6 ? d_prior : nullptr, d_hdr, d_coords, d_nxy, pixels, d_out);
     e = hipGetLastError();
   }
@@ -1305,7 +1268,7 @@ static void cov_sample_design(double xy_range, double yaw_range, int steps, std:
   const size_t m = (size_t)steps * steps * steps;
   offs.assign(3 * m, 0.0); A.assign(10 * m, 0.0);
   int k = 0;
-  for (int it = 0; it < steps; it++)  // the reference's loop order (:294-296), as cfear_cov_by_sampling
+  for (int it = 0; it < steps; it++)  // the reference's loop order (:294-296)
     for (int ix = 0; ix < steps; ix++)
       for (int iy = 0; iy < steps; iy++, k++) {
         const double x = xs[ix], y = xs[iy], z = ths[it];
@@ -1324,29 +1287,20 @@ int cfear_cov_by_sampling(cfear_ctx* ctx, cfear_scan* const* scans, int n, const
   if (n > MAX_SCANS) return cfear_fail(ctx, CFEAR_ERR_UNSUPPORTED, "cov_by_sampling: more than 64 scans");
   *success = 0;
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  for (int i = 0; i < n; i++) if (!scans[i]) return cfear_fail(ctx, CFEAR_ERR_INVALID, "cov_by_sampling: null scan");
-  { const int trc = check_tie_rule_scans(ctx, scans, n, "cov_by_sampling"); if (trc != CFEAR_OK) return trc; }
+  ScanDev* h_ptrs[MAX_SCANS];
+  int capmax = 0;  // (not needed: the samples' match arrays are an allocation of this call)
+  CFEAR_TRY(problem_scans(ctx, scans, n, "cov_by_sampling", h_ptrs, &capmax));
   int nsrc = 0;
-  int rc = cfear_scan_size(ctx, scans[n - 1], &nsrc);
-  if (rc != CFEAR_OK) return rc;
+  CFEAR_TRY(cfear_scan_size(ctx, scans[n - 1], &nsrc));
   const int steps = samples_per_axis, m = steps * steps * steps, L = 3 * (n - 1);
   // match scratch per sample: a pair of capacity per (keyframe, source cell); under a non-production tie rule the kd descent's per-thread stacks
   // live there too (registration_dev.h associate_pair_rule: 64 B per pair of capacity for blockDim x 64 entries of 16 B)
   const int cap = std::max((n - 1) * (nsrc > 0 ? nsrc : 1), ctx->tune_nn_tie != 0 ? 4096 : 1);
-  std::vector<double> xs, ths;  // :277-290
-  linspace(-xy_range * 0.5, xy_range * 0.5, steps, xs);
-  linspace(-yaw_range * 0.5, yaw_range * 0.5, steps, ths);
-  std::vector<double> samples(3 * (size_t)m), A(10 * (size_t)m), costs((size_t)m);
+  std::vector<double> samples, A, costs((size_t)m);  // samples: the design's offsets (in the reference's loop order), then offset + registered pose
   std::vector<int> nres((size_t)m);
-  int k = 0;
-  for (int it = 0; it < steps; it++)      // the reference's loop order (:294-296)
-    for (int ix = 0; ix < steps; ix++)
-      for (int iy = 0; iy < steps; iy++, k++) {
-        samples[3 * k] = xs[ix] + poses_xyt[L]; samples[3 * k + 1] = xs[iy] + poses_xyt[L + 1]; samples[3 * k + 2] = ths[it] + poses_xyt[L + 2];
-        const double x = xs[ix], y = xs[iy], z = ths[it];
-        double* r = &A[10 * (size_t)k];
-        r[0] = x * x; r[1] = y * y; r[2] = z * z; r[3] = x * y; r[4] = y * z; r[5] = z * x; r[6] = x; r[7] = y; r[8] = z; r[9] = 1.0;  // :325-336
-      }
+  cov_sample_design(xy_range, yaw_range, steps, samples, A);
+  for (int k = 0; k < m; k++)
+    for (int j = 0; j < 3; j++) samples[3 * k + j] = samples[3 * k + j] + poses_xyt[L + j];
   // device buffers: poses, samples, scan pointers, costs, residual counts, per-sample match arrays
   const size_t bytes = sizeof(double) * (3 * (size_t)n + 3 * (size_t)m + (size_t)m) + sizeof(void*) * (size_t)n + sizeof(int) * (size_t)m +
                        (sizeof(double) * 8 + 3 * sizeof(int)) * (size_t)m * cap + 256;  // (three ints of association scratch per pair: the grouped path, as scratch_layout)
@@ -1359,8 +1313,6 @@ int cfear_cov_by_sampling(cfear_ctx* ctx, cfear_scan* const* scans, int n, const
   ScanDev** d_ptrs = reinterpret_cast<ScanDev**>(d_costs + m);
   int* d_nres = reinterpret_cast<int*>(d_ptrs + n);
   int* d_assoc = d_nres + m;
-  ScanDev* h_ptrs[MAX_SCANS];
-  for (int i = 0; i < n; i++) h_ptrs[i] = reinterpret_cast<ScanDev*>(scans[i]->d_block);
   hipError_t e = hipMemcpyAsync(d_ptrs, h_ptrs, sizeof(void*) * n, hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(d_poses, poses_xyt, sizeof(double) * 3 * n, hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(d_samples, samples.data(), sizeof(double) * 3 * m, hipMemcpyHostToDevice, ctx->stream);
@@ -1388,24 +1340,18 @@ void cfear_odometry_destroy(cfear_ctx* ctx, cfear_odometry* o) {
   if (!o) return;
   if (ctx) {
     (void)hipSetDevice(ctx->device);
-    std::vector<hipStream_t> all = o->so;
+    std::vector<hipStream_t> all = o->so;  // the object's streams: drained, then no longer the context's to wait for
     all.push_back(o->sf);
+    all.push_back(o->rp_stream);
     for (hipStream_t st : all) {
       if (!st) continue;
       (void)hipStreamSynchronize(st);
-      for (size_t i = 0; i < ctx->aux_streams.size(); i++)
-        if (ctx->aux_streams[i] == st) { ctx->aux_streams.erase(ctx->aux_streams.begin() + i); break; }
+      const auto it = std::find(ctx->aux_streams.begin(), ctx->aux_streams.end(), st);
+      if (it != ctx->aux_streams.end()) ctx->aux_streams.erase(it);
     }
     (void)hipStreamSynchronize(ctx->stream);
   }
-  if (ctx && o->rp_stream) {
-    (void)hipStreamSynchronize(o->rp_stream);
-    for (size_t i = 0; i < ctx->aux_streams.size(); i++)
-      if (ctx->aux_streams[i] == o->rp_stream) { ctx->aux_streams.erase(ctx->aux_streams.begin() + i); break; }
-    (void)hipStreamSynchronize(ctx->stream);
-  }
-  void* ptrs[] = {o->d_scans, o->d_scan_ptrs, o->d_scratch, o->d_scratch_hdr, o->d_states, o->d_poses_work, o->d_cov_work,
-                  o->d_summaries, o->d_poses_out, o->d_slots[0], o->d_slots[1], o->d_polar, o->d_phase_times,
+  void* ptrs[] = {o->d_scans, o->d_scratch, o->d_scratch_hdr, o->d_states, o->d_cov_work, o->d_summaries, o->d_poses_out, o->d_slots[0], o->d_slots[1], o->d_polar, o->d_phase_times,
                   o->rp_polar[0], o->rp_polar[1], o->rp_slots[0], o->rp_slots[1], o->d_records, o->d_flags, o->d_order, o->d_work,
                   o->d_cloud, o->d_cloud_n, o->d_cfar_rows, o->rp_cloud[0], o->rp_cloud[1], o->rp_cloud_n[0], o->rp_cloud_n[1], o->rp_cfar_rows,
                   o->d_cov_ctx, o->d_cov_design, o->d_cov_costs, o->d_cov_seq, o->d_surf_hdr, o->d_surf_coords, o->d_surf_nxy};
@@ -1423,7 +1369,7 @@ void cfear_odometry_destroy(cfear_ctx* ctx, cfear_odometry* o) {
 int cfear_odometry_reset(cfear_ctx* ctx, cfear_odometry* o) {
   if (!ctx || !o) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_reset: bad argument");
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  { const int jrc = odo_join(ctx, o); if (jrc != CFEAR_OK) return jrc; }
+  CFEAR_TRY(odo_join(ctx, o));
   std::vector<SeqState> st((size_t)o->B);
   for (auto& s : st) {
     memset(&s, 0, sizeof(s));
@@ -1444,8 +1390,6 @@ int cfear_odometry_create(cfear_ctx* ctx, int n_sequences, cfear_odometry** out)
   if (!ctx || !out || n_sequences <= 0) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_create: bad argument");
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   *out = nullptr;
-  int rc = set_kernel_attributes(ctx);
-  if (rc != CFEAR_OK) return rc;
   cfear_odometry* o = new (std::nothrow) cfear_odometry();
   if (!o) return cfear_fail(ctx, CFEAR_ERR_NOMEM, "odometry alloc");
   if (ctx->tune_voxel_order != 0) {
@@ -1484,12 +1428,10 @@ int cfear_odometry_create(cfear_ctx* ctx, int n_sequences, cfear_odometry** out)
   }
   bool ok = true;
   ok = ok && hipMalloc(&o->d_scans, SL.total * (size_t)B * o->nslots) == hipSuccess;
-  ok = ok && hipMalloc(&o->d_scan_ptrs, sizeof(ScanDev*) * (size_t)B * o->nslots) == hipSuccess;
   ok = ok && hipMalloc(&o->d_scratch, WL.total * (size_t)B) == hipSuccess;
   ok = ok && hipMemset(o->d_scratch, 0, WL.total * (size_t)B) == hipSuccess;  // dense voxel tables start all-zero
   ok = ok && hipMalloc(&o->d_scratch_hdr, sizeof(BlockScratch) * (size_t)B) == hipSuccess;
   ok = ok && hipMalloc(&o->d_states, sizeof(SeqState) * (size_t)B) == hipSuccess;
-  ok = ok && hipMalloc(&o->d_poses_work, sizeof(double) * 3 * MAX_SCANS * (size_t)B) == hipSuccess;
   ok = ok && hipMalloc(&o->d_cov_work, sizeof(double) * 36 * (size_t)B) == hipSuccess;
   ok = ok && hipMalloc(&o->d_summaries, sizeof(cfear_reg_summary) * (size_t)B) == hipSuccess;
   ok = ok && hipMalloc(&o->d_poses_out, sizeof(double) * 3 * (size_t)B) == hipSuccess;
@@ -1508,22 +1450,17 @@ int cfear_odometry_create(cfear_ctx* ctx, int n_sequences, cfear_odometry** out)
          hipMemset(o->d_work, 0, sizeof(unsigned) * (size_t)B) == hipSuccess;
   if (!ok) { cfear_odometry_destroy(ctx, o); return cfear_fail(ctx, CFEAR_ERR_NOMEM, "hipMalloc odometry state"); }
   o->scan_stride = SL.total;
-  std::vector<ScanDev*> ptrs((size_t)B * o->nslots);
   std::vector<BlockScratch> hdrs((size_t)B);
   std::vector<ScanDev> scan_hdrs((size_t)B * o->nslots);  // all headers built on the host, uploaded with one strided copy
   for (int q = 0; q < B; q++) {
-    for (int j = 0; j < o->nslots; j++) {
-      unsigned char* blk = o->d_scans + SL.total * ((size_t)q * o->nslots + j);
-      scan_hdrs[(size_t)q * o->nslots + j] = scan_header(blk, o->cap_points, o->cap_cells, false, o->with_kd);
-      ptrs[(size_t)q * o->nslots + j] = reinterpret_cast<ScanDev*>(blk);
-    }
+    for (int j = 0; j < o->nslots; j++)
+      scan_hdrs[(size_t)q * o->nslots + j] = scan_header(o->d_scans + SL.total * ((size_t)q * o->nslots + j), o->cap_points, o->cap_cells, false, o->with_kd);
     hdrs[q] = scratch_header(o->d_scratch + WL.total * (size_t)q, o->cap_points, o->pair_cap);
   }
   ok = ok && hipMemcpy2D(o->d_scans, SL.total, scan_hdrs.data(), sizeof(ScanDev), sizeof(ScanDev), scan_hdrs.size(), hipMemcpyHostToDevice) == hipSuccess;
-  ok = ok && hipMemcpy(o->d_scan_ptrs, ptrs.data(), sizeof(ScanDev*) * ptrs.size(), hipMemcpyHostToDevice) == hipSuccess;
   ok = ok && hipMemcpy(o->d_scratch_hdr, hdrs.data(), sizeof(BlockScratch) * hdrs.size(), hipMemcpyHostToDevice) == hipSuccess;
   if (!ok) { cfear_odometry_destroy(ctx, o); return cfear_fail(ctx, CFEAR_ERR_HIP, "odometry state upload"); }
-  rc = cfear_odometry_reset(ctx, o);
+  const int rc = cfear_odometry_reset(ctx, o);
   if (rc != CFEAR_OK) { cfear_odometry_destroy(ctx, o); return rc; }
   ok = hipEventCreateWithFlags(&o->ev_copied, hipEventDisableTiming) == hipSuccess;
   o->overlap = ctx->tune_odo_overlap < 0 ? 0 : (ctx->tune_odo_overlap > 8 ? 8 : ctx->tune_odo_overlap);
@@ -1582,7 +1519,7 @@ static int odo_step_clouds(cfear_ctx* ctx, cfear_odometry* o, const float* d_xyi
     if ((rc = odo_timed_event(ctx, o, o->filter_events, ctx->stream)) != CFEAR_OK) return rc;
   }
   if (o->profile && (rc = odo_timed_event(ctx, o, o->stage_events, ctx->stream)) != CFEAR_OK) return rc;
-  hipLaunchKernelGGL(features_cloud_step_kernel, dim3(o->B), dim3(BLOCK_F), 0, ctx->stream, d_xyi, capacity, d_counts, OP, o->d_states, o->d_scratch_hdr);
+  launch_features_cloud_step(o, OP, d_xyi, capacity, d_counts, o->B, ctx->stream);
   if (o->profile && (rc = odo_timed_event(ctx, o, o->stage_events, ctx->stream)) != CFEAR_OK) return rc;
   launch_register_step(OP, o->B, ctx->stream, o);
   if (o->profile && (rc = odo_timed_event(ctx, o, o->stage_events, ctx->stream)) != CFEAR_OK) return rc;
@@ -1594,7 +1531,7 @@ static int odo_step_clouds(cfear_ctx* ctx, cfear_odometry* o, const float* d_xyi
 
 int cfear_odometry_step_cloud_device(cfear_ctx* ctx, cfear_odometry* o, const float* d_xyi, int capacity, const int* d_counts) {
   if (!ctx || !o || !d_xyi || !d_counts || capacity <= 0) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_step_cloud: bad argument");
-  if (!odo_shape_ok(ctx, o)) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_step_cloud: submap_scan_size / k_strongest / filter_type changed after odometry_create, or a parity mode (cfear_tune NN_TIE_RULE / VOXEL_ORDER) was switched under the object");
+  CFEAR_TRY(odo_shape_check(ctx, o, "odometry_step_cloud"));
   if (capacity > o->cap_points) {
     char msg[256];
     snprintf(msg, sizeof(msg), "odometry_step_cloud: capacity %d exceeds the %d points per scan this object was created for (A * k_strongest, or cfar_max_points with "
@@ -1602,7 +1539,7 @@ int cfear_odometry_step_cloud_device(cfear_ctx* ctx, cfear_odometry* o, const fl
     return cfear_fail(ctx, CFEAR_ERR_INVALID, msg);
   }
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  { const int jrc = odo_join(ctx, o); if (jrc != CFEAR_OK) return jrc; }
+  CFEAR_TRY(odo_join(ctx, o));
   if (!o->d_flags) {  // counts beyond `capacity` are reported like every other truncation
     CFEAR_HIP_CHECK(ctx, hipMalloc(&o->d_flags, sizeof(int) * ((size_t)o->B + 1)));
     CFEAR_HIP_CHECK(ctx, hipMemsetAsync(o->d_flags, 0, sizeof(int) * ((size_t)o->B + 1), ctx->stream));
@@ -1612,8 +1549,7 @@ int cfear_odometry_step_cloud_device(cfear_ctx* ctx, cfear_odometry* o, const fl
 
 int cfear_odometry_step_device(cfear_ctx* ctx, cfear_odometry* o, const uint8_t* d_polar) {
   if (!ctx || !o || !d_polar) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_step: bad argument");
-  if (!odo_shape_ok(ctx, o))
-    return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_step: submap_scan_size / k_strongest / filter_type changed after odometry_create, or a parity mode (cfear_tune NN_TIE_RULE / VOXEL_ORDER) was switched under the object");
+  CFEAR_TRY(odo_shape_check(ctx, o, "odometry_step"));
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   if (o->filter == CFEAR_FILTER_CACFAR) {  // radar_driver.cpp:52-56, then the cloud route
     int rc = CFEAR_OK;
@@ -1654,12 +1590,7 @@ int cfear_odometry_step_device(cfear_ctx* ctx, cfear_odometry* o, const uint8_t*
     hipStream_t so = o->overlap ? o->so[i] : ctx->stream;
     if (o->overlap) CFEAR_HIP_CHECK(ctx, hipStreamWaitEvent(so, o->ev_filt[buf], 0));
     if (o->profile && (rc = odo_timed_event(ctx, o, o->stage_events, so)) != CFEAR_OK) return rc;
-    if (P.phase_times)
-      hipLaunchKernelGGL(features_step_kernel<true>, dim3(count), dim3(BLOCK_F), 0, so, o->d_slots[buf], ctx->d_trig, P, o->d_states,
-                         o->d_scan_ptrs, o->d_scratch_hdr);
-    else
-      hipLaunchKernelGGL(features_step_kernel<false>, dim3(count), dim3(BLOCK_F), 0, so, o->d_slots[buf], ctx->d_trig, P, o->d_states,
-                         o->d_scan_ptrs, o->d_scratch_hdr);
+    launch_features_step(ctx, o, P, o->d_slots[buf], count, so);
     if (o->overlap) CFEAR_HIP_CHECK(ctx, hipEventRecord(o->ev_free[buf][i], so));
     if (o->profile && (rc = odo_timed_event(ctx, o, o->stage_events, so)) != CFEAR_OK) return rc;
     launch_register_step(P, count, so, o);
@@ -1675,7 +1606,7 @@ int cfear_odometry_step_device(cfear_ctx* ctx, cfear_odometry* o, const uint8_t*
 int cfear_odometry_phase_times(cfear_ctx* ctx, cfear_odometry* o, int enable, long long* host_ticks /*[B][32]*/) {
   if (!ctx || !o) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_phase_times: bad argument");
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  { const int jrc = odo_join(ctx, o); if (jrc != CFEAR_OK) return jrc; }
+  CFEAR_TRY(odo_join(ctx, o));
   CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   const size_t bytes = sizeof(long long) * 32 * (size_t)o->B;
   if (enable >= 1 && enable <= 4) {  // (any other non-zero value: read without changing the mode)
@@ -1702,16 +1633,10 @@ int cfear_odometry_phase_times(cfear_ctx* ctx, cfear_odometry* o, int enable, lo
 int cfear_odometry_profile(cfear_ctx* ctx, cfear_odometry* o, int enable) {
   if (!ctx || !o) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_profile: bad argument");
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  { const int jrc = odo_join(ctx, o); if (jrc != CFEAR_OK) return jrc; }
+  CFEAR_TRY(odo_join(ctx, o));
   CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   o->filter_events.clear(); o->stage_events.clear(); o->pool_used = 0;  // the events go back to the pool
-  if (enable && o->pool.empty()) {  // created here, outside any timed region
-    for (int i = 0; i < 1024; i++) {
-      hipEvent_t e = nullptr;
-      CFEAR_HIP_CHECK(ctx, hipEventCreate(&e));
-      o->pool.push_back(e);
-    }
-  }
+  if (enable && o->pool.empty()) CFEAR_TRY(odo_grow_pool(ctx, o));  // created here, outside any timed region
   o->profile = enable != 0;
   return CFEAR_OK;
 }
@@ -1719,7 +1644,7 @@ int cfear_odometry_profile(cfear_ctx* ctx, cfear_odometry* o, int enable) {
 int cfear_odometry_profile_read(cfear_ctx* ctx, cfear_odometry* o, double* filter_seconds, int* filter_launches) {
   if (!ctx || !o) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_profile_read: bad argument");
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  { const int jrc = odo_join(ctx, o); if (jrc != CFEAR_OK) return jrc; }
+  CFEAR_TRY(odo_join(ctx, o));
   CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   double tf = 0;
   const int nf = (int)(o->filter_events.size() / 2);
@@ -1736,7 +1661,7 @@ int cfear_odometry_profile_read(cfear_ctx* ctx, cfear_odometry* o, double* filte
 int cfear_odometry_profile_read_stages(cfear_ctx* ctx, cfear_odometry* o, double* features_seconds, double* registration_seconds, int* launches) {
   if (!ctx || !o) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_profile_read_stages: bad argument");
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  { const int jrc = odo_join(ctx, o); if (jrc != CFEAR_OK) return jrc; }
+  CFEAR_TRY(odo_join(ctx, o));
   CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   double tf = 0, tr = 0;
   const int n = (int)(o->stage_events.size() / 3);
@@ -1892,10 +1817,10 @@ static int replay_impl_queue(cfear_ctx* ctx, cfear_odometry* o, const uint8_t* f
     // chip at one per compute unit). Many sequences: the batched kernels, two launches per sweep, whose occupancy is what counts.
     OP.cs.cov_out = d_cov6 ? d_cov6 + (size_t)t0 * o->B * 36 : nullptr;  // (the persistent kernels step it on per sweep)
     if (persistent && cfar) {
-      cfear_launch_replay_chunk_cloud(o->rp_cloud[b], o->cap_points, o->rp_cloud_n[b], cnt, o->B, &OP, o->d_states, o->d_scratch_hdr, o->d_cov_work, o->d_summaries,
+      cfear_launch_replay_chunk_cloud(o->rp_cloud[b], o->cap_points, o->rp_cloud_n[b], cnt, o->B, OP, o->d_states, o->d_scratch_hdr, o->d_cov_work, o->d_summaries,
                                       o->d_poses_out, d_records ? d_records + (size_t)t0 * o->B : nullptr, ctx->stream);
     } else if (persistent) {
-      cfear_launch_replay_chunk(o->rp_slots[b], cnt, o->B, ctx->d_trig, &OP, o->d_states, o->d_scratch_hdr, o->d_cov_work, o->d_summaries,
+      cfear_launch_replay_chunk(o->rp_slots[b], cnt, o->B, ctx->d_trig, OP, o->d_states, o->d_scratch_hdr, o->d_cov_work, o->d_summaries,
                                 o->d_poses_out, d_records ? d_records + (size_t)t0 * o->B : nullptr, ctx->stream);
     } else {
       for (int t = 0; t < cnt; t++) {
@@ -1929,8 +1854,7 @@ static int replay_impl(cfear_ctx* ctx, cfear_odometry* o, const uint8_t* frames,
 
 static int replay_check(cfear_ctx* ctx, cfear_odometry* o, const uint8_t* frames, int n_sweeps) {
   if (!ctx || !o || !frames || n_sweeps <= 0) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_replay: bad argument");
-  if (!odo_shape_ok(ctx, o))
-    return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_replay: submap_scan_size / k_strongest / filter_type changed after odometry_create, or a parity mode (cfear_tune NN_TIE_RULE / VOXEL_ORDER) was switched under the object");
+  CFEAR_TRY(odo_shape_check(ctx, o, "odometry_replay"));
   // CA-CFAR reads the images as dwords: every chunk of the replay starts a whole number of sweeps (of B images) after `frames`, so the base and the
   // sweep size decide the alignment of all of them - refused here, before any chunk has advanced the sequences' state
   if (o->filter == CFEAR_FILTER_CACFAR && ((reinterpret_cast<uintptr_t>(frames) & 3) != 0 || (n_sweeps > 1 && (((size_t)o->B * ctx->A * ctx->R) & 3) != 0)))
@@ -1983,7 +1907,7 @@ int cfear_odometry_set_cov_sampling(cfear_ctx* ctx, cfear_odometry* o, int enabl
     return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_set_cov_sampling: samples_per_axis < 1 or a range / scaler that is not finite");
   if (samples_per_axis > 8) return cfear_fail(ctx, CFEAR_ERR_UNSUPPORTED, "odometry_set_cov_sampling: at most 8 samples per axis (512 GetCost per sweep)");
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  { const int jrc = odo_join(ctx, o); if (jrc != CFEAR_OK) return jrc; }
+  CFEAR_TRY(odo_join(ctx, o));
   CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // nothing in flight reads the design or the costs while they are replaced
   const int m = samples_per_axis * samples_per_axis * samples_per_axis;
   std::vector<double> offs, A, design((size_t)13 * m);
@@ -2015,7 +1939,7 @@ int cfear_odometry_set_surface_recording(cfear_ctx* ctx, cfear_odometry* o, int 
   if (!enable) { o->surf_on = false; return CFEAR_OK; }
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   if (!o->d_cov_ctx) {
-    { const int jrc = odo_join(ctx, o); if (jrc != CFEAR_OK) return jrc; }
+    CFEAR_TRY(odo_join(ctx, o));
     CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     if (hipMalloc(&o->d_cov_ctx, sizeof(CovSampleCtx) * (size_t)o->B) != hipSuccess) return cfear_fail(ctx, CFEAR_ERR_NOMEM, "hipMalloc surface records");
     CFEAR_HIP_CHECK(ctx, hipMemset(o->d_cov_ctx, 0, sizeof(CovSampleCtx) * (size_t)o->B));
@@ -2036,7 +1960,7 @@ int cfear_odometry_surface(cfear_ctx* ctx, cfear_odometry* o, double res, int wi
     if (rc != CFEAR_OK) return cfear_fail(ctx, rc, "odometry_surface: more than CFEAR_SURFACE_MAX_SIDE pixels per side");
   }
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  { const int jrc = odo_join(ctx, o); if (jrc != CFEAR_OK) return jrc; }
+  CFEAR_TRY(odo_join(ctx, o));
   const int B = o->B;
   // what the last step's registrations used: the grid of each is centred on its recorded pose (computed here, on the host)
   std::vector<CovSampleCtx> rec;
@@ -2093,7 +2017,7 @@ int cfear_odometry_cov_samples(cfear_ctx* ctx, cfear_odometry* o, int sequence, 
   if (!ctx || !o || sequence < 0 || sequence >= o->B || (!costs && !sampled)) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_cov_samples: bad argument");
   if (!o->cov_on) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_cov_samples: cost sampling is off (cfear_odometry_set_cov_sampling)");
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  { const int jrc = odo_join(ctx, o); if (jrc != CFEAR_OK) return jrc; }
+  CFEAR_TRY(odo_join(ctx, o));
   CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   if (costs) CFEAR_HIP_CHECK(ctx, hipMemcpy(costs, o->d_cov_costs + (size_t)sequence * o->cov_m, sizeof(double) * o->cov_m, hipMemcpyDeviceToHost));
   if (sampled) {
@@ -2129,7 +2053,7 @@ static int odo_capacity_check(cfear_ctx* ctx, cfear_odometry* o, const char* wha
 int cfear_odometry_poses(cfear_ctx* ctx, cfear_odometry* o, double* poses_xyt) {
   if (!ctx || !o || !poses_xyt) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_poses: bad argument");
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  { const int jrc = odo_join(ctx, o); if (jrc != CFEAR_OK) return jrc; }
+  CFEAR_TRY(odo_join(ctx, o));
   CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(poses_xyt, o->d_poses_out, sizeof(double) * 3 * (size_t)o->B, hipMemcpyDeviceToHost, ctx->stream));
   CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   return odo_capacity_check(ctx, o, "odometry_poses");
@@ -2138,7 +2062,7 @@ int cfear_odometry_poses(cfear_ctx* ctx, cfear_odometry* o, double* poses_xyt) {
 int cfear_odometry_covariances(cfear_ctx* ctx, cfear_odometry* o, double* cov6) {
   if (!ctx || !o || !cov6) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_covariances: bad argument");
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  { const int jrc = odo_join(ctx, o); if (jrc != CFEAR_OK) return jrc; }
+  CFEAR_TRY(odo_join(ctx, o));
   CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(cov6, o->d_cov_work, sizeof(double) * 36 * (size_t)o->B, hipMemcpyDeviceToHost, ctx->stream));
   CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   return odo_capacity_check(ctx, o, "odometry_covariances");
@@ -2147,7 +2071,7 @@ int cfear_odometry_covariances(cfear_ctx* ctx, cfear_odometry* o, double* cov6) 
 int cfear_odometry_status(cfear_ctx* ctx, cfear_odometry* o, int32_t* per_sequence) {
   if (!ctx || !o) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_status: bad argument");
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  { const int jrc = odo_join(ctx, o); if (jrc != CFEAR_OK) return jrc; }
+  CFEAR_TRY(odo_join(ctx, o));
   CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   if (per_sequence) {
     if (o->d_flags) CFEAR_HIP_CHECK(ctx, hipMemcpy(per_sequence, o->d_flags + 1, sizeof(int) * (size_t)o->B, hipMemcpyDeviceToHost));
@@ -2160,7 +2084,7 @@ int cfear_odometry_summary(cfear_ctx* ctx, cfear_odometry* o, int sequence, cfea
                            int* n_keyframes) {
   if (!ctx || !o || sequence < 0 || sequence >= o->B) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_summary: bad argument");
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  { const int jrc = odo_join(ctx, o); if (jrc != CFEAR_OK) return jrc; }
+  CFEAR_TRY(odo_join(ctx, o));
   CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   if (summary) CFEAR_HIP_CHECK(ctx, hipMemcpy(summary, o->d_summaries + sequence, sizeof(cfear_reg_summary), hipMemcpyDeviceToHost));
   if (n_cells || n_keyframes) {

@@ -13,16 +13,8 @@
 
 static_assert(CFEAR_REG_MAX_SCANS == CFEAR_STEP_SMALL_SCANS, "common.h tells pipeline.hip when to launch these kernels");
 
-// pipeline.hip (launch_register_step): one instantiation per cost metric, the per-phase timers with the cost read at run time
-__attribute__((visibility("hidden"))) void cfear_launch_register_step_small(const void* odo_params, int count, hipStream_t st, void* states, void* const* scan_slots,
-                                                                           const void* scratch, double* poses_work, double* cov_work,
-                                                                           cfear_reg_summary* summaries, double* poses_out) {
-  const OdoParams& P = *static_cast<const OdoParams*>(odo_params);
-#define CFEAR_LAUNCH_REG(T, C) hipLaunchKernelGGL((register_step_kernel<T, C>), dim3(count), dim3(BLOCK_R), 0, st, P, static_cast<SeqState*>(states), \
-                                                  reinterpret_cast<ScanDev* const*>(scan_slots), static_cast<const BlockScratch*>(scratch), poses_work, cov_work, summaries, poses_out)
-  if (P.phase_times) CFEAR_LAUNCH_REG(true, -1);
-  else if (P.rp.cost == CFEAR_COST_P2L) CFEAR_LAUNCH_REG(false, CFEAR_COST_P2L);
-  else if (P.rp.cost == CFEAR_COST_P2D) CFEAR_LAUNCH_REG(false, CFEAR_COST_P2D);
-  else CFEAR_LAUNCH_REG(false, CFEAR_COST_P2P);
-#undef CFEAR_LAUNCH_REG
+// pipeline.hip (launch_register_kernel)
+void cfear_launch_register_step_small(const OdoParams& P, int count, hipStream_t st, SeqState* states, const BlockScratch* scratch, double* cov_work,
+                                      cfear_reg_summary* summaries, double* poses_out) {
+  CFEAR_LAUNCH_REG_BY_COST(register_step_kernel, P, count, st, states, nullptr, scratch, nullptr, cov_work, summaries, poses_out);
 }

@@ -36,15 +36,8 @@ __global__ __launch_bounds__(BLOCK_R, (CFEAR_LARGE_BLOCK / 256) * CFEAR_LARGE_WG
 }
 }  // namespace
 
-// pipeline.hip (launch_register_step): one instantiation per cost metric, the per-phase timers with the cost read at run time
-__attribute__((visibility("hidden"))) void cfear_launch_register_step_large(const void* odo_params, int count, hipStream_t st, void* states, const void* scratch,
-                                                                           double* cov_work, cfear_reg_summary* summaries, double* poses_out) {
-  const OdoParams& P = *static_cast<const OdoParams*>(odo_params);
-#define CFEAR_LAUNCH_REG(T, C) hipLaunchKernelGGL((register_step_large_kernel<T, C>), dim3(count), dim3(BLOCK_R), 0, st, P, static_cast<SeqState*>(states), \
-                                                  static_cast<const BlockScratch*>(scratch), cov_work, summaries, poses_out)
-  if (P.phase_times) CFEAR_LAUNCH_REG(true, -1);
-  else if (P.rp.cost == CFEAR_COST_P2L) CFEAR_LAUNCH_REG(false, CFEAR_COST_P2L);
-  else if (P.rp.cost == CFEAR_COST_P2D) CFEAR_LAUNCH_REG(false, CFEAR_COST_P2D);
-  else CFEAR_LAUNCH_REG(false, CFEAR_COST_P2P);
-#undef CFEAR_LAUNCH_REG
+// pipeline.hip (launch_register_kernel)
+void cfear_launch_register_step_large(const OdoParams& P, int count, hipStream_t st, SeqState* states, const BlockScratch* scratch, double* cov_work,
+                                      cfear_reg_summary* summaries, double* poses_out) {
+  CFEAR_LAUNCH_REG_BY_COST(register_step_large_kernel, P, count, st, states, scratch, cov_work, summaries, poses_out);
 }

@@ -94,19 +94,12 @@ __global__ __launch_bounds__(BLOCK_F) void replay_chunk_cloud_kernel(const float
 }
 }  // namespace
 
-__attribute__((visibility("hidden"))) void cfear_launch_replay_chunk_cloud(const float* d_xyi, int cap, const int* d_counts, int cnt, int B, const void* odo_params,
-                                                                          void* states, const void* scratch, double* cov_work, cfear_reg_summary* summaries,
-                                                                          double* poses_out, cfear_sweep_record* records, hipStream_t stream) {
-  const OdoParams& OP = *static_cast<const OdoParams*>(odo_params);
-  hipLaunchKernelGGL(replay_chunk_cloud_kernel, dim3(B), dim3(BLOCK_F), 0, stream, d_xyi, cap, d_counts, cnt, B, OP, static_cast<SeqState*>(states),
-                     static_cast<const BlockScratch*>(scratch), cov_work, summaries, poses_out, records);
+// pipeline.hip (replay_impl_queue): the chunk kernels on `stream`
+void cfear_launch_replay_chunk_cloud(const float* d_xyi, int cap, const int* d_counts, int cnt, int B, const OdoParams& OP, SeqState* states, const BlockScratch* scratch,
+                                     double* cov_work, cfear_reg_summary* summaries, double* poses_out, cfear_sweep_record* records, hipStream_t stream) {
+  hipLaunchKernelGGL(replay_chunk_cloud_kernel, dim3(B), dim3(BLOCK_F), 0, stream, d_xyi, cap, d_counts, cnt, B, OP, states, scratch, cov_work, summaries, poses_out, records);
 }
-
-// pipeline.hip (cfear_odometry_replay_host): launches the chunk kernel on `stream`
-__attribute__((visibility("hidden"))) void cfear_launch_replay_chunk(const uint32_t* d_slots, int cnt, int B, const double* d_trig, const void* odo_params,
-                                                                    void* states, const void* scratch, double* cov_work, cfear_reg_summary* summaries,
-                                                                    double* poses_out, cfear_sweep_record* records, hipStream_t stream) {
-  const OdoParams& OP = *static_cast<const OdoParams*>(odo_params);
-  hipLaunchKernelGGL(replay_chunk_kernel, dim3(B), dim3(BLOCK_F), 0, stream, d_slots, cnt, B, d_trig, OP, static_cast<SeqState*>(states),
-                     static_cast<const BlockScratch*>(scratch), cov_work, summaries, poses_out, records);
+void cfear_launch_replay_chunk(const uint32_t* d_slots, int cnt, int B, const double* d_trig, const OdoParams& OP, SeqState* states, const BlockScratch* scratch,
+                               double* cov_work, cfear_reg_summary* summaries, double* poses_out, cfear_sweep_record* records, hipStream_t stream) {
+  hipLaunchKernelGGL(replay_chunk_kernel, dim3(B), dim3(BLOCK_F), 0, stream, d_slots, cnt, B, d_trig, OP, states, scratch, cov_work, summaries, poses_out, records);
 }
