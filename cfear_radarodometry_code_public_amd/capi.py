@@ -78,6 +78,7 @@ EXPORTS = [
     "cfear_odometry_replay_host", "cfear_odometry_replay_device", "cfear_odometry_replay_host_cov", "cfear_odometry_replay_device_cov",
     "cfear_odometry_set_cov_sampling", "cfear_odometry_cov_samples", "cfear_host_alloc", "cfear_host_free",
     "cfear_surface_dims", "cfear_get_surface", "cfear_odometry_set_surface_recording", "cfear_odometry_surface",
+    "cfear_odometry_set_sequence_params", "cfear_odometry_sequence_params", "cfear_odometry_set_sequence_sources",
     "cfear_odometry_covariances", "cfear_odometry_status", "cfear_odometry_summary", "cfear_odometry_profile", "cfear_odometry_profile_read", "cfear_odometry_profile_read_stages", "cfear_odometry_phase_times", "cfear_time_kstrongest",
 ]
 
@@ -156,6 +157,9 @@ def lib():
         "cfear_get_surface": (C.c_int, [vp, C.POINTER(vp), C.c_int, f64p, f64p, C.c_int, C.c_double, C.c_int, f64p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "cfear_odometry_set_surface_recording": (C.c_int, [vp, vp, C.c_int]),
         "cfear_odometry_surface": (C.c_int, [vp, vp, C.c_double, C.c_int, vp, vp, vp, vp]),
+        "cfear_odometry_set_sequence_params": (C.c_int, [vp, vp, vp, C.c_int]),
+        "cfear_odometry_sequence_params": (C.c_int, [vp, vp, C.c_int, C.POINTER(Params)]),
+        "cfear_odometry_set_sequence_sources": (C.c_int, [vp, vp, i32p, C.c_int, C.c_int]),
         "cfear_host_alloc": (C.c_int, [vp, C.c_size_t, C.POINTER(vp)]),
         "cfear_host_free": (None, [vp, vp]),
         "cfear_odometry_summary": (C.c_int, [vp, vp, C.c_int, C.POINTER(RegSummary), C.POINTER(C.c_int),
@@ -527,6 +531,7 @@ class Odometry:
 
     def __init__(self, ctx, n_sequences):
         self._ctx, self.B = ctx, int(n_sequences)
+        self.n_sources = self.B  # input sweeps per step (set_sequence_sources)
         self._h = C.c_void_p()
         ctx._check(ctx._L.cfear_odometry_create(ctx._h, self.B, C.byref(self._h)), "cfear_odometry_create")
 
@@ -555,18 +560,18 @@ class Odometry:
 
     def step_host(self, polar):
         polar = np.ascontiguousarray(polar, dtype=np.uint8)
-        assert polar.shape == (self.B, self._ctx.A, self._ctx.R)
+        assert polar.shape == (self.n_sources, self._ctx.A, self._ctx.R), polar.shape
         self._ctx._check(self._ctx._L.cfear_odometry_step_host(self._ctx._h, self._h, polar.ctypes.data),
                          "cfear_odometry_step_host")
 
     def replay_host(self, frames, records=True, covariances=False):
-        """frames: uint8 [n, B, A, R] (or [n, A, R] for one sequence), e.g. a view of Context.pinned(). Runs the n sweeps with
+        """frames: uint8 [n, B, A, R] (or [n, A, R] for one sequence; [n, n_sources, A, R] with a source map), e.g. a view of Context.pinned(). Runs the n sweeps with
         no host round trip in between; -> structured array [n, B] of SWEEP_RECORD_DTYPE (or None). covariances=True: -> (records,
         [n, B, 6, 6] cov_current after every sweep) (cfear_odometry_replay_host_cov)."""
         frames = np.ascontiguousarray(frames, dtype=np.uint8)
         if frames.ndim == 3:
             frames = frames[:, None]
-        assert frames.shape[1:] == (self.B, self._ctx.A, self._ctx.R), frames.shape
+        assert frames.shape[1:] == (self.n_sources, self._ctx.A, self._ctx.R), frames.shape
         n = frames.shape[0]
         rec = np.zeros((n, self.B), dtype=SWEEP_RECORD_DTYPE) if records else None
         if not covariances:
@@ -588,6 +593,36 @@ class Odometry:
         self._ctx._check(self._ctx._L.cfear_odometry_replay_device_cov(self._ctx._h, self._h, _addr(d_frames), int(n_sweeps),
                                                                        _addr(d_records) if d_records is not None else None, _addr(d_cov)),
                          "cfear_odometry_replay_device_cov")
+
+    def set_sequence_params(self, rows):
+        """rows: one Params per sequence (the points of a parameter grid, utils/worker:26-99; replay.param_grid builds them), or None for
+        the context's parameters again (cfear_odometry_set_sequence_params). Before the first sweep since creation / reset()."""
+        if rows is None:
+            self._ctx._check(self._ctx._L.cfear_odometry_set_sequence_params(self._ctx._h, self._h, None, 0), "cfear_odometry_set_sequence_params")
+            return
+        rows = list(rows)
+        arr = (Params * len(rows))(*rows)
+        self._ctx._check(self._ctx._L.cfear_odometry_set_sequence_params(self._ctx._h, self._h, C.cast(arr, C.c_void_p), len(rows)),
+                         "cfear_odometry_set_sequence_params")
+
+    def sequence_params(self, q):
+        """the Params sequence q runs with (cfear_odometry_sequence_params)"""
+        p = Params()
+        self._ctx._check(self._ctx._L.cfear_odometry_sequence_params(self._ctx._h, self._h, int(q), C.byref(p)), "cfear_odometry_sequence_params")
+        return p
+
+    def set_sequence_sources(self, source, n_sources=None):
+        """source[q]: the input sweep sequence q reads; afterwards step_host / step_device / the replays take n_sources sweeps per step
+        instead of B. None: one sweep per sequence again (cfear_odometry_set_sequence_sources)."""
+        if source is None:
+            self._ctx._check(self._ctx._L.cfear_odometry_set_sequence_sources(self._ctx._h, self._h, None, 0, 0), "cfear_odometry_set_sequence_sources")
+            self.n_sources = self.B
+            return
+        src = np.ascontiguousarray(source, dtype=np.int32)
+        ns = int(n_sources) if n_sources is not None else int(src.max()) + 1
+        self._ctx._check(self._ctx._L.cfear_odometry_set_sequence_sources(self._ctx._h, self._h, src.ctypes.data, int(src.size), ns),
+                         "cfear_odometry_set_sequence_sources")
+        self.n_sources = ns
 
     def set_cov_sampling(self, enable=True, xy_range=0.4, yaw_range=0.0043625, samples_per_axis=3, covariance_scaler=4.0):
         """estimate_cov_by_sampling and its companions (odometrykeyframefuser.h:104-110) for every sequence, from the next sweep on"""

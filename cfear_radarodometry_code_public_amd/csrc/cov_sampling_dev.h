@@ -134,14 +134,14 @@ __device__ inline void cov_sample_body(unsigned char* lds, int q, const OdoParam
             par[i] = i < L ? cx->pose[i] : CS.offs[3 * k + (i - L)] + (i == L ? bx : (i == L + 1 ? by : bt));
           __syncthreads();
           // (the sample's poses are converted in place where get_cost_block keeps its parameter vectors: thread i reads and writes pose i)
-          get_cost_block(sp, n, par, OP.rp, RW, par, sh, itr, &s_cost[0], nullptr, 0, &s_cnt[0]);
+          get_cost_block(sp, n, par, OP.rp, RW, par, sh, itr, &s_cost[0], nullptr, 0, &s_cnt[0], seq_row(OP, q));
           __syncthreads();
           if (tid == 0) { if (s_cnt[0] >= 0) last = s_cost[0]; costs[k] = last; }
         }
       } else {
         // the keyframes' side of the problem once: poses as get_cost_block converts them (Affine3dToVectorXYeZ of vectorToAffine3d,
         // :196), their affine maps (ctl_publish_build) and 1-NN views
-        if (tid == 0) { sh->rp = OP.rp; sh->srs = sp[nk]->rsrc; sh->scc = (long long)sp[nk]->cap_cells; }
+        if (tid == 0) { sh->rp = OP.rp; seq_reg_params(sh->rp, seq_row(OP, q)); sh->srs = sp[nk]->rsrc; sh->scc = (long long)sp[nk]->cap_cells; }
         for (int i = tid; i < nk; i += CFEAR_REG_BLOCK) {
           Aff2 T = aff_from_xyt(cx->pose[3 * i], cx->pose[3 * i + 1], cx->pose[3 * i + 2]);
           double v[3]; aff_to_xyt(T, v);

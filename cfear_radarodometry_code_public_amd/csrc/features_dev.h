@@ -251,7 +251,7 @@ __device__ __forceinline__ void point_regs_to_global(const PointRegs& R, float* 
 // slots of one sweep -> compensated cloud (getPeaksFilteredPointCloud, radar_filters.cpp:309-337, + Compensate, utils.cpp:96-107)
 // in S->xyi AND in the registers of the block (PR), with the bounding box. Returns the number of points.
 __device__ inline int cloud_step_block(const uint32_t* __restrict__ slots, int A, int k, const double* __restrict__ trig,
-                                       float range_res_f, float min_distance_f, float* __restrict__ xyi, int cap, int compensate,
+                                       float range_res_f, float min_distance_f, int z_min, float* __restrict__ xyi, int cap, int compensate,
                                        double m0, double m1, double m2, int ccw, int* red_i, float* red_f, double* tab,
                                        int tab_bearings, float bounds[4], PointRegs& PR, bool store = true) {
   // store = false: the caller can do without the cloud in S->xyi when the points are handed over in registers - 58 KB per
@@ -266,6 +266,10 @@ __device__ inline int cloud_step_block(const uint32_t* __restrict__ slots, int A
   const int min_range_bin = (int)ceil((double)min_distance_f / range_res);  // radar_filters.cpp:315
   const double range_res_half = range_res / 2.0;
   const int items = A * k;
+  // z_min: a slot also has to reach this intensity (a sequence's own threshold behind a filter that ran with a lower one; 0: every valid slot).
+  // One comparison for both: the valid bit sits right above the intensity byte
+  const int valid_z = 256 + z_min;
+#define CFEAR_SLOT_VALID_Z(s) ((int)(((s) >> 16) & 0x1FFu) >= valid_z)
   const int wv = threadIdx.x >> 6, ln = lane_id(), nwv = CFEAR_FEAT_BLOCK >> 6;
   // per-bearing table in LDS, six doubles each: principal angle, sin / cos of the compensation rotation at the bearing's
   // angle, its sweep fraction, cos / sin of the bearing (so that the per-point loop has no global load to wait for)
@@ -309,7 +313,7 @@ __device__ inline int cloud_step_block(const uint32_t* __restrict__ slots, int A
     for (int r = 0; r < CFEAR_PT; r++) {
       const int t = (wv * RC + r) * 64 + ln;
       const bool inr = (r < RC) & (t < items);
-      const bool on = inr & (CFEAR_SLOT_VALID(sv[r]) != 0) & (CFEAR_SLOT_RANGE(sv[r]) > min_range_bin);  // :327
+      const bool on = inr & CFEAR_SLOT_VALID_Z(sv[r]) & (CFEAR_SLOT_RANGE(sv[r]) > min_range_bin);  // :327
       PR.bal[r] = __ballot(on);
       PR.onm |= on ? 1u << r : 0u;
       wtot += __popcll(PR.bal[r]);
@@ -383,7 +387,7 @@ __device__ inline int cloud_step_block(const uint32_t* __restrict__ slots, int A
 #pragma unroll
     for (int u = 0; u < 8; u++) {
       const int t = t_wave + (r0 + u) * 64 + ln;
-      const bool on = (r0 + u < RC) & (t < items) & (CFEAR_SLOT_VALID(sv[u]) != 0) & (CFEAR_SLOT_RANGE(sv[u]) > min_range_bin);  // :327
+      const bool on = (r0 + u < RC) & (t < items) & CFEAR_SLOT_VALID_Z(sv[u]) & (CFEAR_SLOT_RANGE(sv[u]) > min_range_bin);  // :327
       wtot += __popcll(__ballot(on));
     }
   }
@@ -412,7 +416,7 @@ __device__ inline int cloud_step_block(const uint32_t* __restrict__ slots, int A
         const int t = t_wave + (r0 + u) * 64 + ln;
         const uint32_t s = sv[u];
         const int range = CFEAR_SLOT_RANGE(s);
-        const bool hit = (r0 + u < RC) & (t < items) & (CFEAR_SLOT_VALID(s) != 0) & (range > min_range_bin);
+        const bool hit = (r0 + u < RC) & (t < items) & CFEAR_SLOT_VALID_Z(s) & (range > min_range_bin);
         const unsigned long long bal = __ballot(hit);
         const int o = run + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
         run += __popcll(bal);
@@ -447,6 +451,7 @@ __device__ inline int cloud_step_block(const uint32_t* __restrict__ slots, int A
   __syncthreads();
   point_regs_from_global(xyi, total, PR);
   return total;
+#undef CFEAR_SLOT_VALID_Z
 }
 
 // closed-form symmetric 2x2 eigen-decomposition; identical formulas to the oracle's eig2()

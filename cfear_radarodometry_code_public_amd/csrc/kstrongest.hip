@@ -992,14 +992,15 @@ __global__ __launch_bounds__(256, 4) void kstrongest_pair_kernel(const uint8_t* 
 }  // namespace
 
 // Launch-shape knobs live in the context (cfear_tune, include/cfear_hip.h): occupancy variant and rows per wave.
-int cfear_launch_kstrongest(cfear_ctx* ctx, const uint8_t* d_polar, int n_scans, uint32_t* d_slots, hipStream_t stream) {
+int cfear_launch_kstrongest(cfear_ctx* ctx, const uint8_t* d_polar, int n_scans, uint32_t* d_slots, hipStream_t stream, int u_zmin_override) {
   const int A = ctx->A, R = ctx->R, k = ctx->par.k_strongest;
   if (!d_polar || !d_slots || n_scans <= 0) return cfear_fail(ctx, CFEAR_ERR_INVALID, "kstrongest: null buffer or n_scans <= 0");
   if (k < 1 || k > 64) return cfear_fail(ctx, CFEAR_ERR_UNSUPPORTED, "kstrongest: k_strongest must be in 1..64");
   if ((reinterpret_cast<uintptr_t>(d_polar) & 15) != 0) return cfear_fail(ctx, CFEAR_ERR_INVALID, "kstrongest: polar buffer must be 16-byte aligned");
   const long long n_rows = (long long)n_scans * A;
   const long long alloc = n_rows * R;
-  const int u_zmin = (int)(uint8_t)(int)ctx->par.z_min;  // float -> int (radar_filters.cpp:198) -> uchar (:212)
+  // float -> int (radar_filters.cpp:198) -> uchar (:212); a batched odometry object with per-sequence z_min filters with the smallest of them
+  const int u_zmin = u_zmin_override >= 0 ? u_zmin_override : (int)(uint8_t)(int)ctx->par.z_min;
   // one resident wave per SIMD slot (256 CUs x 4 SIMDs x occupancy); each wave walks consecutive rows
   const int occ_eff = (R + 27 <= 4 * 1024) ? (ctx->tune_k1_occ >= 7 ? 7 : (ctx->tune_k1_occ <= 5 ? 5 : 6)) : (R + 27 <= 8 * 1024 ? 3 : 2);
   // A wave walks a few consecutive rows (the threshold of one azimuth is the first guess for the next): four rows

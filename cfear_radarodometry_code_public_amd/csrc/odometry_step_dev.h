@@ -81,7 +81,20 @@ struct OdoParams {
   CovSampling cs;  // cost-sampling covariance and / or per-sweep covariances (cs.ctx / cs.cov_out null: neither)
   int* flags;  // word 0 for the odometry object, word 1 + q for sequence q: bit 0 = some scan had more cells than its block holds, bit 1 = some cloud had more points
                // than the object is sized for (both CFEAR_ERR_CAPACITY); null: cannot happen
+  // per-sequence parameters and input sweeps (cfear_odometry_set_sequence_params / _set_sequence_sources): [B] rows, row q for sequence q.
+  // null: every sequence runs with the values above and reads sweep q (the production kernels do exactly the work they did without it)
+  const SeqParams* seq;
+  int n_sources;  // sweeps per step in the filter's output (the sequences when there is no source map)
 };
+// sequence q's row, or null without a table. The table pointer and q are the same in every lane of a workgroup; read through the first
+// lane they are uniform for the compiler too, wherever OP lives (a kernel argument; the LDS copy of the persistent replay kernels), so the
+// row's fields arrive as scalar loads
+__device__ __forceinline__ SeqRow seq_row(const OdoParams& OP, int q) {
+  const unsigned long long a = (unsigned long long)OP.seq;
+  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)a), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(a >> 32));
+  const SeqParams* t = (const SeqParams*)(((unsigned long long)hi << 32) | lo);
+  return t ? (SeqRow)(t + __builtin_amdgcn_readfirstlane(q)) : (SeqRow) nullptr;
+}
 
 static_assert(sizeof(SeqState) == 3 * sizeof(Aff2) + 4 * sizeof(int) + MAX_SCANS * (sizeof(int) + sizeof(Aff2)), "SeqState is sized by the fixed MAX_SCANS");
 static_assert(sizeof(CovSampleCtx) == 4 * sizeof(int) + sizeof(double) + MAX_SCANS * (sizeof(int) + 3 * sizeof(double)), "CovSampleCtx is sized by the fixed MAX_SCANS");
@@ -211,15 +224,23 @@ __device__ __forceinline__ void features_step_body(unsigned char* lds /* FeatLds
   double mot[3]; aff_to_xyt(TprevMot, mot);
   float bounds[4];
   PointRegs PR;
+  // the sequence's own values where it has a row: the sweep it reads, its z_min (applied to the slots of a filter that ran with the smallest
+  // z_min of the object: the k strongest above z are the members above z of the k strongest above any z' <= z), compensation, res, weights
+  FeatureParams fp = OP.fp;
+  int src = q, compensate = OP.compensate, z_min = 0;
+  if (const SeqRow row = seq_row(OP, q)) {
+    src = row->source; compensate = row->compensate; z_min = row->z_min;
+    fp.radius = row->radius; fp.weight_intensity = row->weight_intensity;
+  }
   // (the compact feature path works from the registers: the 58 KB of the cloud are only written when somebody reads them)
-  const int n = cloud_step_block(slots_all + (size_t)q * OP.A * OP.k, OP.A, OP.k, trig, OP.fp.range_res, OP.fp.min_distance,
-                                 cur->xyi, cur->cap_points, OP.compensate, mot[0], mot[1], mot[2], OP.ccw,
+  const int n = cloud_step_block(slots_all + (size_t)src * OP.A * OP.k, OP.A, OP.k, trig, OP.fp.range_res, OP.fp.min_distance, z_min,
+                                 cur->xyi, cur->cap_points, compensate, mot[0], mot[1], mot[2], OP.ccw,
                                  reinterpret_cast<int*>(lds + FeatLdsC::red_i), reinterpret_cast<float*>(lds + FeatLdsC::red_f),
                                  reinterpret_cast<double*>(lds + FeatLdsC::pxy),  // 6 doubles per bearing where the sorted points go later
                                  (int)(CFEAR_CPT_CAP * 8 / (6 * sizeof(double))), bounds, PR, false);
   if (TIMED) { pt.mark(); pt.mark(); }
   CFEAR_STOP_AT(1, );
-  features_dispatch(cur, n, OP.fp, B, lds, TIMED ? &pt : nullptr, n > 0 ? bounds : nullptr, true, true, PR, true);  // :161
+  features_dispatch(cur, n, fp, B, lds, TIMED ? &pt : nullptr, n > 0 ? bounds : nullptr, true, true, PR, true);  // :161
   if (OP.flags && threadIdx.x == 0 && cur->status == CFEAR_ERR_CAPACITY) { atomicOr(OP.flags, 1); OP.flags[1 + q] |= 1; }  // (thread 0 wrote the status itself; word 1 + q: this sequence's own)
   if (!TIMED && OP.wg_times && threadIdx.x == 0) OP.wg_times[(size_t)q * 32 + 1] = (long long)wall_clock64();
 }
@@ -250,13 +271,18 @@ __device__ __forceinline__ void features_cloud_step_body(unsigned char* lds /* F
     bytes &= (w >= 0.f && w <= 255.f && w == (float)(int)w) ? 1 : 0;
   }
   const bool byte_intensities = __syncthreads_and(bytes) != 0;  // (the barrier also makes the copy visible to the whole block)
-  if (OP.compensate) {
+  FeatureParams fp = OP.fp;
+  int compensate = OP.compensate;
+  if (const SeqRow row = seq_row(OP, q)) {  // (z_min and the source belong to the filter in front: uniform on this route)
+    compensate = row->compensate; fp.radius = row->radius; fp.weight_intensity = row->weight_intensity;
+  }
+  if (compensate) {
     double mot[3]; aff_to_xyt(TprevMot, mot);
     compensate_block(cur->xyi, n, mot[0], mot[1], mot[2], OP.ccw);  // :147 (the peaks cloud of :149 is empty and never read)
   }
   PointRegs PR;
   point_regs_from_global(cur->xyi, n, PR);
-  features_dispatch(cur, n, OP.fp, B, lds, nullptr, nullptr, false, byte_intensities, PR);  // :161
+  features_dispatch(cur, n, fp, B, lds, nullptr, nullptr, false, byte_intensities, PR);  // :161
   if (OP.flags && threadIdx.x == 0 && cur->status == CFEAR_ERR_CAPACITY) { atomicOr(OP.flags, 1); OP.flags[1 + q] |= 1; }
   if (OP.wg_times && threadIdx.x == 0) OP.wg_times[(size_t)q * 32 + 1] = (long long)wall_clock64();
 }
@@ -324,7 +350,7 @@ __device__ __forceinline__ void register_step_body(unsigned char* lds /* RegLds:
   __syncthreads();
   const RegScratch RW = make_rscratch(B, lds);
   register_block<KCOST>(sp, ns, poses, cov_work + (size_t)q * 36, OP.rp, RW, reinterpret_cast<double*>(lds + RegLds::par),
-                 reinterpret_cast<RegShared*>(lds + RegLds::regsh), sum, TIMED ? &pt : nullptr);  // :186 (result ignored, :184-186)
+                 reinterpret_cast<RegShared*>(lds + RegLds::regsh), sum, TIMED ? &pt : nullptr, nullptr, seq_row(OP, q));  // :186 (result ignored, :184-186)
   __syncthreads();
   if (TIMED) pt.mark();
   if (tid == 0) {
@@ -349,10 +375,12 @@ __device__ __forceinline__ void register_step_body(unsigned char* lds /* RegLds:
     st->Tcurrent = Tcurrent;
     const Aff2 Tkeydiff = aff_mul(aff_inv(st->kf_pose[nkf - 1]), Tcurrent);  // :227
     bool fuse = true;
-    if (OP.use_keyframe) {  // KeyFrameBasedFuse (:62-73)
+    const SeqRow row = seq_row(OP, q);  // the sequence's own keyframe rule where it has a row
+    if (row ? row->use_keyframe : OP.use_keyframe) {  // KeyFrameBasedFuse (:62-73)
       const double tn = sqrt(Tkeydiff.t0 * Tkeydiff.t0 + Tkeydiff.t1 * Tkeydiff.t1);
       const double rot = fabs(atan2(Tkeydiff.l2, Tkeydiff.l3));
-      fuse = (tn > OP.min_keyframe_dist) || (rot > OP.min_keyframe_rot_deg * 3.14159265358979323846 / 180.0);
+      const double kd = row ? row->min_keyframe_dist : OP.min_keyframe_dist, kr = row ? row->min_keyframe_rot_deg : OP.min_keyframe_rot_deg;
+      fuse = (tn > kd) || (rot > kr * 3.14159265358979323846 / 180.0);
     }
     if (fuse) {  // AddToReference (:470-476)
       int m = nkf;

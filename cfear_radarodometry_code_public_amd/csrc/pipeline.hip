@@ -200,7 +200,7 @@ __global__ __launch_bounds__(BLOCK_R, 3) void surface_build_step_kernel(OdoParam
   const CovSampleCtx* cx = OP.cs.ctx + q;
   const int n = cx->n;  // (block-uniform)
   if (n < 2) {
-    if (threadIdx.x == 0) { hdr[q].blk = nullptr; hdr[q].cap = 0; hdr[q].nblk = 0; hdr[q].prior_on = 0; hdr[q].yaw = 0; }
+    if (threadIdx.x == 0) { hdr[q].blk = nullptr; hdr[q].cap = 0; hdr[q].nblk = 0; hdr[q].prior_on = 0; hdr[q].yaw = 0; hdr[q].loss = 0; hdr[q].loss_limit = 0; }
     if (NAIVE) for (int p = threadIdx.x; p < pixels * pixels; p += BLOCK_R) out[(size_t)q * pixels * pixels + p] = __builtin_nan("");
     return;
   }
@@ -211,7 +211,7 @@ __global__ __launch_bounds__(BLOCK_R, 3) void surface_build_step_kernel(OdoParam
   __syncthreads();
   const RegScratch W = make_rscratch(scratch[q], lds);
   RegShared* sh = reinterpret_cast<RegShared*>(lds + RegLds::regsh);
-  surface_build_block(sp, n, cx->pose, OP.rp, W, reinterpret_cast<double*>(lds + RegLds::par), sh, cx->itr, nullptr, hdr + q);
+  surface_build_block(sp, n, cx->pose, OP.rp, W, reinterpret_cast<double*>(lds + RegLds::par), sh, cx->itr, nullptr, hdr + q, seq_row(OP, q));
   if (NAIVE) {
     __syncthreads();
     surface_naive_eval(sh, hdr + q, coords + (size_t)q * 2 * pixels, nxy[2 * q], nxy[2 * q + 1], pixels, out + (size_t)q * pixels * pixels);
@@ -219,11 +219,9 @@ __global__ __launch_bounds__(BLOCK_R, 3) void surface_build_step_kernel(OdoParam
 }
 // the evaluation (the hot path): grid (tiles of BLOCK * PPT pixels, problems)
 template <int COST, int PPT>
-__global__ __launch_bounds__(CFEAR_SURFACE_BLOCK) void surface_eval_kernel(const SurfHdr* hdr, const double* coords, const int* nxy, int pixels, int loss,
-                                                                           double loss_limit, double* out) {
+__global__ __launch_bounds__(CFEAR_SURFACE_BLOCK) void surface_eval_kernel(const SurfHdr* hdr, const double* coords, const int* nxy, int pixels, double* out) {
   const int q = blockIdx.y;
-  surface_eval_tile<COST, PPT>(hdr + q, coords + (size_t)q * 2 * pixels, nxy[2 * q], nxy[2 * q + 1], pixels, loss, loss_limit,
-                               out + (size_t)q * pixels * pixels, blockIdx.x);
+  surface_eval_tile<COST, PPT>(hdr + q, coords + (size_t)q * 2 * pixels, nxy[2 * q], nxy[2 * q + 1], pixels, out + (size_t)q * pixels * pixels, blockIdx.x);
 }
 
 // ---- batched odometry: one launch per stage and sweep (bodies: odometry_step_dev.h) ----
@@ -504,7 +502,16 @@ struct cfear_odometry {
   double* d_surf_coords = nullptr;   // [B][2][pixels]
   int* d_surf_nxy = nullptr;         // [B][2]
   int surf_px_cap = 0;               // pixels per side d_surf_coords is sized for
+  // per-sequence parameters / shared input sweeps (cfear_odometry_set_sequence_params / _set_sequence_sources)
+  std::vector<cfear_params> seq_rows;  // [B] the caller's table; empty: every sequence runs with the context's parameters
+  std::vector<int32_t> seq_src;        // [B] the sweep each sequence reads; empty: sweep q for sequence q
+  int n_sources = 0;                   // sweeps per step with a source map (0: B)
+  SeqParams* d_seq = nullptr;          // [B] what the kernels read (OdoParams::seq); exists while either of the above does
+  cfear_params seq_par_seen;           // the context's parameters d_seq was built and the rows were checked against
+  int seq_zmin = -1;                   // the filter's threshold: the smallest z_min of the rows (-1: the context's)
+  long long sweeps = 0;                // sweeps processed since cfear_odometry_create / cfear_odometry_reset
 };
+static int odo_sources(const cfear_odometry* o) { return o->n_sources > 0 ? o->n_sources : o->B; }
 // a timing event from the pool, recorded on `st`
 static int odo_grow_pool(cfear_ctx* ctx, cfear_odometry* o) {
   for (int i = 0; i < 1024; i++) {
@@ -556,7 +563,101 @@ static OdoParams odo_params(const cfear_ctx* ctx, const cfear_odometry* o) {
     OP.cs.pinv = o->d_cov_design; OP.cs.offs = o->d_cov_design + 10 * (size_t)o->cov_m;
     OP.cs.costs = o->d_cov_costs; OP.cs.scaler = o->cov_scaler; OP.cs.m = o->cov_m;
   }
+  OP.seq = o->d_seq; OP.n_sources = odo_sources(o);
   return OP;
+}
+
+// ---- per-sequence parameters (the grids of utils/worker:26-99 as sequences of one object) ------------------------------------------
+static SeqParams seq_row_of(const cfear_params& p, int source) {
+  SeqParams r;
+  memset(&r, 0, sizeof(r));
+  r.loss_limit = p.loss_limit; r.covar_scale = p.covar_scale; r.regularization = p.regularization;
+  r.min_keyframe_dist = p.min_keyframe_dist; r.min_keyframe_rot_deg = p.min_keyframe_rot_deg;
+  r.radius = (float)p.res; r.weight_intensity = p.weight_intensity; r.loss = p.loss; r.weight_opt = p.weight_opt;
+  r.max_outer = p.max_itr_association; r.min_itr = p.min_itr; r.max_inner = p.max_solver_iterations;
+  r.compensate = p.compensate; r.use_keyframe = p.use_keyframe;
+  r.z_min = (int)(uint8_t)(int)p.z_min;  // as the filter takes it (radar_filters.cpp:198, :212)
+  r.source = source;
+  return r;
+}
+// may the rows be the sequences of `o` under the context's parameters? The fields that size memory or select a kernel are the object's
+static int seq_rows_check(cfear_ctx* ctx, const cfear_odometry* o, const cfear_params* rows, int n, const char* what) {
+  const cfear_params& c = ctx->par;
+  for (int q = 0; q < n; q++) {
+    const cfear_params& r = rows[q];
+    const char* f = nullptr;
+    if (r.k_strongest != c.k_strongest) f = "k_strongest";
+    else if (r.cost != c.cost) f = "cost";
+    else if (r.submap_scan_size != c.submap_scan_size) f = "submap_scan_size";
+    else if (r.filter_type != c.filter_type) f = "filter_type";
+    else if (r.range_res != c.range_res) f = "range_res";
+    else if (r.min_distance != c.min_distance) f = "min_distance";
+    else if (r.downsample_factor != c.downsample_factor) f = "downsample_factor";
+    else if (r.radar_ccw != c.radar_ccw) f = "radar_ccw";
+    else if (r.assoc_radius != c.assoc_radius) f = "assoc_radius";
+    else if (r.cfar_window_size != c.cfar_window_size) f = "cfar_window_size";
+    else if (r.cfar_nb_guard_cells != c.cfar_nb_guard_cells) f = "cfar_nb_guard_cells";
+    else if (r.cfar_false_alarm_rate != c.cfar_false_alarm_rate) f = "cfar_false_alarm_rate";
+    else if (r.cfar_max_points != c.cfar_max_points) f = "cfar_max_points";
+    else if (r.cfar_max_distance != c.cfar_max_distance) f = "cfar_max_distance";
+    else if (o->filter == CFEAR_FILTER_CACFAR && r.z_min != c.z_min) f = "z_min (the CA-CFAR detector's static threshold)";
+    if (f) {
+      char msg[320];
+      snprintf(msg, sizeof(msg), "%s: row %d differs from the context's parameters in %s, which sizes memory or selects a kernel for the whole object "
+               "(per-sequence: z_min, res, weight_intensity, loss, loss_limit, weight_opt, covar_scale, regularization, compensate, the keyframe rule, the iteration limits)", what, q, f);
+      return cfear_fail(ctx, CFEAR_ERR_INVALID, msg);
+    }
+    const char* bad = nullptr;  // the values cfear_set_params would refuse
+    if (!(r.res > 0.05) || !std::isfinite(r.res)) bad = "res must be finite and > 0.05";
+    else if (r.loss < 0 || r.loss > 5) bad = "unknown loss";
+    else if (r.max_itr_association < 1 || r.max_itr_association > CFEAR_MAX_OUTER) bad = "max_itr_association must be in 1..64";
+    else if (r.max_solver_iterations < 1) bad = "max_solver_iterations must be >= 1";
+    else if (r.min_itr < 0) bad = "min_itr must be >= 0";
+    else if (!std::isfinite(r.z_min) || !std::isfinite(r.loss_limit)) bad = "z_min and loss_limit must be finite";
+    if (bad) {
+      char msg[160];
+      snprintf(msg, sizeof(msg), "%s: row %d: %s", what, q, bad);
+      return cfear_fail(ctx, CFEAR_ERR_INVALID, msg);
+    }
+  }
+  return CFEAR_OK;
+}
+// (re)builds the device table from the rows (or the context's parameters) and the source map; frees it when neither is set. The context
+// stream and the object's streams are idle when this is called.
+static int seq_table_upload(cfear_ctx* ctx, cfear_odometry* o) {
+  if (o->seq_rows.empty() && o->seq_src.empty()) {
+    if (o->d_seq) (void)hipFree(o->d_seq);
+    o->d_seq = nullptr; o->seq_zmin = -1;
+    return CFEAR_OK;
+  }
+  std::vector<SeqParams> t((size_t)o->B);
+  int zmin = 255;
+  for (int q = 0; q < o->B; q++) {
+    t[q] = seq_row_of(o->seq_rows.empty() ? ctx->par : o->seq_rows[q], o->seq_src.empty() ? q : o->seq_src[q]);
+    zmin = std::min(zmin, t[q].z_min);
+  }
+  if (!o->d_seq && hipMalloc(&o->d_seq, sizeof(SeqParams) * (size_t)o->B) != hipSuccess) return cfear_fail(ctx, CFEAR_ERR_NOMEM, "hipMalloc sequence parameter table");
+  CFEAR_HIP_CHECK(ctx, hipMemcpy(o->d_seq, t.data(), sizeof(SeqParams) * t.size(), hipMemcpyHostToDevice));
+  o->seq_zmin = o->seq_rows.empty() ? -1 : zmin;
+  o->seq_par_seen = ctx->par;
+  return CFEAR_OK;
+}
+// before a step / replay / surface call: cfear_set_params since the table was built? The rows are checked against the new parameters
+// (loud, never silent) and the table follows them
+static int odo_seq_sync(cfear_ctx* ctx, cfear_odometry* o, const char* what) {
+  if (!o->d_seq || memcmp(&o->seq_par_seen, &ctx->par, sizeof(cfear_params)) == 0) return CFEAR_OK;
+  if (!o->seq_rows.empty()) CFEAR_TRY(seq_rows_check(ctx, o, o->seq_rows.data(), o->B, what));
+  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  CFEAR_TRY(odo_join(ctx, o));
+  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  return seq_table_upload(ctx, o);
+}
+static int seq_fresh_check(cfear_ctx* ctx, const cfear_odometry* o, const char* what) {
+  if (o->sweeps == 0) return CFEAR_OK;
+  char msg[256];
+  snprintf(msg, sizeof(msg), "%s: the object has processed %lld sweeps since cfear_odometry_create / cfear_odometry_reset - keyframes built under other parameters or "
+           "from other sweeps are not a state the reference can be in; call cfear_odometry_reset first", what, o->sweeps);
+  return cfear_fail(ctx, CFEAR_ERR_INVALID, msg);
 }
 // the registration step kernel of a sweep. register_step.hip holds the production instantiations (one per cost metric, registrations of
 // up to CFEAR_STEP_SMALL_SCANS scans: a bigger LDS match array); a larger submap runs the instantiation of this file (any cost, 64 scans)
@@ -1115,7 +1216,7 @@ static void launch_surface_eval(const RegParams& P, int problems, const SurfHdr*
   const bool two = (long long)t2 * problems >= 512;
   const dim3 grid(two ? t2 : (np + CFEAR_SURFACE_BLOCK - 1) / CFEAR_SURFACE_BLOCK, problems);
 #define CFEAR_SURF_EVAL(C, K) hipLaunchKernelGGL((surface_eval_kernel<C, K>), grid, dim3(CFEAR_SURFACE_BLOCK), 0, st, d_hdr, d_coords, d_nxy, \
-                                                 pixels, P.loss, P.loss_limit, d_out)
+                                                 pixels, d_out)
   if (P.cost == CFEAR_COST_P2L) { if (two) CFEAR_SURF_EVAL(CFEAR_COST_P2L, 2); else CFEAR_SURF_EVAL(CFEAR_COST_P2L, 1); }
   else if (P.cost == CFEAR_COST_P2D) { if (two) CFEAR_SURF_EVAL(CFEAR_COST_P2D, 2); else CFEAR_SURF_EVAL(CFEAR_COST_P2D, 1); }
   else { if (two) CFEAR_SURF_EVAL(CFEAR_COST_P2P, 2); else CFEAR_SURF_EVAL(CFEAR_COST_P2P, 1); }
@@ -1354,7 +1455,7 @@ void cfear_odometry_destroy(cfear_ctx* ctx, cfear_odometry* o) {
   void* ptrs[] = {o->d_scans, o->d_scratch, o->d_scratch_hdr, o->d_states, o->d_cov_work, o->d_summaries, o->d_poses_out, o->d_slots[0], o->d_slots[1], o->d_polar, o->d_phase_times,
                   o->rp_polar[0], o->rp_polar[1], o->rp_slots[0], o->rp_slots[1], o->d_records, o->d_flags, o->d_order, o->d_work,
                   o->d_cloud, o->d_cloud_n, o->d_cfar_rows, o->rp_cloud[0], o->rp_cloud[1], o->rp_cloud_n[0], o->rp_cloud_n[1], o->rp_cfar_rows,
-                  o->d_cov_ctx, o->d_cov_design, o->d_cov_costs, o->d_cov_seq, o->d_surf_hdr, o->d_surf_coords, o->d_surf_nxy};
+                  o->d_cov_ctx, o->d_cov_design, o->d_cov_costs, o->d_cov_seq, o->d_surf_hdr, o->d_surf_coords, o->d_surf_nxy, o->d_seq};
   for (hipEvent_t e : {o->rp_filt[0], o->rp_filt[1], o->rp_used[0], o->rp_used[1], o->rp_in}) if (e) (void)hipEventDestroy(e);
   if (o->rp_stream) (void)hipStreamDestroy(o->rp_stream);
   for (void* p : ptrs) if (p) (void)hipFree(p);
@@ -1382,6 +1483,7 @@ int cfear_odometry_reset(cfear_ctx* ctx, cfear_odometry* o) {
   if (o->d_flags) CFEAR_HIP_CHECK(ctx, hipMemsetAsync(o->d_flags, 0, sizeof(int) * ((size_t)o->B + 1), ctx->stream));
   o->order_ready = false;
   o->surf_ready = false;
+  o->sweeps = 0;  // (the parameter table and the source map stay)
   CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   return CFEAR_OK;
 }
@@ -1524,7 +1626,7 @@ static int odo_step_clouds(cfear_ctx* ctx, cfear_odometry* o, const float* d_xyi
   launch_register_step(OP, o->B, ctx->stream, o);
   if (o->profile && (rc = odo_timed_event(ctx, o, o->stage_events, ctx->stream)) != CFEAR_OK) return rc;
   o->surf_ready = OP.cs.ctx != nullptr;
-  o->step_no++;
+  o->step_no++; o->sweeps++;
   CFEAR_HIP_CHECK(ctx, hipGetLastError());
   return CFEAR_OK;
 }
@@ -1532,6 +1634,10 @@ static int odo_step_clouds(cfear_ctx* ctx, cfear_odometry* o, const float* d_xyi
 int cfear_odometry_step_cloud_device(cfear_ctx* ctx, cfear_odometry* o, const float* d_xyi, int capacity, const int* d_counts) {
   if (!ctx || !o || !d_xyi || !d_counts || capacity <= 0) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_step_cloud: bad argument");
   CFEAR_TRY(odo_shape_check(ctx, o, "odometry_step_cloud"));
+  if (!o->seq_src.empty())
+    return cfear_fail(ctx, CFEAR_ERR_UNSUPPORTED, "odometry_step_cloud: the object has a source map (cfear_odometry_set_sequence_sources), which the cloud route does not "
+                      "read - it takes one cloud per sequence; clear the map (NULL) first");
+  CFEAR_TRY(odo_seq_sync(ctx, o, "odometry_step_cloud"));
   if (capacity > o->cap_points) {
     char msg[256];
     snprintf(msg, sizeof(msg), "odometry_step_cloud: capacity %d exceeds the %d points per scan this object was created for (A * k_strongest, or cfar_max_points with "
@@ -1551,6 +1657,7 @@ int cfear_odometry_step_device(cfear_ctx* ctx, cfear_odometry* o, const uint8_t*
   if (!ctx || !o || !d_polar) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_step: bad argument");
   CFEAR_TRY(odo_shape_check(ctx, o, "odometry_step"));
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  CFEAR_TRY(odo_seq_sync(ctx, o, "odometry_step"));
   if (o->filter == CFEAR_FILTER_CACFAR) {  // radar_driver.cpp:52-56, then the cloud route
     int rc = CFEAR_OK;
     if (o->profile && (rc = odo_timed_event(ctx, o, o->filter_events, ctx->stream)) != CFEAR_OK) return rc;
@@ -1571,7 +1678,7 @@ int cfear_odometry_step_device(cfear_ctx* ctx, cfear_odometry* o, const uint8_t*
   }
   // radar_driver.cpp:58
   if (o->profile && (rc = odo_timed_event(ctx, o, o->filter_events, sf)) != CFEAR_OK) return rc;
-  rc = cfear_launch_kstrongest(ctx, d_polar, o->B, o->d_slots[buf], sf);
+  rc = cfear_launch_kstrongest(ctx, d_polar, odo_sources(o), o->d_slots[buf], sf, o->seq_zmin);  // (once per source sweep, at the smallest z_min of the rows)
   if (rc != CFEAR_OK) return rc;
   if (o->profile && (rc = odo_timed_event(ctx, o, o->filter_events, sf)) != CFEAR_OK) return rc;
   if (o->overlap) {
@@ -1598,7 +1705,7 @@ int cfear_odometry_step_device(cfear_ctx* ctx, cfear_odometry* o, const uint8_t*
   }
   if (o->overlap) o->filt_pending[buf] = true;
   o->surf_ready = OP.cs.ctx != nullptr;
-  o->step_no++;
+  o->step_no++; o->sweeps++;
   CFEAR_HIP_CHECK(ctx, hipGetLastError());
   return CFEAR_OK;
 }
@@ -1680,7 +1787,7 @@ int cfear_odometry_profile_read_stages(cfear_ctx* ctx, cfear_odometry* o, double
 int cfear_odometry_step_host(cfear_ctx* ctx, cfear_odometry* o, const uint8_t* h_polar) {
   if (!ctx || !o || !h_polar) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_step_host: bad argument");
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  const size_t bytes = (size_t)o->B * ctx->A * ctx->R;
+  const size_t bytes = (size_t)odo_sources(o) * ctx->A * ctx->R;  // (cfear_odometry_set_sequence_sources releases a staging buffer of another size)
   if (!o->d_polar && hipMalloc(&o->d_polar, bytes + 64) != hipSuccess) return cfear_fail(ctx, CFEAR_ERR_NOMEM, "hipMalloc polar batch");
   // the staging buffer is reused: the copy waits for the filter of the previous sweep (its only reader), not for that
   // sweep's features / registration
@@ -1720,7 +1827,7 @@ static int replay_ensure(cfear_ctx* ctx, cfear_odometry* o, int chunk, bool stag
     }
     o->rp_ready = true;
   }
-  const size_t sweep = (size_t)o->B * ctx->A * ctx->R, slots = (size_t)o->B * o->cap_points;
+  const size_t sweep = (size_t)odo_sources(o) * ctx->A * ctx->R, slots = (size_t)odo_sources(o) * o->cap_points;  // (a source map: CFEAR_FILTER_KSTRONG only)
   if (chunk > o->rp_chunk) {
     CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(o->rp_stream));
     CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
@@ -1769,7 +1876,8 @@ static int replay_ensure(cfear_ctx* ctx, cfear_odometry* o, int chunk, bool stag
 // they lie); d_records: where the per-sweep records go on the device (null: none)
 static int replay_impl_queue(cfear_ctx* ctx, cfear_odometry* o, const uint8_t* frames, bool on_device, int n_sweeps, cfear_sweep_record* d_records,
                              double* d_cov6) {
-  const size_t sweep = (size_t)o->B * ctx->A * ctx->R, slots = (size_t)o->B * o->cap_points;
+  const int nsrc = odo_sources(o);  // input sweeps per step: the sequences, or the sources of a source map
+  const size_t sweep = (size_t)nsrc * ctx->A * ctx->R, slots = (size_t)nsrc * o->cap_points;
   // chunk: enough sweeps for the filter to run at its streaming rate (>= ~16 k azimuth rows per launch) and for the copy of the
   // next chunk to hide behind the odometry kernels of this one, at most 256 MB per buffer (host route: of staged sweeps; device
   // route: of filter slots - there is no staging)
@@ -1802,7 +1910,7 @@ static int replay_impl_queue(cfear_ctx* ctx, cfear_odometry* o, const uint8_t* f
       src = o->rp_polar[b];
     }
     const int frc = cfar ? odo_launch_cfar(ctx, o, src, cnt * o->B, o->rp_cloud[b], o->rp_cloud_n[b], o->rp_cfar_rows, o->rp_stream)  // radar_driver.cpp:52-56
-                         : cfear_launch_kstrongest(ctx, src, cnt * o->B, o->rp_slots[b], o->rp_stream);  // radar_driver.cpp:58, pose-independent
+                         : cfear_launch_kstrongest(ctx, src, cnt * nsrc, o->rp_slots[b], o->rp_stream, o->seq_zmin);  // radar_driver.cpp:58, pose-independent
     if (frc != CFEAR_OK) return frc;
     CFEAR_HIP_CHECK(ctx, hipEventRecord(o->rp_filt[b], o->rp_stream));
     return CFEAR_OK;
@@ -1832,7 +1940,7 @@ static int replay_impl_queue(cfear_ctx* ctx, cfear_odometry* o, const uint8_t* f
     }
     CFEAR_HIP_CHECK(ctx, hipEventRecord(o->rp_used[b], ctx->stream));
     o->rp_used_pending[b] = true;
-    o->step_no += cnt;
+    o->step_no += cnt; o->sweeps += cnt;
     if (c + 1 < nchunks && (rc = stage(c + 1)) != CFEAR_OK) return rc;  // (queued after this chunk's launches: a copy from pageable memory blocks the host)
   }
   CFEAR_HIP_CHECK(ctx, hipGetLastError());
@@ -1855,6 +1963,8 @@ static int replay_impl(cfear_ctx* ctx, cfear_odometry* o, const uint8_t* frames,
 static int replay_check(cfear_ctx* ctx, cfear_odometry* o, const uint8_t* frames, int n_sweeps) {
   if (!ctx || !o || !frames || n_sweeps <= 0) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_replay: bad argument");
   CFEAR_TRY(odo_shape_check(ctx, o, "odometry_replay"));
+  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  CFEAR_TRY(odo_seq_sync(ctx, o, "odometry_replay"));
   // CA-CFAR reads the images as dwords: every chunk of the replay starts a whole number of sweeps (of B images) after `frames`, so the base and the
   // sweep size decide the alignment of all of them - refused here, before any chunk has advanced the sequences' state
   if (o->filter == CFEAR_FILTER_CACFAR && ((reinterpret_cast<uintptr_t>(frames) & 3) != 0 || (n_sweeps > 1 && (((size_t)o->B * ctx->A * ctx->R) & 3) != 0)))
@@ -1960,6 +2070,7 @@ int cfear_odometry_surface(cfear_ctx* ctx, cfear_odometry* o, double res, int wi
     if (rc != CFEAR_OK) return cfear_fail(ctx, rc, "odometry_surface: more than CFEAR_SURFACE_MAX_SIDE pixels per side");
   }
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  CFEAR_TRY(odo_seq_sync(ctx, o, "odometry_surface"));
   CFEAR_TRY(odo_join(ctx, o));
   const int B = o->B;
   // what the last step's registrations used: the grid of each is centred on its recorded pose (computed here, on the host)
@@ -2011,6 +2122,70 @@ int cfear_odometry_surface(cfear_ctx* ctx, cfear_odometry* o, double res, int wi
     CFEAR_HIP_CHECK(ctx, hipGetLastError());
   }
   return cap_rc;
+}
+
+// ---- per-sequence parameters and shared input sweeps (odometrykeyframefuser.h:72-114; utils/worker:26-99) -----------------------------
+int cfear_odometry_set_sequence_params(cfear_ctx* ctx, cfear_odometry* o, const cfear_params* rows, int n_rows) {
+  if (!ctx || !o || (rows && n_rows != o->B)) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_set_sequence_params: bad argument (n_rows must be the object's n_sequences)");
+  CFEAR_TRY(seq_fresh_check(ctx, o, "odometry_set_sequence_params"));
+  if (rows) CFEAR_TRY(seq_rows_check(ctx, o, rows, n_rows, "odometry_set_sequence_params"));
+  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  CFEAR_TRY(odo_join(ctx, o));
+  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  std::vector<cfear_params> keep;
+  if (rows) keep.assign(rows, rows + n_rows);
+  o->seq_rows.swap(keep);
+  const int rc = seq_table_upload(ctx, o);
+  if (rc != CFEAR_OK) { o->seq_rows.swap(keep); (void)seq_table_upload(ctx, o); }  // (the previous table)
+  return rc;
+}
+
+int cfear_odometry_sequence_params(cfear_ctx* ctx, cfear_odometry* o, int sequence, cfear_params* out) {
+  if (!ctx || !o || !out || sequence < 0 || sequence >= o->B) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_sequence_params: bad argument");
+  *out = o->seq_rows.empty() ? ctx->par : o->seq_rows[(size_t)sequence];
+  return CFEAR_OK;
+}
+
+int cfear_odometry_set_sequence_sources(cfear_ctx* ctx, cfear_odometry* o, const int32_t* source, int n_sequences, int n_sources) {
+  if (!ctx || !o || (source && (n_sequences != o->B || n_sources < 1 || n_sources > o->B)))
+    return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_set_sequence_sources: bad argument (n_sequences must be the object's, 1 <= n_sources <= n_sequences)");
+  CFEAR_TRY(seq_fresh_check(ctx, o, "odometry_set_sequence_sources"));
+  if (source) {
+    if (o->filter == CFEAR_FILTER_CACFAR)
+      return cfear_fail(ctx, CFEAR_ERR_UNSUPPORTED, "odometry_set_sequence_sources: filter_type CA-CFAR objects take one sweep per sequence (the detector's clouds are "
+                        "per sequence); source maps are for k-strongest objects");
+    for (int q = 0; q < n_sequences; q++)
+      if (source[q] < 0 || source[q] >= n_sources) {
+        char msg[160];
+        snprintf(msg, sizeof(msg), "odometry_set_sequence_sources: source[%d] = %d is outside [0, %d)", q, (int)source[q], n_sources);
+        return cfear_fail(ctx, CFEAR_ERR_INVALID, msg);
+      }
+  }
+  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  CFEAR_TRY(odo_join(ctx, o));
+  if (o->rp_stream) CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(o->rp_stream));
+  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  std::vector<int32_t> keep;
+  int keep_n = source ? n_sources : 0;
+  if (source) keep.assign(source, source + n_sequences);
+  o->seq_src.swap(keep); std::swap(o->n_sources, keep_n);
+  const int rc = seq_table_upload(ctx, o);
+  if (rc != CFEAR_OK) { o->seq_src.swap(keep); std::swap(o->n_sources, keep_n); (void)seq_table_upload(ctx, o); return rc; }
+  // both parities of the filter-ahead slot buffers hold one slot block per input sweep (nothing is in flight: the streams were joined above)
+  {
+    uint32_t* ns[2] = {nullptr, nullptr};
+    const size_t bytes = sizeof(uint32_t) * (size_t)odo_sources(o) * o->cap_points;
+    if (hipMalloc(&ns[0], bytes) != hipSuccess || hipMalloc(&ns[1], bytes) != hipSuccess) {
+      if (ns[0]) (void)hipFree(ns[0]);
+      o->seq_src.swap(keep); std::swap(o->n_sources, keep_n); (void)seq_table_upload(ctx, o);
+      return cfear_fail(ctx, CFEAR_ERR_NOMEM, "hipMalloc filter slot buffers for the source map");
+    }
+    for (int i = 0; i < 2; i++) { (void)hipFree(o->d_slots[i]); o->d_slots[i] = ns[i]; o->filt_pending[i] = false; }
+  }
+  // the staging and chunk buffers are sized per input sweep of a step: released here, allocated again (for the sources) by the next call that needs them
+  for (void** p : {(void**)&o->d_polar, (void**)&o->rp_polar[0], (void**)&o->rp_polar[1], (void**)&o->rp_slots[0], (void**)&o->rp_slots[1]}) { if (*p) (void)hipFree(*p); *p = nullptr; }
+  o->rp_chunk = 0; o->rp_polar_chunk = 0; o->rp_used_pending[0] = o->rp_used_pending[1] = false;
+  return CFEAR_OK;
 }
 
 int cfear_odometry_cov_samples(cfear_ctx* ctx, cfear_odometry* o, int sequence, double* costs, int* sampled) {

@@ -24,6 +24,27 @@ struct RegParams {
                // the non-zero rules take the general association path (slow: sensitivity / parity modes)
 };
 
+// One row of a batched odometry object's per-sequence parameter table (cfear_odometry_set_sequence_params / _set_sequence_sources: the
+// evaluation grids of utils/worker:26-99 as sequences of one object, odometrykeyframefuser.h:72-114): the fields of cfear_params that may
+// differ between sequences, as the kernels take them, and the input sweep the sequence reads. The table lives in device memory that no
+// kernel writes; a workgroup reads its sequence's row through a wave-uniform pointer (scalar loads).
+struct SeqParams {
+  double loss_limit, covar_scale, regularization, min_keyframe_dist, min_keyframe_rot_deg;
+  float radius;  // (float)res
+  int weight_intensity, loss, weight_opt, max_outer, min_itr, max_inner, compensate, use_keyframe;
+  int z_min;     // as the filter compares it: (uint8_t)(int)z_min
+  int source;    // the sweep of a step's input this sequence reads
+  int pad_;
+};
+typedef const __attribute__((address_space(4))) SeqParams* SeqRow;  // (constant address space: never written while a kernel may read it)
+// the registration's parameters of a sequence with a row (null: P stays what the context gave)
+__device__ __forceinline__ void seq_reg_params(RegParams& P, SeqRow row) {
+  if (!row) return;
+  P.loss = row->loss; P.weight_opt = row->weight_opt;
+  P.loss_limit = row->loss_limit; P.covar_scale = row->covar_scale; P.regularization = row->regularization;
+  P.max_outer = row->max_outer; P.min_itr = row->min_itr; P.max_inner = row->max_inner;
+}
+
 // Per-block global scratch: compacted matches (SoA) + per-pair association result.
 struct RegScratch {
   double* tmx; double* tmy;  // Ttar * tar_mean
@@ -1497,11 +1518,12 @@ __device__ __forceinline__ void ctl_step(LRegShared* sh, long long* acc = nullpt
 template <int KCOST = -1>
 __device__ inline int register_block(ScanDev* const* scans, int n, double* poses, double* cov6, const RegParams& P_in,
                                      const RegScratch& W_in, double* par_lds, RegShared* sh, cfear_reg_summary* out,
-                                     PhaseTimer* pt = nullptr, const double* prior_cov6 = nullptr) {
+                                     PhaseTimer* pt = nullptr, const double* prior_cov6 = nullptr, SeqRow row = nullptr) {
   const int tid = threadIdx.x;
   LRegShared* ls = (LRegShared*)sh;  // the same object through an LDS-typed pointer (see LRegShared)
   if (tid == 0) {
     sh->rp = P_in; sh->rw = W_in;
+    seq_reg_params(sh->rp, row);
     sh->rio.poses = poses; sh->rio.cov6 = cov6; sh->rio.out = out; sh->rio.par = par_lds; sh->rio.n = n;
   }
   __syncthreads();
@@ -1599,11 +1621,13 @@ __device__ inline int register_block(ScanDev* const* scans, int n, double* poses
 // ceres::Problem::Evaluate with default options: *score = 1/2 sum rho, residuals = sqrt(rho') r per residual in
 // residual-block order. *n_res = number of residuals, or -1 where the reference returns false (<= 1 residuals).
 __device__ inline void get_cost_block(ScanDev* const* scans, int n, const double* poses, const RegParams& P_in, const RegScratch& W_in,
-                                      double* par_lds, RegShared* sh, int itr, double* score, double* residuals, int cap, int* n_res) {
+                                      double* par_lds, RegShared* sh, int itr, double* score, double* residuals, int cap, int* n_res,
+                                      SeqRow row = nullptr) {
   const int tid = threadIdx.x;
   LRegShared* ls = (LRegShared*)sh;
   if (tid == 0) {
     sh->rp = P_in; sh->rw = W_in;
+    seq_reg_params(sh->rp, row);
     sh->rio.poses = nullptr; sh->rio.cov6 = nullptr; sh->rio.out = nullptr; sh->rio.par = par_lds; sh->rio.n = n;
   }
   for (int i = tid; i < n; i += CFEAR_REG_BLOCK) {  // Affine3dToVectorXYeZ (:196)

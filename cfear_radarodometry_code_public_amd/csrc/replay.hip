@@ -42,12 +42,12 @@ __device__ __noinline__ void cov_sample_stage_general(unsigned char* lds, int q,
   cov_sample_body<true>(lds, q, *P, scratch, cov_work);
 }
 
-__global__ __launch_bounds__(BLOCK_F) void replay_chunk_kernel(const uint32_t* slots_chunk /*[cnt][B][A * k]*/, int cnt, int B, const double* trig,
+__global__ __launch_bounds__(BLOCK_F) void replay_chunk_kernel(const uint32_t* slots_chunk /*[cnt][n_sources][A * k]*/, int cnt, int B, const double* trig,
                                                                OdoParams OP, SeqState* states, const BlockScratch* scratch, double* cov_work,
                                                                cfear_reg_summary* summaries, double* poses_out, cfear_sweep_record* records /*[cnt][B] or null*/) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[kChunkLds];
   const int q = OP.seq0 + (int)blockIdx.x;
-  const size_t sweep_slots = (size_t)B * OP.A * OP.k;
+  const size_t sweep_slots = (size_t)OP.n_sources * OP.A * OP.k;  // (a sweep of the chunk: one slot block per source, B without a source map)
   __shared__ OdoParams P;  // by pointer to the stages: LDS, not a per-thread stack copy
   if (threadIdx.x == 0) P = OP;
   for (int t = 0; t < cnt; t++) {

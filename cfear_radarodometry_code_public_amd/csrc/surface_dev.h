@@ -28,6 +28,8 @@ struct SurfHdr {
   long long cap;
   int nblk;           // residual blocks
   int prior_on;       // the soft prior joins (mahalanobisDistanceError, n_scan_normal.h:259-290)
+  int loss;           // the robust loss the problem was built under (a sequence's own on the batched route) and its limit
+  double loss_limit;
   double pL[9], pguess[3], palpha, yaw;
 };
 }  // namespace cfear_dev
@@ -38,11 +40,13 @@ namespace {
 // :35-38) with the object's itr_ (:222), through the registration's association (tie rules, weights, radius rule). prior_cov6: the
 // soft prior's covariance (reg_cov.back()), null: soft_constraints false. Every thread of the workgroup calls it.
 __device__ inline void surface_build_block(ScanDev* const* scans, int n, const double* poses, const RegParams& P_in, const RegScratch& W_in,
-                                           double* par_lds, RegShared* sh, int itr, const double* prior_cov6, SurfHdr* hdr) {
+                                           double* par_lds, RegShared* sh, int itr, const double* prior_cov6, SurfHdr* hdr,
+                                           SeqRow row = nullptr) {
   const int tid = threadIdx.x;
   LRegShared* ls = (LRegShared*)sh;
   if (tid == 0) {
     sh->rp = P_in; sh->rw = W_in;
+    seq_reg_params(sh->rp, row);
     sh->rio.poses = nullptr; sh->rio.cov6 = nullptr; sh->rio.out = nullptr; sh->rio.par = par_lds; sh->rio.n = n;
   }
   for (int i = tid; i < n; i += CFEAR_REG_BLOCK) {  // Affine3dToVectorXYeZ (:35-38)
@@ -86,6 +90,7 @@ __device__ inline void surface_build_block(ScanDev* const* scans, int n, const d
   }
   if (tid == 0) {
     hdr->blk = ls->rw.tmx; hdr->cap = (long long)ls->rw.cap; hdr->nblk = M; hdr->yaw = ls->xcur[2];
+    hdr->loss = P.loss; hdr->loss_limit = P.loss_limit;
     const int nres = M * ((P.cost == CFEAR_COST_P2L) ? 1 : 2);
     hdr->prior_on = 0;
     if (prior_cov6 && nres > 1) {  // the prior is added after the residual-count check (:370-377)
@@ -102,8 +107,7 @@ __device__ inline void surface_build_block(ScanDev* const* scans, int n, const d
 // coords: the x values (rows) then the y values (columns) the reference's accumulating loops visit, pixels each; nx, ny of them
 // are visited, the other cells are NaN. Tile t of the problem covers pixels t * BLOCK * PPT .. + BLOCK * PPT - 1 (row-major).
 template <int COST, int PPT>
-__device__ __forceinline__ void surface_eval_tile(const SurfHdr* hdr, const double* coords, int nx, int ny, int pixels, int loss, double loss_limit,
-                                                  double* out, int tile) {
+__device__ __forceinline__ void surface_eval_tile(const SurfHdr* hdr, const double* coords, int nx, int ny, int pixels, double* out, int tile) {
   typedef __attribute__((address_space(3))) double lds_f64_t;
   __shared__ double s_blk[8 * CFEAR_SURFACE_CHUNK];
   lds_f64_t* lb = (lds_f64_t*)s_blk;
@@ -111,6 +115,8 @@ __device__ __forceinline__ void surface_eval_tile(const SurfHdr* hdr, const doub
   const int M = hdr->nblk;
   const long long cap = hdr->cap;
   const double* blk = hdr->blk;
+  const int loss = hdr->loss;  // (what the build stage recorded: uniform over the workgroup)
+  const double loss_limit = hdr->loss_limit;
   const int np = pixels * pixels;
   double px[PPT], py[PPT], cost[PPT];
   int pix[PPT];

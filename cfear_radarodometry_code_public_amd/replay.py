@@ -19,6 +19,59 @@ import numpy as np
 from . import capi, kitti, readers
 
 
+# the nesting of the reference's evaluation grids (utils/worker:42-87, outermost loop first) by the cfear_params field each loop sets
+GRID_ORDER = ("radar_ccw", "compensate", "cost", "submap_scan_size", "min_keyframe_dist", "res", "k_strongest", "z_min", "loss", "loss_limit",
+              "covar_scale", "regularization", "weight_intensity", "weight_opt")
+
+
+def param_grid(base, **axes):
+    """The parameter sets of a nested-loop evaluation grid in the reference's loop order (utils/worker:26-99: ... res, k_strongest, z_min,
+    loss, loss_limit, covar_scale, regularization, weight_intensity, weight_opt innermost), whatever order the axes are given in; axes the
+    reference's worker does not loop over (iteration limits, ...) nest inside those, in the order given. base: a capi.Params; each axis a
+    list of values of that field. -> list of capi.Params, job 1 first. Pure Python (no device)."""
+    import copy
+    import itertools
+    for k in axes:
+        if not hasattr(base, k):
+            raise AttributeError(k)
+    names = [k for k in GRID_ORDER if k in axes] + [k for k in axes if k not in GRID_ORDER]
+    rows = []
+    for values in itertools.product(*[list(axes[k]) for k in names]):
+        p = copy.copy(base) if not isinstance(base, capi.Params) else capi.Params.from_buffer_copy(base)
+        for k, v in zip(names, values):
+            setattr(p, k, v)
+        rows.append(p)
+    return rows
+
+
+def replay_grid(frames, rows, A=None, R=None, gt=None, device=0, piece=256, context_params=None):
+    """One recording under len(rows) parameter sets in one batched odometry object: frames uint8 [n, A, R], rows a list of capi.Params that
+    agree in the object-wide fields (param_grid of one base does). The recording is the single source sweep of every sequence: it is
+    copied and filtered once per sweep. -> dict(poses [n, len(rows), 3], records, drift: per row KITTI drift against gt ([n, 4, 4]
+    poses) or None)."""
+    frames = np.ascontiguousarray(frames, dtype=np.uint8)
+    n, A, R = frames.shape
+    rows = list(rows)
+    piece = max(1, int(piece))
+    ctx = capi.Context(context_params if context_params is not None else rows[0], A, R, device=device)
+    odo = None
+    try:
+        odo = ctx.odometry(len(rows))
+        odo.set_sequence_params(rows)
+        odo.set_sequence_sources(np.zeros(len(rows), dtype=np.int32), 1)
+        recs = [odo.replay_host(frames[t0:t0 + piece, None]) for t0 in range(0, n, piece)]
+        rec = np.concatenate(recs, axis=0)
+    finally:
+        if odo is not None:
+            odo.release()
+        ctx.close()
+    poses = np.array(rec["pose"])
+    drift = None
+    if gt is not None:
+        drift = [kitti.drift(np.asarray(gt)[:n], kitti.poses_from_xyt(poses[:, q])) for q in range(len(rows))]
+    return {"poses": poses, "records": rec, "drift": drift}
+
+
 def sweeps(args):
     if args.bag:
         for kind, t, payload in readers.BagReader(args.bag).sweeps_and_gt(args.image_topic, args.gt_topic):

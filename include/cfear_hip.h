@@ -365,6 +365,36 @@ int cfear_odometry_set_surface_recording(cfear_ctx* ctx, cfear_odometry* odo, in
  * CFEAR_ERR_INVALID while neither the recording nor the cost sampling is on. */
 int cfear_odometry_surface(cfear_ctx* ctx, cfear_odometry* odo, double res, int width, double* d_surface, int* n_used, int* itr_used,
                            double* poses_used);
+/* ---- Parameter grids in one batch: per-sequence parameters and shared input sweeps. The reference evaluates one recording under many
+ * parameter sets by running one offline_odometry process per point of a nested-loop grid (utils/worker:26-99, utils/start_workers:54-57);
+ * each process builds its OdometryKeyframeFuser::Parameters (odometrykeyframefuser.h:72-114) from its own arguments. Here the points of
+ * the grid are the sequences of one object: each sequence may run under its own parameter set, and several sequences may read the same
+ * sweep, with the results of running each parameter set on its own.
+ *
+ * cfear_odometry_set_sequence_params: rows = n_sequences cfear_params, row q for sequence q (n_rows must be the object's n_sequences);
+ * NULL: back to the context's parameters for all sequences. Per sequence: z_min, res, weight_intensity, loss, loss_limit, weight_opt,
+ * covar_scale, regularization, compensate, use_keyframe, min_keyframe_dist, min_keyframe_rot_deg, max_itr_association, min_itr,
+ * max_solver_iterations. Every other field (k_strongest, cost, submap_scan_size, filter_type, range_res, min_distance, downsample_factor,
+ * radar_ccw, assoc_radius, cfar_*; with filter_type CA-CFAR also z_min) sizes memory or selects a kernel and must equal the context's value
+ * in every row: otherwise CFEAR_ERR_INVALID with a message that names the row and the field, and nothing is changed. Only on an object
+ * that has processed no sweep since cfear_odometry_create / cfear_odometry_reset (CFEAR_ERR_INVALID otherwise); cfear_odometry_reset
+ * keeps the table. cfear_set_params on the context afterwards is checked against the table at the next step / replay (CFEAR_ERR_INVALID
+ * there if a row no longer agrees in an object-wide field). Every batched route honours the table: the step and replay entry points, the
+ * cost-sampling covariance (loss, weights, radius rule of the sampled GetCost) and cfear_odometry_surface (each sequence's loss).
+ * Per-sequence z_min: the k-strongest filter runs once per input sweep with the smallest z_min of the rows and each sequence drops the
+ * slots below its own - exact, because intensity is the filter's primary sort key (the k strongest above z are the members above z of
+ * the k strongest above any z' <= z). The peaks flag of a slot does depend on the kept set; no batched route reads it.
+ * Synchronises the context stream. */
+int cfear_odometry_set_sequence_params(cfear_ctx* ctx, cfear_odometry* odo, const cfear_params* rows, int n_rows);
+/* The parameter set sequence q runs with: its row, or the context's parameters without a table. */
+int cfear_odometry_sequence_params(cfear_ctx* ctx, cfear_odometry* odo, int sequence, cfear_params* out);
+/* source[q] in [0, n_sources): the input sweep sequence q reads (1 <= n_sources <= n_sequences). Afterwards cfear_odometry_step_device /
+ * _step_host take n_sources sweeps and the replay entry points n_sweeps x n_sources x A x R bytes instead of n_sequences per sweep: a
+ * shared sweep is stored, copied and filtered once. NULL: identity (one sweep per sequence). k-strongest objects only: a CA-CFAR object
+ * refuses a map, and cfear_odometry_step_cloud_device refuses to run while one is set (both CFEAR_ERR_UNSUPPORTED). A source out of
+ * range: CFEAR_ERR_INVALID, nothing changed. As the table: only before the first sweep since create / reset; reset keeps it.
+ * Synchronises the context stream. */
+int cfear_odometry_set_sequence_sources(cfear_ctx* ctx, cfear_odometry* odo, const int32_t* source, int n_sequences, int n_sources);
 /* Has any scan of this object been truncated - more oriented surface points than CFEAR_TUNE_MAX_CELLS, or a cloud with more points than the object
  * holds? Synchronises the context stream; returns CFEAR_OK or CFEAR_ERR_CAPACITY (with the message the reading calls give). For callers of the
  * asynchronous cfear_odometry_replay_device, which read their records on the device and never pass through poses / summary / replay_host.

@@ -1,0 +1,106 @@
+# Parameter grids in one batch (cfear_odometry_set_sequence_params / _set_sequence_sources): what the feature is worth. BASELINE configs[1]
+# (bench.PARAMS), CFEAR_GRID_B sequences (default 1536) over CFEAR_GRID_SOURCES generated recordings (default 64), after bench.py's 8-sweep pre-roll
+# and W warm-up steps; per leg three repeats of K timed steps, medians, the filter time from cfear_odometry_profile_read and the features /
+# registration split from cfear_odometry_profile_read_stages. One JSON line per leg:
+#   (a) no table                      - the behaviour without the feature, the reference point
+#   (b) identity table + identity map - the overhead of the lookups
+#   (c) a B-row grid (losses x limits x weights x res x z_min x weight_intensity), every sequence with its own copy of its sweep
+#   (d) the same grid on the shared sources: the filter runs on 64 sweeps per step instead of B, and 64 sweeps per step are resident
+# usage: python tools/gpu_param_grid.py > profiles/param_grid_steps.jsonl
+import json, os, sys, time
+import numpy as np
+import torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import bench
+
+
+def grid_rows(capi, replay, base, B):
+    rows = replay.param_grid(base, loss=[1, 2, 3, 5], loss_limit=[0.1, 0.5, 1.0, 2.0], weight_opt=[0, 2, 4, 5], res=[2.5, 3.0, 3.5, 5.0],
+                             z_min=[50.0, 60.0, 70.0], weight_intensity=[0, 1])  # 1536 points in the worker's loop order
+    return [rows[q % len(rows)] for q in range(B)]
+
+
+def leg(capi, name, ctx_params, stream, B, S, d_frames, d_pre, idx, rows, shared, W, K, reps):
+    """d_frames: [frames, S, A, R] resident sweeps of the S sources; shared: the object reads them through a source map, otherwise every
+    sequence gets its own copy ([frames, B, A, R], gathered here, resident for the leg)"""
+    ctx = capi.Context(ctx_params, bench.A, bench.R, device=0, stream=stream)
+    odo = ctx.odometry(B)
+    if rows is not None:
+        odo.set_sequence_params(rows)
+    frames = d_frames.shape[0]
+    if shared:
+        odo.set_sequence_sources(idx.cpu().numpy().astype(np.int32), S)
+        d_in, d_tmp = d_frames, None
+    else:
+        if rows is not None and name.startswith("b"):
+            odo.set_sequence_sources(np.arange(B, dtype=np.int32), B)
+        d_in = torch.empty((frames, B, bench.A, bench.R), dtype=torch.uint8, device=d_frames.device)
+        for t in range(frames):
+            torch.index_select(d_frames[t], 0, idx, out=d_in[t])
+        d_tmp = torch.empty((B, bench.A, bench.R), dtype=torch.uint8, device=d_frames.device)
+    torch.cuda.synchronize()
+    period = 2 * (frames - 1)
+    frame_of = lambda s: (s % period) if (s % period) < frames else period - (s % period)  # forwards, then backwards (bench.Resident.frame_of)
+    for t in range(bench.PRE_ROLL):
+        if shared:
+            src = d_pre[:, t].contiguous()
+        else:
+            torch.index_select(d_pre[:, t], 0, idx, out=d_tmp); src = d_tmp
+        torch.cuda.current_stream().synchronize()
+        odo.step_device(src.data_ptr())
+        ctx.synchronize()
+    step = 0
+    for _ in range(W):
+        odo.step_device(d_in[frame_of(step)].data_ptr()); step += 1
+    res = []
+    for r in range(reps):
+        ctx.synchronize(); torch.cuda.synchronize()
+        odo.profile(True)
+        t0 = time.perf_counter()
+        for _ in range(K):
+            odo.step_device(d_in[frame_of(step)].data_ptr()); step += 1
+        ctx.synchronize(); torch.cuda.synchronize()
+        el = time.perf_counter() - t0
+        t_f, n_f = odo.profile_read()
+        t_feat, t_reg, n = odo.profile_read_stages()
+        odo.profile(False)
+        res.append(dict(step_us=1e6 * el / K, scans_per_s=B * K / el, filter_us=1e6 * t_f / max(n_f, 1), features_us=1e6 * t_feat / max(n, 1),
+                        registration_us=1e6 * t_reg / max(n, 1)))
+    outer = [odo.summary(q)[0].outer_iterations for q in range(0, B, max(1, B // 128))]
+    out = {"leg": name, "sequences": B, "input_sweeps_per_step": S if shared else B, "resident_input_MB_per_step": (S if shared else B) * bench.A * bench.R / 1e6,
+           "steps_per_repeat": K, "repeats": reps, "outer_iterations_last_step_min_mean_max": [int(min(outer)), float(np.mean(outer)), int(max(outer))]}
+    for k in res[0]:
+        out[k] = float(np.median([x[k] for x in res]))
+        out[k + "_all"] = [round(x[k], 1) for x in res]
+    print(json.dumps(out), flush=True)
+    odo.release(); ctx.close()
+    del d_in, d_tmp
+    torch.cuda.empty_cache()
+
+
+def main():
+    torch.cuda.set_stream(torch.cuda.Stream())
+    from cfear_radarodometry_code_public_amd import capi, replay
+    dev = torch.device("cuda:0")
+    stream = torch.cuda.current_stream().cuda_stream
+    W, K, reps = 4, 12, 3
+    B = int(os.environ.get("CFEAR_GRID_B", "1536"))
+    S = int(os.environ.get("CFEAR_GRID_SOURCES", "64"))
+    st = bench.make_streams(S, bench.PRE_ROLL + W + K, 0)  # [S, PRE_ROLL + frames, A, R]
+    d_all = torch.from_numpy(np.ascontiguousarray(st)).to(dev)
+    d_pre = d_all[:, :bench.PRE_ROLL].clone()
+    d_frames = d_all[:, bench.PRE_ROLL:].transpose(0, 1).contiguous()  # [frames, S, A, R]
+    del d_all
+    idx = torch.from_numpy(np.arange(B) % S).to(dev)  # sequence q replays recording q % S
+    base = capi.default_params(range_res=bench.RANGE_RES, **bench.PARAMS)
+    rows = grid_rows(capi, replay, base, B)
+    ident = [base] * B
+    leg(capi, "a_no_table", base, stream, B, S, d_frames, d_pre, idx, None, False, W, K, reps)
+    leg(capi, "b_identity_table", base, stream, B, S, d_frames, d_pre, idx, ident, False, W, K, reps)
+    leg(capi, "a_no_table_again", base, stream, B, S, d_frames, d_pre, idx, None, False, W, K, reps)  # (a)'s own spread between objects
+    leg(capi, "c_grid_replicated_frames", base, stream, B, S, d_frames, d_pre, idx, rows, False, W, K, reps)
+    leg(capi, "d_grid_shared_sources", base, stream, B, S, d_frames, d_pre, idx, rows, True, W, K, reps)
+
+
+if __name__ == "__main__":
+    main()
