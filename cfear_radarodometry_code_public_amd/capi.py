@@ -73,7 +73,7 @@ EXPORTS = [
     "cfear_rotate_polar", "cfear_rotate_polar_device", "cfear_filter_polar", "cfear_filter_polar_device", "cfear_filter_cfar", "cfear_filter_cfar_device", "cfear_filter_cfar_batch_device", "cfear_cloud_upload", "cfear_cloud_size",
     "cfear_cloud_download", "cfear_clouds_download", "cfear_cloud_release", "cfear_compensate", "cfear_compensate_pair", "cfear_scan_create",
     "cfear_scan_from_cells", "cfear_scan_release", "cfear_scan_size", "cfear_scan_download_cells", "cfear_scan_closest",
-    "cfear_register", "cfear_register_soft", "cfear_get_cost", "cfear_cov_by_sampling", "cfear_odometry_create", "cfear_odometry_destroy", "cfear_odometry_reset",
+    "cfear_register", "cfear_register_soft", "cfear_register_time_continuous", "cfear_get_cost", "cfear_cov_by_sampling", "cfear_odometry_create", "cfear_odometry_destroy", "cfear_odometry_reset",
     "cfear_odometry_step_device", "cfear_odometry_step_cloud_device", "cfear_odometry_step_host", "cfear_odometry_poses",
     "cfear_odometry_replay_host", "cfear_odometry_replay_device", "cfear_odometry_replay_host_cov", "cfear_odometry_replay_device_cov",
     "cfear_odometry_set_cov_sampling", "cfear_odometry_cov_samples", "cfear_host_alloc", "cfear_host_free",
@@ -135,6 +135,7 @@ def lib():
         "cfear_scan_closest": (C.c_int, [vp, vp, f64p, C.c_int, C.c_double, i32p]),
         "cfear_register": (C.c_int, [vp, C.POINTER(vp), C.c_int, f64p, f64p, C.POINTER(RegSummary)]),
         "cfear_register_soft": (C.c_int, [vp, C.POINTER(vp), C.c_int, f64p, f64p, f64p, C.POINTER(RegSummary)]),
+        "cfear_register_time_continuous": (C.c_int, [vp, C.POINTER(vp), C.c_int, f64p, f64p, C.c_int, f64p, f64p, C.POINTER(RegSummary)]),
         "cfear_get_cost": (C.c_int, [vp, C.POINTER(vp), C.c_int, f64p, C.c_int, f64p, f64p, C.c_int, C.POINTER(C.c_int)]),
         "cfear_cov_by_sampling": (C.c_int, [vp, C.POINTER(vp), C.c_int, f64p, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double,
                                             C.c_double, C.c_int, f64p, C.POINTER(C.c_int), f64p]),
@@ -376,6 +377,21 @@ class Context:
         cov = np.zeros(36)
         S = RegSummary()
         self._check(self._L.cfear_register_soft(self._h, arr, n, P.ctypes.data, pc.ctypes.data, cov.ctypes.data, C.byref(S)), "cfear_register_soft")
+        return bool(S.success), P, cov.reshape(6, 6), S
+
+    def register_time_continuous(self, scans, poses, velocity, ccw=False, prior_cov6=None):
+        """RegisterTimeContinuous(scans, Tsrc, reg_cov, Tvel, soft_constraints, ccw) (n_scan_normal.cpp:67-80): the last scan keeps its
+        motion distortion; velocity = (vx, vy, vtheta) over one sweep = Affine3dToVectorXYeZ(Tvel); prior_cov6: reg_cov.back() with
+        soft_constraints, None: without. Returns what register returns."""
+        n = len(scans)
+        arr = (C.c_void_p * n)(*[s._h for s in scans])
+        P = np.ascontiguousarray(poses, dtype=np.float64).reshape(n, 3).copy()
+        v = np.ascontiguousarray(velocity, dtype=np.float64).reshape(3).copy()
+        pc = None if prior_cov6 is None else np.ascontiguousarray(prior_cov6, dtype=np.float64).reshape(36).copy()
+        cov = np.zeros(36)
+        S = RegSummary()
+        self._check(self._L.cfear_register_time_continuous(self._h, arr, n, P.ctypes.data, v.ctypes.data, int(bool(ccw)), None if pc is None else pc.ctypes.data,
+                                                           cov.ctypes.data, C.byref(S)), "cfear_register_time_continuous")
         return bool(S.success), P, cov.reshape(6, 6), S
 
     def get_cost(self, scans, poses, itr=2):

@@ -11,6 +11,7 @@
 //                          association, robust normal equations, LM, outer loop, keyframe logic
 // Per-call entry points (clouds, scans, Register, GetCost, cost-sampling covariance) use the same device code.
 #include <math.h>
+#include <cmath>
 #include <stdlib.h>
 
 #include <algorithm>
@@ -109,6 +110,30 @@ __global__ __launch_bounds__(BLOCK_R, 3) void register_kernel(ScanDev* const* sc
   const RegScratch W = make_rscratch(B, lds);
   register_block(sp, n, poses, cov6, P, W, reinterpret_cast<double*>(lds + RegLds::par),
                  reinterpret_cast<RegShared*>(lds + RegLds::regsh), out, nullptr, prior_cov6);
+}
+
+// ---- RegisterTimeContinuous (registration_dev.h: time-continuous registration) ----------------------------------------
+// the prologue, once per call: one thread per source cell writes the compensated source view; thread 0 its header - the source's own
+// with rsrc pointing at the view (same cap_cells, so the same strides)
+__global__ __launch_bounds__(BLOCK_R) void tc_prologue_kernel(const ScanDev* src, ScanDev* hdr, double* view, int view_cells, double vx, double vy,
+                                                              double vth, int ccw) {
+  const int j = blockIdx.x * BLOCK_R + threadIdx.x;
+  const int cc = src->cap_cells;
+  const bool fits = cc <= view_cells;  // (the host sizes the view for the scan's capacity; a view that cannot hold it is a scan without cells)
+  if (j == 0) { *hdr = *src; hdr->rsrc = view; if (!fits) { hdr->n_cells = 0; hdr->status = CFEAR_ERR_EMPTY; } }
+  if (!fits || j >= src->n_cells || j >= cc) return;
+  tc_compensate_cell(src->rsrc, (size_t)cc, view, j, vx, vy, vth, ccw);
+}
+// register_kernel with the header of the compensated view in the place of the last scan
+__global__ __launch_bounds__(BLOCK_R, 3) void register_tc_kernel(ScanDev* const* scans, int n, double* poses, double* cov6, RegParams P,
+                                                              BlockScratch B, cfear_reg_summary* out, const double* prior_cov6, ScanDev* src_view) {
+  __shared__ __attribute__((aligned(16))) unsigned char lds[RegLds::total];
+  ScanDev** sp = reinterpret_cast<ScanDev**>(lds + RegLds::scanptr);
+  for (int i = threadIdx.x; i < n; i += blockDim.x) sp[i] = (i == n - 1) ? src_view : scans[i];
+  __syncthreads();
+  const RegScratch W = make_rscratch(B, lds);
+  register_block<-1, true>(sp, n, poses, cov6, P, W, reinterpret_cast<double*>(lds + RegLds::par),
+                           reinterpret_cast<RegShared*>(lds + RegLds::regsh), out, nullptr, prior_cov6);
 }
 
 __global__ __launch_bounds__(BLOCK_R, 3) void get_cost_kernel(ScanDev* const* scans, int n, const double* poses, RegParams P, BlockScratch B,
@@ -742,11 +767,15 @@ struct CallTail {
   alignas(16) double prior[36];       // cfear_register_soft
 };
 static_assert(offsetof(CallTail, sum) == sizeof(double) * (3 * MAX_SCANS + 36) + sizeof(void*) * MAX_SCANS, "the arrays that travel as one copy lie back to back");
-// per-context scratch of the per-call API for scans of up to cap_points points and up to MAX_SCANS - 1 keyframes: the working arrays (B), then a CallTail
-static int ensure_ctx_scratch(cfear_ctx* ctx, int cap_points, BlockScratch* B, CallTail** tail = nullptr) {
+// cfear_register_time_continuous: the compensated source view (registration_dev.h) of a scan of up to view_cells cells and its header
+struct TcView { ScanDev* hdr; double* view; int view_cells; };
+// per-context scratch of the per-call API for scans of up to cap_points points and up to MAX_SCANS - 1 keyframes: the working arrays (B), then a CallTail,
+// then a TcView
+static int ensure_ctx_scratch(cfear_ctx* ctx, int cap_points, BlockScratch* B, CallTail** tail = nullptr, TcView* tc = nullptr) {
   const int pair_cap = (MAX_SCANS - 1) * cap_points;
   const ScratchLayout L = scratch_layout(cap_points, pair_cap);
-  const size_t need = L.total + sizeof(CallTail) + 4096;  // (and some headroom)
+  const size_t tc_hdr = align_up(L.total + sizeof(CallTail), 256), tc_view = align_up(tc_hdr + sizeof(ScanDev), 256);
+  const size_t need = tc_view + sizeof(double) * 8 * (size_t)cap_points + 4096;  // (and some headroom)
   if (need > ctx->scratch_bytes) {
     if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
     ctx->d_scratch = nullptr; ctx->scratch_bytes = 0;
@@ -757,6 +786,7 @@ static int ensure_ctx_scratch(cfear_ctx* ctx, int cap_points, BlockScratch* B, C
   unsigned char* base = static_cast<unsigned char*>(ctx->d_scratch);
   *B = scratch_header(base, cap_points, pair_cap);
   if (tail) *tail = reinterpret_cast<CallTail*>(base + L.total);
+  if (tc) { tc->hdr = reinterpret_cast<ScanDev*>(base + tc_hdr); tc->view = reinterpret_cast<double*>(base + tc_view); tc->view_cells = cap_points; }
   return CFEAR_OK;
 }
 // the scans of a per-call problem: all there and built under the current tie rule; their device blocks and the largest point capacity among them
@@ -774,11 +804,11 @@ static int problem_scans(cfear_ctx* ctx, cfear_scan* const* scans, int n, const 
   return check_tie_rule_scans(ctx, scans, n, what);
 }
 // ... with the context scratch sized for them: the kernels' working memory, the device tail (d) and the scan pointer table to upload into it
-struct CallProblem { BlockScratch B; CallTail* d; ScanDev* ptrs[MAX_SCANS]; };
+struct CallProblem { BlockScratch B; CallTail* d; ScanDev* ptrs[MAX_SCANS]; TcView tc; };
 static int call_problem(cfear_ctx* ctx, cfear_scan* const* scans, int n, const char* what, CallProblem* pb) {
   int capmax = 0;
   CFEAR_TRY(problem_scans(ctx, scans, n, what, pb->ptrs, &capmax));
-  return ensure_ctx_scratch(ctx, capmax, &pb->B, &pb->d);
+  return ensure_ctx_scratch(ctx, capmax, &pb->B, &pb->d, &pb->tc);
 }
 
 extern "C" {
@@ -1122,8 +1152,9 @@ int cfear_scan_closest(cfear_ctx* ctx, const cfear_scan* s, const double* qxy, i
 }
 
 // ---- registration ------------------------------------------------------------------------------
+// vel: null = Register; the sweep velocity (vx, vy, vtheta) = RegisterTimeContinuous with that velocity and rotation direction
 static int register_impl(cfear_ctx* ctx, cfear_scan* const* scans, int n, double* poses_xyt, const double* prior_cov6, double* cov6_last,
-                         cfear_reg_summary* summary) {
+                         cfear_reg_summary* summary, const double* vel = nullptr, int ccw = 0) {
   if (!ctx || !scans || !poses_xyt || n < 2) return cfear_fail(ctx, CFEAR_ERR_INVALID, "register: need >= 2 scans and poses");
   if (n > MAX_SCANS) return cfear_fail(ctx, CFEAR_ERR_UNSUPPORTED, "register: more than 64 scans");
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
@@ -1147,7 +1178,17 @@ static int register_impl(cfear_ctx* ctx, cfear_scan* const* scans, int n, double
     memcpy(h->prior, prior_cov6, sizeof(double) * 36);
     CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(d_prior, h->prior, sizeof(double) * 36, hipMemcpyHostToDevice, ctx->stream));
   }
-  hipLaunchKernelGGL(register_kernel, dim3(1), dim3(BLOCK_R), 0, ctx->stream, pb.d->ptrs, n, pb.d->poses, pb.d->cov, reg_params(ctx), pb.B, &pb.d->sum, d_prior);
+  if (vel) {
+    // (the cells of a scan are known on the host since its creation; a scan that does not know them yet is covered by its capacity)
+    const int cells = scans[n - 1]->n_cells >= 0 ? scans[n - 1]->n_cells : scans[n - 1]->cap_points;
+    hipLaunchKernelGGL(tc_prologue_kernel, dim3(std::max(1, (cells + BLOCK_R - 1) / BLOCK_R)), dim3(BLOCK_R), 0, ctx->stream, pb.ptrs[n - 1], pb.tc.hdr,
+                       pb.tc.view, pb.tc.view_cells, vel[0], vel[1], vel[2], ccw ? 1 : 0);
+    CFEAR_HIP_CHECK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(register_tc_kernel, dim3(1), dim3(BLOCK_R), 0, ctx->stream, pb.d->ptrs, n, pb.d->poses, pb.d->cov, reg_params(ctx), pb.B, &pb.d->sum,
+                       d_prior, pb.tc.hdr);
+  } else {
+    hipLaunchKernelGGL(register_kernel, dim3(1), dim3(BLOCK_R), 0, ctx->stream, pb.d->ptrs, n, pb.d->poses, pb.d->cov, reg_params(ctx), pb.B, &pb.d->sum, d_prior);
+  }
   CFEAR_HIP_CHECK(ctx, hipGetLastError());
   CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(h, pb.d, in_bytes + sizeof(cfear_reg_summary), hipMemcpyDeviceToHost, ctx->stream));
   CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
@@ -1168,6 +1209,14 @@ int cfear_register_soft(cfear_ctx* ctx, cfear_scan* const* scans, int n, double*
                         cfear_reg_summary* summary) {
   if (!prior_cov6) return cfear_fail(ctx, CFEAR_ERR_INVALID, "register_soft: null prior covariance");
   return register_impl(ctx, scans, n, poses_xyt, prior_cov6, cov6_last, summary);
+}
+
+int cfear_register_time_continuous(cfear_ctx* ctx, cfear_scan* const* scans, int n, double* poses_xyt, const double velocity_xyt[3], int ccw,
+                                   const double* prior_cov6, double* cov6_last, cfear_reg_summary* summary) {
+  if (!ctx || !velocity_xyt) return cfear_fail(ctx, CFEAR_ERR_INVALID, "register_time_continuous: null context or velocity");
+  if (!std::isfinite(velocity_xyt[0]) || !std::isfinite(velocity_xyt[1]) || !std::isfinite(velocity_xyt[2]))
+    return cfear_fail(ctx, CFEAR_ERR_INVALID, "register_time_continuous: the velocity is not finite");
+  return register_impl(ctx, scans, n, poses_xyt, prior_cov6, cov6_last, summary, velocity_xyt, ccw);
 }
 
 int cfear_get_cost(cfear_ctx* ctx, cfear_scan* const* scans, int n, const double* poses_xyt, int itr, double* score, double* residuals,

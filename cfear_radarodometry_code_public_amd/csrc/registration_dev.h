@@ -646,6 +646,45 @@ __device__ __forceinline__ RCell rcell_tar(const ScanDev* S, int ti) {  // one 6
   return c;
 }
 
+// ---- time-continuous registration (RegisterTimeContinuous, n_scan_normal.cpp:67-80, :231-237) ----------------------------
+// The compensation transform of a source cell, Tcomp_j = vectorToAffine2d(ts_j * vel), depends on the cell and the sweep velocity
+// only, not on the pose being solved: a prologue (pipeline.hip tc_prologue_kernel) applies it once per call and leaves a
+// COMPENSATED SOURCE VIEW in the rsrc layout with two more arrays - [8][cap_cells]: u'_j = Tcomp_j u_j (x, y), n'_j =
+// Tcomp_j.linear() n_j (x, y), nsamples, scale, and the uncorrected mean u_j (x, y) - behind a copy of the source's ScanDev header
+// whose rsrc points at it. The TC instantiations below get that header as their last scan, so every association path reads
+// u'_j and n'_j where it read u_j and n_j; what differs in the code is the source mean a residual block keeps:
+//   P2P        u'_j: P2PEfficientContinuousCost (n_scan_normal.h:363-404) is P2PEfficientCost of the corrected mean, the velocity
+//              being a constant of the problem;
+//   P2L, P2D   u_j, the UNCORRECTED mean, although the match was found with the corrected one (:279-300 pass src_mean) - quirk q19.
+// The reference composes Ttar^-1 Tsrc Tcomp_j and applies the product; here Tcomp_j is applied first and Ttar^-1 Tsrc second,
+// which differs by a few ulp of the query before its cast to float (and of the rotated normal): accepted.
+struct TcMean { double x, y; };
+__device__ __forceinline__ TcMean tc_uncorrected_mean(const double* view, size_t cc, int j) {
+  TcMean u; u.x = view[6 * cc + j]; u.y = view[7 * cc + j];
+  return u;
+}
+// GetRelTimeStamp (utils.h:28-32) of a cell mean in the scan's own frame
+__device__ __forceinline__ double tc_rel_stamp(double x, double y, int ccw) {
+  const double two_pi = 2 * 3.14159265358979323846;
+  const double a = atan2(y, x);
+  const double d = ((a > 0.00001) ? a : (two_pi + a)) / two_pi;
+  return ccw ? -(d - 0.5) : (d - 0.5);
+}
+// one cell of the compensated source view (the prologue: one thread per source cell)
+__device__ __forceinline__ void tc_compensate_cell(const double* rsrc, size_t cc, double* view, int j, double vx, double vy, double vth, int ccw) {
+  const double ux = rsrc[j], uy = rsrc[cc + j], nx = rsrc[2 * cc + j], ny = rsrc[3 * cc + j];
+  const double ts = tc_rel_stamp(ux, uy, ccw);
+  const Aff2 T = aff_from_xyt(ts * vx, ts * vy, ts * vth);  // vectorToAffine2d (registration.cpp:146-150)
+  view[j] = (T.l0 * ux + T.l1 * uy) + T.t0;
+  view[cc + j] = (T.l2 * ux + T.l3 * uy) + T.t1;
+  view[2 * cc + j] = T.l0 * nx + T.l1 * ny;
+  view[3 * cc + j] = T.l2 * nx + T.l3 * ny;
+  view[4 * cc + j] = rsrc[4 * cc + j];
+  view[5 * cc + j] = rsrc[5 * cc + j];
+  view[6 * cc + j] = ux;
+  view[7 * cc + j] = uy;
+}
+
 // one match record (AddScanPairCost :266-320) written at position o of the destination SoA
 __device__ __forceinline__ void write_match(const MatchPtrs& m, int o, const RegParams& P, const double* T, const double* Tt,
                                             const RCell& cs, const RCell& ct, const double* ct_cov /* xx, xy, yy (P2D) */) {
@@ -722,11 +761,13 @@ __device__ __noinline__ int associate_pair_rule(ScanDev* const* scans, const Sca
   }
   return ti;
 }
+template <bool TC = false>
 __device__ __noinline__ void emit_match(ScanDev* const* scans, const ScanDev* src, const LRegShared* sh, int nsrc, int p, int ti, int o, bool use_lds) {
   const RegParams& P = CFEAR_GENERIC(const RegParams, sh->rp);
   const RegScratch& W = CFEAR_GENERIC(const RegScratch, sh->rw);
   const int i = p / nsrc, j = p - i * nsrc;
-  const RCell cs = rcell_src(src, j);
+  RCell cs = rcell_src(src, j);
+  if (TC && P.cost != CFEAR_COST_P2P) { const TcMean u = tc_uncorrected_mean(src->rsrc, (size_t)src->cap_cells, j); cs.mx = u.x; cs.my = u.y; }  // q19
   RCell ct;
   {
     const double2* r = reinterpret_cast<const double2*>(sh->kf[i].rtar + 8 * (size_t)ti);  // the LDS view: no pointer chase
@@ -908,7 +949,7 @@ __device__ __forceinline__ Assoc4 associate_cell(const ScanDev* src, const LRegS
 // residual blocks of one source cell (up to four keyframes); pos = four 16-bit positions in the match arrays.
 // The source cell is read once; matches that fit the LDS array are stored through an LDS-typed pointer (ds_write, not
 // flat stores through the address unit). Same arithmetic as write_match.
-template <int KCOST = -1>
+template <int KCOST = -1, bool TC = false>
 __device__ __forceinline__ void emit_cell(ScanDev* const* scans, const ScanDev* src, const LRegShared* sh,
                                           int nsrc, int k0, int nk, int j, Assoc4 a, unsigned long long pos, int mode /* RegShared::lds_match */) {
   // block-uniform values in scalar registers: read from LDS they sit in vector registers, and every branch on them is compiled as
@@ -923,6 +964,7 @@ __device__ __forceinline__ void emit_cell(ScanDev* const* scans, const ScanDev* 
     const size_t cc = (size_t)sh->scc;
     g_cf64* r = (g_cf64*)sh->srs + j;
     cs.mx = r[0]; cs.my = r[cc]; cs.nx = r[2 * cc]; cs.ny = r[3 * cc]; cs.ns = r[4 * cc]; cs.scale = r[5 * cc];
+    if (TC && cost != CFEAR_COST_P2P) { cs.mx = r[6 * cc]; cs.my = r[7 * cc]; }  // q19: P2L / P2D keep the uncorrected mean (cs.mx / my only feed the stores below)
   }
   (void)src;
   typedef __attribute__((address_space(3))) double lds_double;
@@ -1017,7 +1059,7 @@ __device__ __forceinline__ AssocBlock assoc_block(const ScanDev* src, const LReg
 }
 // residual blocks of block b of the source cells for the keyframes of group g; before = positions the group's keyframes start at
 // plus their matches in earlier blocks. Returns the matches of the block per keyframe (0 when nothing was parked: nothing follows).
-template <int KCOST = -1>
+template <int KCOST = -1, bool TC = false>
 __device__ __noinline__ unsigned long long emit_block(ScanDev* const* scans, const ScanDev* src, const LRegShared* sh, int k0, int nk, int nsrc, int b, int g,
                                                       bool parked, Assoc4 a, unsigned long long e, unsigned long long before, int mode) {
   const int j = b * CFEAR_REG_BLOCK + threadIdx.x;
@@ -1027,20 +1069,20 @@ __device__ __noinline__ unsigned long long emit_block(ScanDev* const* scans, con
     if (j < nsrc) { const int4 v = reinterpret_cast<const int4*>(sh->rw.assoc)[(size_t)g * nsrc + j]; a.t0 = v.x; a.t1 = v.y; a.t2 = v.z; a.t3 = v.w; }
     e = block_exclusive_scan64<CFEAR_REG_BLOCK>(assoc_counts(a), reinterpret_cast<unsigned long long*>(sh->rw.red), &tb);
   }
-  if (a.t0 >= 0 || a.t1 >= 0 || a.t2 >= 0 || a.t3 >= 0) emit_cell<KCOST>(scans, src, sh, nsrc, k0, nk, j, a, before + e, mode);
+  if (a.t0 >= 0 || a.t1 >= 0 || a.t2 >= 0 || a.t3 >= 0) emit_cell<KCOST, TC>(scans, src, sh, nsrc, k0, nk, j, a, before + e, mode);
   return tb;
 }
 
 // the residual blocks of one (group of four keyframes, source cell) item of the grouped path; out of line like emit_block (inlined, the
 // emission's registers are the kernel's)
-template <int KCOST = -1>
+template <int KCOST = -1, bool TC = false>
 __device__ __noinline__ void emit_item(ScanDev* const* scans, const ScanDev* src, const LRegShared* sh, int nsrc, int k0, int nk, int j, int4 v,
                                        unsigned long long pos, int mode) {
   const Assoc4 a = {v.x, v.y, v.z, v.w};
-  emit_cell<KCOST>(scans, src, sh, nsrc, k0, nk, j, a, pos, mode);
+  emit_cell<KCOST, TC>(scans, src, sh, nsrc, k0, nk, j, a, pos, mode);
 }
 
-template <int KCOST = -1>
+template <int KCOST = -1, bool TC = false>
 __device__ __forceinline__ int build_problem_block(ScanDev* const* scans, int n, LRegShared* sh, int itr) {
   const ScanDev* src = scans[n - 1];
   const int nsrc = sh->kf[n - 1].n_cells;  // (the view in LDS: src->n_cells is a round trip to memory in front of every association)
@@ -1062,7 +1104,7 @@ __device__ __forceinline__ int build_problem_block(ScanDev* const* scans, int n,
     const unsigned long long t0 = T & 0xFFFF, t1 = (T >> 16) & 0xFFFF, t2 = (T >> 32) & 0xFFFF, t3 = (T >> 48) & 0xFFFF;
     M = (int)(t0 + t1 + t2 + t3);
     mode = M <= lcap ? 1 : 2;
-    (void)emit_block<KCOST>(scans, src, sh, 0, nk, nsrc, 0, 0, false, R.a, R.e, (t0 << 16) | ((t0 + t1) << 32) | ((t0 + t1 + t2) << 48), mode);
+    (void)emit_block<KCOST, TC>(scans, src, sh, 0, nk, nsrc, 0, 0, false, R.a, R.e, (t0 << 16) | ((t0 + t1) << 32) | ((t0 + t1 + t2) << 48), mode);
     done = true; assoc_path = 1;
   } else if (tie_rule == 0 && can_park && (long long)nk * nsrc <= 65535 && nk <= 64) {
     // several blocks of cells and / or several groups of four keyframes (a submap of 5 .. 63 keyframes: the reference's s10 and s50
@@ -1119,7 +1161,7 @@ __device__ __forceinline__ int build_problem_block(ScanDev* const* scans, int n,
     for (int it = tid; it < nitems; it += nt) {
       const int g = it / nsrc, j = it - g * nsrc;
       const int4 v = park[it];
-      if (v.x >= 0 || v.y >= 0 || v.z >= 0 || v.w >= 0) emit_item<KCOST>(scans, src, sh, nsrc, 4 * g, min(4, nk - 4 * g), j, v, gt[16 + g] + ppos[it], mode);
+      if (v.x >= 0 || v.y >= 0 || v.z >= 0 || v.w >= 0) emit_item<KCOST, TC>(scans, src, sh, nsrc, 4 * g, min(4, nk - 4 * g), j, v, gt[16 + g] + ppos[it], mode);
     }
     done = true; assoc_path = 2;
   }
@@ -1144,7 +1186,7 @@ __device__ __forceinline__ int build_problem_block(ScanDev* const* scans, int n,
     mode = M <= lcap ? 1 : 2;
     for (int p = p0; p < p1; p++) {
       const int ti = sh->rw.assoc[p];
-      if (ti >= 0) { emit_match(scans, src, sh, nsrc, p, ti, o, mode == 1 || o < lcap); o++; }
+      if (ti >= 0) { emit_match<TC>(scans, src, sh, nsrc, p, ti, o, mode == 1 || o < lcap); o++; }
     }
   }
   if (tid == 0) { sh->lds_match = mode; sh->assoc_path = assoc_path; }
@@ -1515,7 +1557,8 @@ __device__ __forceinline__ void ctl_step(LRegShared* sh, long long* acc = nullpt
 // n_scan_normal_reg::Register. poses: n x 3 in global memory (in/out); cov6: 36 doubles or null;
 // out: summary in global memory. par_lds: >= 3*n doubles of LDS; sh: RegShared in LDS.
 // Wave 0 is the controller; every wave executes the published commands (two barriers per command).
-template <int KCOST = -1>
+// TC: RegisterTimeContinuous - scans[n - 1] is the header of the compensated source view (see tc_compensate_cell)
+template <int KCOST = -1, bool TC = false>
 __device__ inline int register_block(ScanDev* const* scans, int n, double* poses, double* cov6, const RegParams& P_in,
                                      const RegScratch& W_in, double* par_lds, RegShared* sh, cfear_reg_summary* out,
                                      PhaseTimer* pt = nullptr, const double* prior_cov6 = nullptr, SeqRow row = nullptr) {
@@ -1586,7 +1629,7 @@ __device__ inline int register_block(ScanDev* const* scans, int n, double* poses
     if (acc2) tb = (long long)wall_clock64();
     if (cmd == REG_CMD_BUILD) {
       if (pt) pt->mark();
-      const int M = build_problem_block<KCOST>(scans, n, ls, ls->itr);
+      const int M = build_problem_block<KCOST, TC>(scans, n, ls, ls->itr);
       if (tid == 0) ls->M = M;
       // the first evaluation of the solve that follows, at the pose the problem was built for: straight away instead of as a
       // command of its own (a barrier pair and a turn of the controller less per outer iteration); block-uniform condition,

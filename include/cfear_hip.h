@@ -261,6 +261,19 @@ int cfear_register(cfear_ctx* ctx, cfear_scan* const* scans, int n, double* pose
 int cfear_register_soft(cfear_ctx* ctx, cfear_scan* const* scans, int n, double* poses_xyt, const double* prior_cov6,
                         double* cov6_last, cfear_reg_summary* summary);
 
+/* bool RegisterTimeContinuous(std::vector<MapNormalPtr>& scans, std::vector<Eigen::Affine3d>& Tsrc, std::vector<Matrix6d>& reg_cov,
+ *                             const Eigen::Affine3d& Tvel, bool soft_constraints=false, bool ccw=false)
+ * (n_scan_normal.h:39, n_scan_normal.cpp:67-80): Register of a last scan whose motion distortion has NOT been removed.
+ * velocity_xyt = Affine3dToVectorXYeZ(Tvel), the motion over one sweep. Source cell j of the last scan gets the stamp
+ * ts_j = GetRelTimeStamp(mean_j, ccw) in (-0.5, 0.5] (utils.h:28-32) and the transform Tcomp_j = vectorToAffine2d(ts_j * velocity);
+ * the association - nearest-neighbour query, 30 degree gate, direction similarity and the weights built on it - uses Tcomp_j mean_j
+ * and Tcomp_j.linear() normal_j, the P2P residual the corrected mean Tcomp_j mean_j (P2PEfficientContinuousCost), the P2L and
+ * P2D residuals the UNCORRECTED mean_j as the reference does (n_scan_normal.cpp:279-300). Outer loop, solver,
+ * termination, covariance and summary as cfear_register. prior_cov6: NULL, or the prior of cfear_register_soft. A velocity of
+ * zero is cfear_register / cfear_register_soft bit for bit. Returns CFEAR_ERR_INVALID for a null or non-finite velocity. */
+int cfear_register_time_continuous(cfear_ctx* ctx, cfear_scan* const* scans, int n, double* poses_xyt, const double velocity_xyt[3], int ccw,
+                                   const double* prior_cov6 /* NULL: no soft constraint */, double* cov6_last, cfear_reg_summary* summary);
+
 /* bool GetCost(std::vector<MapNormalPtr>& scans, std::vector<Eigen::Affine3d>& Tsrc, double& score,
  *              std::vector<double>& residuals) (n_scan_normal.cpp:188-213; called by the cost-sampling covariance,
  * odometrykeyframefuser.cpp:305): associations and residual blocks at the given poses, no solve. itr = the object's

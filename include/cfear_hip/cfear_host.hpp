@@ -593,6 +593,18 @@ class n_scan_normal_reg {
   void SetParameters(unsigned int max_itr_association, unsigned int max_itr_solver) { max_itr_association_ = (int)max_itr_association; max_itr_solver_ = (int)max_itr_solver; }
   // bool Register(scans, Tsrc, reg_cov, soft_constraints = false) (n_scan_normal.cpp:82-187); only Tsrc.back() is free.
   bool Register(std::vector<MapNormalPtr>& scans, std::vector<Affine3d>& Tsrc, std::vector<Matrix6d>& reg_cov, bool soft_constraints = false) {
+    return register_with(scans, Tsrc, reg_cov, soft_constraints, nullptr, false);
+  }
+  // bool RegisterTimeContinuous(scans, Tsrc, reg_cov, Tvel, soft_constraints = false, ccw = false) (n_scan_normal.h:39, n_scan_normal.cpp:67-80):
+  // Register of a last scan whose motion distortion has NOT been removed - every source cell is moved by the share of the sweep
+  // velocity Affine3dToVectorXYeZ(Tvel) that belongs to its azimuth, in the association and in the P2P residual (cfear_register_time_continuous)
+  bool RegisterTimeContinuous(std::vector<MapNormalPtr>& scans, std::vector<Affine3d>& Tsrc, std::vector<Matrix6d>& reg_cov, const Affine3d& Tvel,
+                              bool soft_constraints = false, bool ccw = false) {
+    const double vel[3] = {cfear_tx(Tvel), cfear_ty(Tvel), cfear_yaw(Tvel)};  // :71
+    return register_with(scans, Tsrc, reg_cov, soft_constraints, vel, ccw);
+  }
+ private:
+  bool register_with(std::vector<MapNormalPtr>& scans, std::vector<Affine3d>& Tsrc, std::vector<Matrix6d>& reg_cov, bool soft_constraints, const double* vel, bool ccw) {
     const size_t n = scans.size();
     if (Tsrc.size() != n || reg_cov.size() != n || n < 2) throw std::runtime_error("Register: scans/Tsrc/reg_cov size mismatch");  // assert at n_scan_normal.cpp:84
     const DevicePtr dev = device(scans);
@@ -600,9 +612,12 @@ class n_scan_normal_reg {
     std::vector<cfear_scan*> h(n); std::vector<double> poses(3 * n);
     for (size_t i = 0; i < n; i++) { h[i] = scans[i]->handle(); poses[3 * i] = cfear_tx(Tsrc[i]); poses[3 * i + 1] = cfear_ty(Tsrc[i]); poses[3 * i + 2] = cfear_yaw(Tsrc[i]); }
     double cov[36] = {0};  // (in/out at the C ABI: left as passed when no usable solution comes back)
-    if (soft_constraints) {  // :373-377: prior from reg_cov.back() as passed in
-      double prior[36];
-      for (int a = 0; a < 6; a++) for (int b = 0; b < 6; b++) prior[6 * a + b] = reg_cov.back()(a, b);
+    double prior[36];
+    if (soft_constraints) for (int a = 0; a < 6; a++) for (int b = 0; b < 6; b++) prior[6 * a + b] = reg_cov.back()(a, b);  // :373-377: prior from reg_cov.back() as passed in
+    if (vel) {
+      dev->check(cfear_register_time_continuous(dev->ctx(), h.data(), (int)n, poses.data(), vel, ccw ? 1 : 0, soft_constraints ? prior : nullptr, cov, &summary_),
+                 "cfear_register_time_continuous");
+    } else if (soft_constraints) {
       dev->check(cfear_register_soft(dev->ctx(), h.data(), (int)n, poses.data(), prior, cov, &summary_), "cfear_register_soft");
     } else {
       dev->check(cfear_register(dev->ctx(), h.data(), (int)n, poses.data(), cov, &summary_), "cfear_register");
@@ -618,6 +633,7 @@ class n_scan_normal_reg {
     CFEAR_TIMING.Document("itrs", (double)itr_);  // n_scan_normal.cpp:161
     return summary_.success != 0;
   }
+ public:
   // bool GetCost(scans, Tsrc, score, residuals) (n_scan_normal.cpp:188-213): cost and robustified residuals at the given poses
   bool GetCost(std::vector<MapNormalPtr>& scans, std::vector<Affine3d>& Tsrc, double& score, std::vector<double>& residuals) {
     const size_t n = scans.size();

@@ -6,6 +6,6 @@
 #pragma once
 #include "cfear_radarodometry/cfear_types_ros.h"
 #include "cfear_hip/cfear_host.hpp"  // (this repository's include/ directory is on the include path: installed as include/cfear_hip/)
-// n_scan_normal.h:27-85 class n_scan_normal_reg: both constructors (:33,:35), Register (:37), GetCost (:41), getScore (:47,:51),
-// GetSurface (:43; the Eigen::MatrixXd of cfear_types_ros.h), GetCovarianceScaler (:49), SetD2dPar (:53), SetParameters (:55), public
-// summary_ / itr_ (registration.h:107-110). RegisterTimeContinuous (off by default) is not provided.
+// n_scan_normal.h:27-85 class n_scan_normal_reg: both constructors (:33,:35), Register (:37), RegisterTimeContinuous (:39; Tvel an
+// Eigen::Affine3d), GetCost (:41), getScore (:47,:51), GetSurface (:43; the Eigen::MatrixXd of cfear_types_ros.h), GetCovarianceScaler
+// (:49), SetD2dPar (:53), SetParameters (:55), public summary_ / itr_ (registration.h:107-110): every public method of the class.

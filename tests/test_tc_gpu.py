@@ -1,0 +1,304 @@
+"""Time-continuous registration on the device (cfear_register_time_continuous = n_scan_normal_reg::RegisterTimeContinuous,
+n_scan_normal.cpp:67-80) against the numpy restatement tc_ref: every association path (asserted through summary.assoc_path),
+the three costs, the soft prior, both rotation directions; a zero velocity is cfear_register bit for bit; a P2P problem is the plain
+registration of hand-compensated cells; quirk q19 (P2L / P2D residuals keep the uncorrected mean); the failure modes; the C++
+mirror through host/tc_check. Tolerances: tests/test_register_fuzz_gpu.py::compare.
+
+The inputs were checked not to sit on a decision boundary (tc_ref.on_decision_boundary: the restatement keeps its iteration counts
+when the velocity moves by 1e-12); a comparison that fails says whether its input does."""
+import ctypes as C
+import json
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import tc_ref
+from cfear_radarodometry_code_public_amd import capi, synth
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HOST = os.path.join(ROOT, "cfear_radarodometry_code_public_amd", "host")
+A, R, RR = 400, 3360, np.float32(0.0595238)
+BASE = dict(range_res=RR, k_strongest=12, z_min=60.0, res=3.0, weight_intensity=1, weight_opt=4, cost=1, loss=1, loss_limit=0.1,
+            regularization=0.1, covar_scale=1.0)
+PRIOR = np.diag([0.05 ** 2, 0.04 ** 2, 1.0, 1.0, 1.0, 0.01 ** 2])
+VELS = [(1.0, 0.1, 0.02), (3.5, -0.4, 0.1), (-2.0, 0.5, -0.3)]
+LARGEST = 1  # (3.5, -0.4, 0.1)
+P2P, P2L, P2D = 0, 1, 2
+HUBER, CAUCHY = 1, 2
+MATCH_LDS_CAP = 622  # CFEAR_MATCH_LDS_CAP: residual blocks the LDS match array holds
+
+
+class World:
+    """clouds of one synthetic drive, oracle scans and device scans of them under one context"""
+
+    def __init__(self, oracle, tie=0, imgs=None):
+        self.oracle = oracle
+        kw = dict(BASE)
+        self.kw = kw
+        if imgs is None:
+            imgs, self.gt = synth.world_sequence(6, seed=31, world_seed=555)
+        self.ctx = capi.Context(capi.default_params(**kw), A, R)
+        if tie:
+            self.ctx.tune(capi.TUNE_NN_TIE_RULE, tie)
+        po = oracle.default_params(**kw)
+        clouds = [oracle.cloud(oracle.filter_polar(img, 60, 12), RR, 2.5) for img in imgs]
+        self.so = [oracle.Scan(c, po) for c in clouds]
+        self.sg = [self.ctx.scan_create(self.ctx.cloud_upload(c)) for c in clouds]
+        assert [s.size for s in self.sg] == [s.size for s in self.so]
+        if len(imgs) != 6:  # a drive without ground truth: the oracle's own registration of the sweeps, each against up to three before it
+            poses = [np.zeros(3)]
+            for t in range(1, len(self.so)):
+                k0 = max(0, t - 3)
+                poses.append(oracle.register(self.so[k0:t + 1], np.array(poses[k0:t] + [poses[-1]]), po)[1][-1].copy())
+            self.gt = np.array(poses)
+
+    def params(self, **kw):
+        kw = dict(self.kw, **kw)
+        self.ctx.set_params(capi.default_params(**kw))
+        return self.oracle.default_params(**kw)
+
+    def close(self):
+        self.ctx.close()
+
+
+@pytest.fixture(scope="module")
+def world(oracle):
+    w = World(oracle)
+    yield w
+    w.close()
+
+
+def off_the_stamp_edge(oscan):
+    """no source cell within 1e-9 of the stamp's discontinuity atan2(u_y, u_x) = 1e-5"""
+    assert tc_ref.stamp_margin(oscan.cells()) >= 1e-9
+
+
+def compare(ref, dev, boundary=None):
+    """tests/test_register_fuzz_gpu.py::compare, tc_ref's result against the device's"""
+    retr, Pr, covr, Sr = ref
+    retg, Pg, covg, Sg = dev
+    k = len(Sr.inner_iterations)
+    same = (bool(retr) == retg and Sr.usable == Sg.usable and Sr.success == Sg.success and Sr.outer_iterations == Sg.outer_iterations and
+            list(Sr.inner_iterations) == list(Sg.inner_iterations[:k]) and not any(Sg.inner_iterations[k:8]) and
+            list(Sr.termination) == list(Sg.termination[:k]) and Sr.num_residuals == Sg.num_residuals and
+            Sr.num_residual_blocks == Sg.num_residual_blocks)
+    if not same:
+        note = "" if boundary is None else " (input on a decision boundary: %s)" % boundary()
+        raise AssertionError("decisions differ%s: restatement %r, device %r" % (note, tc_ref.decisions(Sr), (
+            Sg.success, Sg.usable, Sg.outer_iterations, list(Sg.inner_iterations[:8]), list(Sg.termination[:8]), Sg.num_residuals, Sg.num_residual_blocks)))
+    assert np.all(np.abs(Pg[:, :2] - Pr[:, :2]) < 1e-4) and np.all(np.abs(Pg[:, 2] - Pr[:, 2]) < 1e-5), (Pg[-1], Pr[-1])
+    if Sr.usable:
+        assert np.allclose(Sg.final_cost, Sr.final_cost, rtol=1e-9, atol=1e-12), (Sg.final_cost, Sr.final_cost)
+    assert np.allclose(covg, np.zeros((6, 6)) if covr is None else covr, rtol=1e-6, atol=1e-12)
+
+
+def differs(a, b):
+    """two device results further apart than the tolerance, or with other residual blocks"""
+    return bool(np.any(np.abs(a[1][:, :2] - b[1][:, :2]) >= 1e-4) or np.any(np.abs(a[1][:, 2] - b[1][:, 2]) >= 1e-5) or
+                a[3].num_residual_blocks != b[3].num_residual_blocks)
+
+
+def summary_bytes(S):
+    return bytes(memoryview(S))
+
+
+def run_case(w, sel, dpose, vel, ccw, prior=None, path=None, **kw):
+    oracle = w.oracle
+    po = w.params(**kw)
+    so, sg = [w.so[i] for i in sel], [w.sg[i] for i in sel]
+    off_the_stamp_edge(so[-1])
+    poses = w.gt[sel].copy()
+    poses[-1] += dpose
+    dev = w.ctx.register_time_continuous(sg, poses, vel, ccw, prior)
+    if path is not None:
+        assert dev[3].assoc_path == path, dev[3].assoc_path
+    ref = tc_ref.register(oracle, so, poses, po, vel, ccw, prior)
+    compare(ref, dev, lambda: tc_ref.on_decision_boundary(oracle, so, poses, po, vel, ccw, prior))
+    return ref, dev, (sg, poses)
+
+
+# ---- zero velocity ---------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("cost", [P2L, P2D, P2P])
+def test_zero_velocity_is_register_bit_for_bit(world, cost):
+    w = world
+    w.params(cost=cost)
+    sg = w.sg[:4]
+    poses = w.gt[:4].copy()
+    poses[-1] += [0.25, -0.15, 0.01]
+    for prior in (None, PRIOR):
+        exp = w.ctx.register(sg, poses) if prior is None else w.ctx.register_soft(sg, poses, prior)
+        assert exp[3].usable == 1 and exp[3].assoc_path == 1
+        for ccw in (0, 1):
+            got = w.ctx.register_time_continuous(sg, poses, (0.0, 0.0, 0.0), ccw, prior)
+            assert got[0] == exp[0] and got[1].tobytes() == exp[1].tobytes() and got[2].tobytes() == exp[2].tobytes()
+            assert summary_bytes(got[3]) == summary_bytes(exp[3])
+
+
+# ---- the block path: <= 4 keyframes, <= 256 source cells ---------------------------------------------------------------------
+@pytest.mark.parametrize("nkf,cost,loss,wopt,vi,ccw", [
+    (1, P2L, HUBER, 0, 0, 0), (3, P2L, CAUCHY, 2, 1, 1), (4, P2L, HUBER, 4, 2, 0), (4, P2L, CAUCHY, 4, 1, 0),
+    (1, P2D, CAUCHY, 2, 2, 1), (3, P2D, HUBER, 4, 0, 0), (4, P2D, CAUCHY, 0, 1, 1), (3, P2D, HUBER, 2, 2, 0),
+    (1, P2P, HUBER, 4, 1, 0), (3, P2P, CAUCHY, 0, 2, 1), (4, P2P, HUBER, 2, 0, 1), (1, P2P, CAUCHY, 0, 0, 1),
+])
+def test_block_path(world, nkf, cost, loss, wopt, vi, ccw):
+    sel = list(range(nkf)) + [nkf]
+    assert world.sg[nkf].size <= 256
+    ref, dev, (sg, poses) = run_case(world, sel, [0.2, 0.1, -0.008], VELS[vi], ccw, path=1, cost=cost, loss=loss, weight_opt=wopt)
+    assert dev[3].usable == 1
+    if vi == LARGEST:  # the compensation is being exercised: the plain registration of the same scans is another result
+        assert differs(world.ctx.register(sg, poses), dev)
+
+
+def test_block_path_with_prior(world):
+    for cost, ccw in ((P2L, 0), (P2P, 1)):
+        run_case(world, [0, 1, 2, 3], [0.2, 0.1, -0.008], VELS[1], ccw, prior=PRIOR, path=1, cost=cost)
+
+
+# ---- the grouped path ----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("cost,loss,wopt,vi,ccw,soft", [(P2L, HUBER, 4, 1, 0, False), (P2D, CAUCHY, 2, 2, 1, True), (P2P, HUBER, 0, 0, 1, False)])
+def test_grouped_path_nine_keyframes(world, cost, loss, wopt, vi, ccw, soft):
+    """9 keyframes (the scans repeated at their own poses): three groups, the last of one keyframe; more residual blocks than the
+    LDS match array holds, so part of them lives in memory"""
+    sel = [i % 5 for i in range(9)] + [5]
+    ref, dev, _ = run_case(world, sel, [0.3, 0.2, -0.01], VELS[vi], ccw, prior=PRIOR if soft else None, path=2, cost=cost, loss=loss, weight_opt=wopt)
+    assert dev[3].num_residual_blocks > MATCH_LDS_CAP
+
+
+@pytest.fixture(scope="module")
+def dense(oracle):
+    """five sweeps of the canyon drive (tests/test_surface_paths_gpu.py): more than 500 cells per scan"""
+    frames = np.empty((5, A, R), dtype=np.uint8)
+    for t0, chunk in synth.drive_chunks(5, "canyon", 3, 5, A, R, RR, ccw=False):
+        frames[t0:t0 + len(chunk)] = chunk
+    w = World(oracle, imgs=frames)
+    yield w
+    w.close()
+
+
+@pytest.mark.parametrize("nkf,cost,vi,ccw", [(2, P2L, 1, 1), (4, P2P, 2, 0)])
+def test_grouped_path_dense_scan(dense, nkf, cost, vi, ccw):
+    """<= 4 keyframes, but more source cells than one block of threads (a smaller res does not get this world past 256 cells: a cell
+    needs six points, and the sweeps have 3500; the canyon drive has the cells)"""
+    assert dense.sg[nkf].size > 256
+    run_case(dense, list(range(nkf)) + [nkf], [0.2, 0.1, -0.008], VELS[vi], ccw, path=2, cost=cost)
+
+
+# ---- the general path ------------------------------------------------------------------------------------------------------------
+def test_general_path_under_the_flann_tie_rule(oracle):
+    oracle.set_perturbation(["nn_tie_flann"])
+    try:
+        w = World(oracle, tie=2)
+        run_case(w, [0, 1, 2], [0.2, 0.1, -0.008], VELS[1], 0, path=3, cost=P2L)
+        w.close()
+    finally:
+        oracle.set_perturbation(0)
+
+
+# ---- P2P: the plain registration of compensated cells, through the existing kernel ---------------------------------------------------
+@pytest.mark.parametrize("vi,ccw", [(1, 0), (2, 1)])
+def test_p2p_equals_register_on_compensated_cells(world, vi, ccw):
+    w = world
+    w.params(cost=P2P)
+    sg = w.sg[:4]
+    poses = w.gt[:4].copy()
+    poses[-1] += [0.2, 0.1, -0.008]
+    cells = sg[-1].cells()
+    assert tc_ref.stamp_margin(cells) >= 1e-9
+    comp = w.ctx.scan_from_cells(tc_ref.compensate_cells(cells, VELS[vi], ccw))
+    tc = w.ctx.register_time_continuous(sg, poses, VELS[vi], ccw)
+    plain = w.ctx.register(sg[:3] + [comp], poses)
+    assert tc[3].assoc_path == 1 and plain[3].assoc_path == 1 and tc[3].usable == 1
+    assert tc[0] == plain[0] and tc[3].usable == plain[3].usable and tc[3].success == plain[3].success
+    assert tc[3].outer_iterations == plain[3].outer_iterations and list(tc[3].inner_iterations[:8]) == list(plain[3].inner_iterations[:8])
+    assert list(tc[3].termination[:8]) == list(plain[3].termination[:8])
+    assert tc[3].num_residuals == plain[3].num_residuals and tc[3].num_residual_blocks == plain[3].num_residual_blocks
+    assert np.all(np.abs(tc[1][:, :2] - plain[1][:, :2]) < 1e-4) and np.all(np.abs(tc[1][:, 2] - plain[1][:, 2]) < 1e-5)
+    assert np.allclose(tc[3].final_cost, plain[3].final_cost, rtol=1e-9, atol=1e-12) and np.allclose(tc[2], plain[2], rtol=1e-6, atol=1e-12)
+    comp.release()
+
+
+# ---- q19 ---------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("cost", [P2L, P2D])
+def test_q19_residuals_keep_the_uncorrected_mean(world, cost):
+    """the device follows the reference (matches found with the corrected mean, residuals on the uncorrected one), not the variant a
+    reader would expect (the corrected mean in the residual too)"""
+    ref, dev, (sg, poses) = run_case(world, [0, 1, 2, 3], [0.2, 0.1, -0.008], VELS[LARGEST], 0, path=1, cost=cost)
+    po = world.params(cost=cost)
+    so = world.so[:4]
+    expected_by_a_reader = tc_ref.register(world.oracle, so, poses, po, VELS[LARGEST], False, corrected_residual=True)
+    assert expected_by_a_reader[3].usable == 1
+    with pytest.raises(AssertionError):
+        compare(expected_by_a_reader, dev)
+
+
+# ---- failure modes -------------------------------------------------------------------------------------------------------------------
+def test_no_overlap_fails_and_leaves_the_covariance(world):
+    w = world
+    w.params(cost=P2L)
+    sg = w.sg[:2]
+    poses = w.gt[:2].copy()
+    poses[-1] += [500.0, 300.0, 0.0]
+    ref, dev, _ = run_case(w, [0, 1], [500.0, 300.0, 0.0], VELS[1], 0, cost=P2L)
+    assert dev[0] is False and dev[3].num_residuals <= 1 and dev[3].usable == 0
+    # the caller's covariance comes back as it went in (through the C ABI: capi.register_time_continuous starts from zeros)
+    L = capi.lib()
+    arr = (C.c_void_p * 2)(*[s._h for s in sg])
+    P, v, cov, S = poses.copy(), np.array(VELS[1]), np.arange(36, dtype=np.float64) + 0.5, capi.RegSummary()
+    rc = L.cfear_register_time_continuous(w.ctx.handle, arr, 2, P.ctypes.data, v.ctypes.data, 0, None, cov.ctypes.data, C.byref(S))
+    assert rc == 0 and S.success == 0 and S.num_residuals <= 1
+    assert np.array_equal(cov, np.arange(36, dtype=np.float64) + 0.5) and np.array_equal(P[-1], poses[-1])
+
+
+def test_bad_velocity_is_refused(world):
+    w = world
+    w.params(cost=P2L)
+    sg = w.sg[:3]
+    poses = w.gt[:3].copy()
+    for bad in ((np.nan, 0.0, 0.0), (0.0, np.inf, 0.0), (0.0, 0.0, -np.inf)):
+        with pytest.raises(capi.CfearError, match="rc=-1"):
+            w.ctx.register_time_continuous(sg, poses, bad)
+    L = capi.lib()
+    arr = (C.c_void_p * 3)(*[s._h for s in sg])
+    P, cov, S = poses.copy(), np.zeros(36), capi.RegSummary()
+    assert L.cfear_register_time_continuous(w.ctx.handle, arr, 3, P.ctypes.data, None, 0, None, cov.ctypes.data, C.byref(S)) == -1
+    v = np.array(VELS[0])
+    assert L.cfear_register_time_continuous(w.ctx.handle, arr, 1, P.ctypes.data, v.ctypes.data, 0, None, cov.ctypes.data, C.byref(S)) == -1  # n < 2
+    assert L.cfear_register_time_continuous(w.ctx.handle, arr, 65, P.ctypes.data, v.ctypes.data, 0, None, cov.ctypes.data, C.byref(S)) == -3  # n > 64
+    # ... and the context still registers
+    assert w.ctx.register_time_continuous(sg, poses, VELS[0])[3].usable == 1
+
+
+# ---- the C++ mirror --------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("vel,ccw,soft,cost", [((3.5, -0.4, 0.1), 0, 0, 1), ((-2.0, 0.5, -0.3), 1, 1, 0)])
+def test_mirror_register_time_continuous_matches_python(tmp_path, vel, ccw, soft, cost):
+    """host/tc_check: radarDriver, MapPointNormal, n_scan_normal_reg::RegisterTimeContinuous through the C++ mirror = the Python binding
+    on the same sweeps, poses and velocity, bit for bit"""
+    import math
+    from cfear_radarodometry_code_public_amd import build
+    build.build()
+    subprocess.check_call(["make", "-C", HOST], stdout=subprocess.DEVNULL)
+    imgs, _ = synth.world_sequence(3, seed=29)
+    f = tmp_path / "three.u8"
+    imgs[:3].tofile(f)
+    r = subprocess.run([os.path.join(HOST, "tc_check"), str(f)] + ["%r" % x for x in vel] + [str(ccw), str(soft), str(cost)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    got = json.loads(r.stdout)
+    ctx = capi.Context(capi.default_params(range_res=RR, k_strongest=12, z_min=60.0, res=3.0, weight_intensity=1, loss_limit=0.1, cost=cost, loss=1, weight_opt=4), A, R)
+    dsc = [ctx.scan_create(ctx.filter_polar(img, peaks=False)[0]) for img in imgs[:3]]
+    poses = np.array([[0, 0, 0], [1.0, 0.02, 0.02], [2.2, 0.1, 0.05]], dtype=np.float64)
+    # (the mirror hands Affine3d poses over: x, y and the yaw of the rotation matrix; Tvel likewise)
+    trip = lambda q: [q[0], q[1], math.atan2(math.sin(q[2]), math.cos(q[2]))]
+    prior = np.diag([0.1 * 0.1, 0.1 * 0.1, 0.0, 0.0, 0.0, 0.01 * 0.01]) if soft else None
+    ret, P, cov, S = ctx.register_time_continuous(dsc, np.array([trip(q) for q in poses]), trip(vel), ccw, prior)
+    assert S.assoc_path == 1 and S.usable == 1
+    assert got["ok"] == int(ret) and got["itr"] == S.outer_iterations and got["usable"] == S.usable and got["assoc_path"] == S.assoc_path
+    assert got["num_residuals"] == S.num_residuals and got["num_residual_blocks"] == S.num_residual_blocks
+    assert got["final_cost"] == S.final_cost and got["score"] == S.score
+    k = S.outer_iterations - 1
+    assert got["inner_iterations"] == list(S.inner_iterations[:k]) and got["termination"] == list(S.termination[:k])
+    assert np.array_equal(np.array(got["cov"]).reshape(6, 6), cov)
+    assert np.array_equal(np.array(got["poses"]), np.array([trip(q) for q in P]))
+    ctx.close()
