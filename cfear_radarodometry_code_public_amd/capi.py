@@ -37,6 +37,15 @@ class Params(C.Structure):
 FILTER_KSTRONG, FILTER_CACFAR = 0, 1
 
 
+class FuserOptions(C.Structure):
+    """cfear_fuser_options (include/cfear_hip.h): the fuser's soft_constraint and use_guess (odometrykeyframefuser.h:94) of a batched
+    odometry object or of one of its sequences"""
+    _fields_ = [("soft_constraint", C.c_int32), ("use_guess", C.c_int32)]
+
+    def __repr__(self):
+        return "FuserOptions(soft_constraint=%d, use_guess=%d)" % (self.soft_constraint, self.use_guess)
+
+
 class Cell(C.Structure):
     _fields_ = [
         ("mean", C.c_double * 2), ("cov", C.c_double * 3), ("normal", C.c_double * 2),
@@ -79,6 +88,7 @@ EXPORTS = [
     "cfear_odometry_set_cov_sampling", "cfear_odometry_cov_samples", "cfear_host_alloc", "cfear_host_free",
     "cfear_surface_dims", "cfear_get_surface", "cfear_odometry_set_surface_recording", "cfear_odometry_surface",
     "cfear_odometry_set_sequence_params", "cfear_odometry_sequence_params", "cfear_odometry_set_sequence_sources",
+    "cfear_default_fuser_options", "cfear_odometry_set_fuser_options", "cfear_odometry_fuser_options",
     "cfear_odometry_covariances", "cfear_odometry_status", "cfear_odometry_summary", "cfear_odometry_profile", "cfear_odometry_profile_read", "cfear_odometry_profile_read_stages", "cfear_odometry_phase_times", "cfear_time_kstrongest",
 ]
 
@@ -161,6 +171,9 @@ def lib():
         "cfear_odometry_set_sequence_params": (C.c_int, [vp, vp, vp, C.c_int]),
         "cfear_odometry_sequence_params": (C.c_int, [vp, vp, C.c_int, C.POINTER(Params)]),
         "cfear_odometry_set_sequence_sources": (C.c_int, [vp, vp, i32p, C.c_int, C.c_int]),
+        "cfear_default_fuser_options": (None, [C.POINTER(FuserOptions)]),
+        "cfear_odometry_set_fuser_options": (C.c_int, [vp, vp, vp, C.c_int]),
+        "cfear_odometry_fuser_options": (C.c_int, [vp, vp, C.c_int, C.POINTER(FuserOptions)]),
         "cfear_host_alloc": (C.c_int, [vp, C.c_size_t, C.POINTER(vp)]),
         "cfear_host_free": (None, [vp, vp]),
         "cfear_odometry_summary": (C.c_int, [vp, vp, C.c_int, C.POINTER(RegSummary), C.POINTER(C.c_int),
@@ -197,6 +210,16 @@ def default_params(**kw):
             raise AttributeError(k)
         setattr(p, k, v)
     return p
+
+
+def default_fuser_options(**kw):
+    o = FuserOptions()
+    lib().cfear_default_fuser_options(C.byref(o))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
 
 
 def _addr(a):
@@ -639,6 +662,23 @@ class Odometry:
         self._ctx._check(self._ctx._L.cfear_odometry_set_sequence_sources(self._ctx._h, self._h, src.ctypes.data, int(src.size), ns),
                          "cfear_odometry_set_sequence_sources")
         self.n_sources = ns
+
+    def set_fuser_options(self, rows):
+        """rows: one FuserOptions for every sequence, a list of one per sequence, or None for the defaults again
+        (cfear_odometry_set_fuser_options). Before the first sweep since creation / reset()."""
+        fn, c = self._ctx._L.cfear_odometry_set_fuser_options, self._ctx
+        if rows is None:
+            c._check(fn(c._h, self._h, None, 0), "cfear_odometry_set_fuser_options")
+            return
+        rows = [rows] if isinstance(rows, FuserOptions) else list(rows)
+        arr = (FuserOptions * len(rows))(*rows)
+        c._check(fn(c._h, self._h, C.cast(arr, C.c_void_p), len(rows)), "cfear_odometry_set_fuser_options")
+
+    def fuser_options(self, q):
+        """the FuserOptions sequence q runs with (cfear_odometry_fuser_options)"""
+        o = FuserOptions()
+        self._ctx._check(self._ctx._L.cfear_odometry_fuser_options(self._ctx._h, self._h, int(q), C.byref(o)), "cfear_odometry_fuser_options")
+        return o
 
     def set_cov_sampling(self, enable=True, xy_range=0.4, yaw_range=0.0043625, samples_per_axis=3, covariance_scaler=4.0):
         """estimate_cov_by_sampling and its companions (odometrykeyframefuser.h:104-110) for every sequence, from the next sweep on"""

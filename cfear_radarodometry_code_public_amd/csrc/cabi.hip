@@ -40,6 +40,11 @@ void cfear_default_params(cfear_params* p) {
   p->cfar_max_points = 0;
 }
 
+void cfear_default_fuser_options(cfear_fuser_options* o) {
+  o->soft_constraint = 0;  // odometrykeyframefuser.h:94
+  o->use_guess = 1;        // odometrykeyframefuser.h:94 (offline_odometry.cpp:273 forces it)
+}
+
 static int validate_params(cfear_ctx* ctx, const cfear_params* p) {
   if (p->k_strongest < 1 || p->k_strongest > 64) return cfear_fail(ctx, CFEAR_ERR_UNSUPPORTED, "k_strongest must be in 1..64");
   if (!(p->range_res > 0.f)) return cfear_fail(ctx, CFEAR_ERR_INVALID, "range_res must be > 0");

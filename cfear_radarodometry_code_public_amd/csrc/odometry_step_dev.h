@@ -45,6 +45,9 @@ struct CovSampleCtx {
   int itr;            // radar_reg->itr_ after Register: the sweep's outer iterations (selects the association radius of GetCost)
   int num_residuals;  // of the registration's last problem (GetCovarianceScaler)
   int sampled;        // cov_sampled_success of the last sampling (written by the sampling stage)
+  int soft;           // the registration ran soft (cfear_fuser_options::soft_constraint): num_residuals / final_cost include the prior
+                      // block where it joined; cfear_odometry_surface builds its problem with the prior too
+  int pad_;
   double final_cost;
   int slot[MAX_SCANS];
   double pose[3 * MAX_SCANS];  // the registration's parameter vectors after the solve: keyframes, then the registered pose (T_vek)
@@ -81,8 +84,9 @@ struct OdoParams {
   CovSampling cs;  // cost-sampling covariance and / or per-sweep covariances (cs.ctx / cs.cov_out null: neither)
   int* flags;  // word 0 for the odometry object, word 1 + q for sequence q: bit 0 = some scan had more cells than its block holds, bit 1 = some cloud had more points
                // than the object is sized for (both CFEAR_ERR_CAPACITY); null: cannot happen
-  // per-sequence parameters and input sweeps (cfear_odometry_set_sequence_params / _set_sequence_sources): [B] rows, row q for sequence q.
-  // null: every sequence runs with the values above and reads sweep q (the production kernels do exactly the work they did without it)
+  // per-sequence parameters, input sweeps and fuser options (cfear_odometry_set_sequence_params / _set_sequence_sources /
+  // _set_fuser_options): [B] rows, row q for sequence q. null: every sequence runs with the values above, reads sweep q and keeps the
+  // fuser's defaults (the production kernels do exactly the work they did without it)
   const SeqParams* seq;
   int n_sources;  // sweeps per step in the filter's output (the sequences when there is no source map)
 };
@@ -97,7 +101,7 @@ __device__ __forceinline__ SeqRow seq_row(const OdoParams& OP, int q) {
 }
 
 static_assert(sizeof(SeqState) == 3 * sizeof(Aff2) + 4 * sizeof(int) + MAX_SCANS * (sizeof(int) + sizeof(Aff2)), "SeqState is sized by the fixed MAX_SCANS");
-static_assert(sizeof(CovSampleCtx) == 4 * sizeof(int) + sizeof(double) + MAX_SCANS * (sizeof(int) + 3 * sizeof(double)), "CovSampleCtx is sized by the fixed MAX_SCANS");
+static_assert(sizeof(CovSampleCtx) == 6 * sizeof(int) + sizeof(double) + MAX_SCANS * (sizeof(int) + 3 * sizeof(double)), "CovSampleCtx is sized by the fixed MAX_SCANS");
 static_assert(std::is_trivially_copyable<OdoParams>::value && std::is_trivially_copyable<BlockScratch>::value && std::is_trivially_copyable<SeqState>::value,
               "kernel arguments and device state are copied byte for byte");
 }  // namespace cfear_dev
@@ -309,7 +313,11 @@ __device__ __forceinline__ void register_step_body(unsigned char* lds /* RegLds:
   if (TIMED && pt.acc2 && tid == 0) for (int i = 0; i < 8; i++) pt.acc2[i] = 0;
   if (TIMED) pt.mark();
   if (!TIMED && OP.wg_times && tid == 0) OP.wg_times[(size_t)q * 32 + 14] = (long long)wall_clock64();
-  const Aff2 Tguess = aff_mul(T_prev, TprevMot);  // :166
+  // the fuser's switches of this sequence (cfear_fuser_options; no row: the defaults). Read here and again after the solve: nothing of
+  // the row stays in registers across it
+  int fopt = 0;
+  if (const SeqRow row = seq_row(OP, q)) fopt = row->fuser;
+  const Aff2 Tguess = (fopt & SEQ_FUSER_NO_GUESS) ? T_prev : aff_mul(T_prev, TprevMot);  // :165-168 (use_guess)
   cfear_reg_summary* sum = &summaries[q];
   __syncthreads();  // every thread has read the state before thread 0 rewrites it
   if (nkf == 0) {  // :171-177
@@ -349,14 +357,18 @@ __device__ __forceinline__ void register_step_body(unsigned char* lds /* RegLds:
   if (tid >= 64 && tid < 100) cov_work[(size_t)q * 36 + (tid - 64)] = ((tid - 64) % 7 == 0) ? 1.0 : 0.0;
   __syncthreads();
   const RegScratch RW = make_rscratch(B, lds);
+  // soft_constraint (:186): the prior's covariance is cov_vek.back(), the Identity66 just written (read by the controller wave before
+  // anything writes the covariance); its centre is the normalised Tguess, its weight sqrt(#cells of the current scan) (register_block)
   register_block<KCOST>(sp, ns, poses, cov_work + (size_t)q * 36, OP.rp, RW, reinterpret_cast<double*>(lds + RegLds::par),
-                 reinterpret_cast<RegShared*>(lds + RegLds::regsh), sum, TIMED ? &pt : nullptr, nullptr, seq_row(OP, q));  // :186 (result ignored, :184-186)
+                 reinterpret_cast<RegShared*>(lds + RegLds::regsh), sum, TIMED ? &pt : nullptr,
+                 (fopt & SEQ_FUSER_SOFT) ? cov_work + (size_t)q * 36 : nullptr, seq_row(OP, q));  // :186 (result ignored, :184-186)
   __syncthreads();
   if (TIMED) pt.mark();
   if (tid == 0) {
     if (OP.cs.ctx) {  // estimate_cov_by_sampling: the scans and poses of this registration, before the sanity check and AddToReference (:202-208)
       CovSampleCtx* c = OP.cs.ctx + q;
       c->n = ns; c->itr = sum->outer_iterations; c->num_residuals = sum->num_residuals; c->final_cost = sum->final_cost;
+      c->soft = reinterpret_cast<const RegShared*>(lds + RegLds::regsh)->prior_on;  // (the solver's own state: no option kept across the solve)
       for (int i = 0; i < nkf; i++) c->slot[i] = st->ring[i];
       c->slot[ns - 1] = cur_slot;
       for (int i = 0; i < 3 * ns; i++) c->pose[i] = poses[i];

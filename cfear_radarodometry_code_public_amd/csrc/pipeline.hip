@@ -216,7 +216,9 @@ __global__ __launch_bounds__(BLOCK_R, 3) void surface_build_kernel(ScanDev* cons
   }
 }
 // ... of every sequence of a batched odometry object around its last registration (cfear_odometry_surface): what register_step_body
-// recorded in OP.cs.ctx; a sequence without a registration in the last step (n < 2) gets no blocks (its coordinates: none visited)
+// recorded in OP.cs.ctx; a sequence without a registration in the last step (n < 2) gets no blocks (its coordinates: none visited).
+// A sequence whose registration ran soft (cfear_fuser_options::soft_constraint) gets the prior the fuser passes: Identity66
+// (FormatScans, odometrykeyframefuser.cpp:486-491) around the recorded pose, as cfear_get_surface with that prior_cov6
 template <bool NAIVE>
 __global__ __launch_bounds__(BLOCK_R, 3) void surface_build_step_kernel(OdoParams OP, const BlockScratch* scratch, SurfHdr* hdr, const double* coords,
                                                                      const int* nxy, int pixels, double* out) {
@@ -233,10 +235,13 @@ __global__ __launch_bounds__(BLOCK_R, 3) void surface_build_step_kernel(OdoParam
   ScanDev** sp = reinterpret_cast<ScanDev**>(lds + RegLds::scanptr);
   for (int i = threadIdx.x; i < n; i += BLOCK_R)
     sp[i] = reinterpret_cast<ScanDev*>(OP.scans_base + OP.scan_stride * ((size_t)q * nslots + cx->slot[i]));
+  __shared__ double prior_id[36];
+  if (threadIdx.x < 36) prior_id[threadIdx.x] = (threadIdx.x % 7 == 0) ? 1.0 : 0.0;
   __syncthreads();
   const RegScratch W = make_rscratch(scratch[q], lds);
   RegShared* sh = reinterpret_cast<RegShared*>(lds + RegLds::regsh);
-  surface_build_block(sp, n, cx->pose, OP.rp, W, reinterpret_cast<double*>(lds + RegLds::par), sh, cx->itr, nullptr, hdr + q, seq_row(OP, q));
+  surface_build_block(sp, n, cx->pose, OP.rp, W, reinterpret_cast<double*>(lds + RegLds::par), sh, cx->itr, cx->soft ? prior_id : nullptr, hdr + q,
+                      seq_row(OP, q));
   if (NAIVE) {
     __syncthreads();
     surface_naive_eval(sh, hdr + q, coords + (size_t)q * 2 * pixels, nxy[2 * q], nxy[2 * q + 1], pixels, out + (size_t)q * pixels * pixels);
@@ -531,7 +536,8 @@ struct cfear_odometry {
   std::vector<cfear_params> seq_rows;  // [B] the caller's table; empty: every sequence runs with the context's parameters
   std::vector<int32_t> seq_src;        // [B] the sweep each sequence reads; empty: sweep q for sequence q
   int n_sources = 0;                   // sweeps per step with a source map (0: B)
-  SeqParams* d_seq = nullptr;          // [B] what the kernels read (OdoParams::seq); exists while either of the above does
+  std::vector<cfear_fuser_options> fuser_opts;  // [B] cfear_odometry_set_fuser_options; empty: the defaults (no prior, constant-velocity guess)
+  SeqParams* d_seq = nullptr;          // [B] what the kernels read (OdoParams::seq); exists while any of the above does
   cfear_params seq_par_seen;           // the context's parameters d_seq was built and the rows were checked against
   int seq_zmin = -1;                   // the filter's threshold: the smallest z_min of the rows (-1: the context's)
   long long sweeps = 0;                // sweeps processed since cfear_odometry_create / cfear_odometry_reset
@@ -647,10 +653,10 @@ static int seq_rows_check(cfear_ctx* ctx, const cfear_odometry* o, const cfear_p
   }
   return CFEAR_OK;
 }
-// (re)builds the device table from the rows (or the context's parameters) and the source map; frees it when neither is set. The context
+// (re)builds the device table from the rows (or the context's parameters), the source map and the fuser options; frees it when none is set. The context
 // stream and the object's streams are idle when this is called.
 static int seq_table_upload(cfear_ctx* ctx, cfear_odometry* o) {
-  if (o->seq_rows.empty() && o->seq_src.empty()) {
+  if (o->seq_rows.empty() && o->seq_src.empty() && o->fuser_opts.empty()) {
     if (o->d_seq) (void)hipFree(o->d_seq);
     o->d_seq = nullptr; o->seq_zmin = -1;
     return CFEAR_OK;
@@ -660,6 +666,7 @@ static int seq_table_upload(cfear_ctx* ctx, cfear_odometry* o) {
   for (int q = 0; q < o->B; q++) {
     t[q] = seq_row_of(o->seq_rows.empty() ? ctx->par : o->seq_rows[q], o->seq_src.empty() ? q : o->seq_src[q]);
     zmin = std::min(zmin, t[q].z_min);
+    if (!o->fuser_opts.empty()) t[q].fuser = (o->fuser_opts[q].soft_constraint ? SEQ_FUSER_SOFT : 0) | (o->fuser_opts[q].use_guess ? 0 : SEQ_FUSER_NO_GUESS);
   }
   if (!o->d_seq && hipMalloc(&o->d_seq, sizeof(SeqParams) * (size_t)o->B) != hipSuccess) return cfear_fail(ctx, CFEAR_ERR_NOMEM, "hipMalloc sequence parameter table");
   CFEAR_HIP_CHECK(ctx, hipMemcpy(o->d_seq, t.data(), sizeof(SeqParams) * t.size(), hipMemcpyHostToDevice));
@@ -1532,7 +1539,7 @@ int cfear_odometry_reset(cfear_ctx* ctx, cfear_odometry* o) {
   if (o->d_flags) CFEAR_HIP_CHECK(ctx, hipMemsetAsync(o->d_flags, 0, sizeof(int) * ((size_t)o->B + 1), ctx->stream));
   o->order_ready = false;
   o->surf_ready = false;
-  o->sweeps = 0;  // (the parameter table and the source map stay)
+  o->sweeps = 0;  // (the parameter table, the source map and the fuser options stay)
   CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   return CFEAR_OK;
 }
@@ -2234,6 +2241,46 @@ int cfear_odometry_set_sequence_sources(cfear_ctx* ctx, cfear_odometry* o, const
   // the staging and chunk buffers are sized per input sweep of a step: released here, allocated again (for the sources) by the next call that needs them
   for (void** p : {(void**)&o->d_polar, (void**)&o->rp_polar[0], (void**)&o->rp_polar[1], (void**)&o->rp_slots[0], (void**)&o->rp_slots[1]}) { if (*p) (void)hipFree(*p); *p = nullptr; }
   o->rp_chunk = 0; o->rp_polar_chunk = 0; o->rp_used_pending[0] = o->rp_used_pending[1] = false;
+  return CFEAR_OK;
+}
+
+// ---- the fuser's own switches (odometrykeyframefuser.h:94; odometrykeyframefuser.cpp:165-168, :186) per sequence ------------------------
+int cfear_odometry_set_fuser_options(cfear_ctx* ctx, cfear_odometry* o, const cfear_fuser_options* rows, int n_rows) {
+  if (!ctx || !o) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_set_fuser_options: bad argument");
+  if (rows && n_rows != 1 && n_rows != o->B) {
+    char msg[200];
+    snprintf(msg, sizeof(msg), "odometry_set_fuser_options: n_rows = %d (1: every sequence, or the object's n_sequences = %d: row q for sequence q)", n_rows, o->B);
+    return cfear_fail(ctx, CFEAR_ERR_INVALID, msg);
+  }
+  CFEAR_TRY(seq_fresh_check(ctx, o, "odometry_set_fuser_options"));
+  bool defaults = true;
+  for (int q = 0; rows && q < n_rows; q++) {
+    const char* f = nullptr;
+    int v = 0;
+    if (rows[q].soft_constraint != 0 && rows[q].soft_constraint != 1) { f = "soft_constraint"; v = rows[q].soft_constraint; }
+    else if (rows[q].use_guess != 0 && rows[q].use_guess != 1) { f = "use_guess"; v = rows[q].use_guess; }
+    if (f) {
+      char msg[200];
+      snprintf(msg, sizeof(msg), "odometry_set_fuser_options: row %d: %s = %d (must be 0 or 1)", q, f, v);
+      return cfear_fail(ctx, CFEAR_ERR_INVALID, msg);
+    }
+    if (rows[q].soft_constraint != 0 || rows[q].use_guess != 1) defaults = false;
+  }
+  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  CFEAR_TRY(odo_join(ctx, o));
+  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  std::vector<cfear_fuser_options> keep;  // (all rows at the defaults: no options, the object as it was before the call)
+  if (!defaults) for (int q = 0; q < o->B; q++) keep.push_back(rows[n_rows == 1 ? 0 : q]);
+  o->fuser_opts.swap(keep);
+  const int rc = seq_table_upload(ctx, o);
+  if (rc != CFEAR_OK) { o->fuser_opts.swap(keep); (void)seq_table_upload(ctx, o); }  // (the previous setting)
+  return rc;
+}
+
+int cfear_odometry_fuser_options(cfear_ctx* ctx, cfear_odometry* o, int sequence, cfear_fuser_options* out) {
+  if (!ctx || !o || !out || sequence < 0 || sequence >= o->B) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_fuser_options: bad argument");
+  if (o->fuser_opts.empty()) cfear_default_fuser_options(out);
+  else *out = o->fuser_opts[(size_t)sequence];
   return CFEAR_OK;
 }
 

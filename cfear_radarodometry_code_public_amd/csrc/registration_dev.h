@@ -34,8 +34,10 @@ struct SeqParams {
   int weight_intensity, loss, weight_opt, max_outer, min_itr, max_inner, compensate, use_keyframe;
   int z_min;     // as the filter compares it: (uint8_t)(int)z_min
   int source;    // the sweep of a step's input this sequence reads
-  int pad_;
+  int fuser;     // cfear_fuser_options as the step takes them (cfear_odometry_set_fuser_options): SEQ_FUSER_* bits, 0 = the defaults
 };
+constexpr int SEQ_FUSER_SOFT = 1;      // soft_constraint: Register(..., soft_constraints = true) (odometrykeyframefuser.cpp:186)
+constexpr int SEQ_FUSER_NO_GUESS = 2;  // use_guess = 0: Tguess = T_prev (:167-168)
 typedef const __attribute__((address_space(4))) SeqParams* SeqRow;  // (constant address space: never written while a kernel may read it)
 // the registration's parameters of a sequence with a row (null: P stays what the context gave)
 __device__ __forceinline__ void seq_reg_params(RegParams& P, SeqRow row) {

@@ -40,7 +40,8 @@ int main(int argc, char** argv) {
            "                      message is a fresh pageable allocation per sweep - the default 0 measures that\n"
            "       [--replay 1]   whole recording through cfear_odometry_replay_host (pieces of 256 sweeps in pinned memory, no\n"
            "                      host round trip per sweep) instead of one CallbackOffline + pointcloudCallback per sweep; --covar_sampling and\n"
-           "                      --cov_file work there too (cfear_odometry_set_cov_sampling, cfear_odometry_replay_host_cov), --soft_constraint does not\n");
+           "                      --cov_file work there too (cfear_odometry_set_cov_sampling, cfear_odometry_replay_host_cov), and so does\n"
+           "                      --soft_constraint (cfear_odometry_set_fuser_options); Oxford sweeps only\n");
     return argc < 2;
   }
   const std::string frames = arg(argc, argv, "--frames", "");
@@ -94,8 +95,8 @@ int main(int argc, char** argv) {
     dev->check(cfear_tune(dev->ctx(), CFEAR_TUNE_NN_TIE_RULE, atoi(arg(argc, argv, "--nn-tie", "0"))), "cfear_tune");
     if (!atoi(arg(argc, argv, "--replay", "0"))) dev->check(cfear_tune(dev->ctx(), CFEAR_TUNE_VOXEL_ORDER, atoi(arg(argc, argv, "--voxel-order", "0"))), "cfear_tune");
     if (atoi(arg(argc, argv, "--replay", "0"))) {
-      if (rad_par.dataset != "oxford" || par.soft_constraint)
-        throw std::runtime_error("--replay 1 runs the Oxford route without soft constraints; use the per-sweep route for those");
+      if (rad_par.dataset != "oxford")
+        throw std::runtime_error("--replay 1 runs the Oxford route; use the per-sweep route for the other datasets");
       // maximum-rate replay: the same parameters the two classes would apply, set once; the loop of offline_odometry.cpp:103-125
       // runs on the device sweep after sweep, the poses of a piece come back together
       cfear_params q = p;
@@ -117,6 +118,11 @@ int main(int argc, char** argv) {
       if (par.estimate_cov_by_sampling)  // odometrykeyframefuser.cpp:202-208 on the device, after every sweep's registration
         dev->check(cfear_odometry_set_cov_sampling(dev->ctx(), odo, 1, par.cov_sampling_xy_range, par.cov_sampling_yaw_range,
                                                    (int)par.cov_sampling_samples_per_axis, par.cov_sampling_covariance_scaler), "cfear_odometry_set_cov_sampling");
+      {  // the fuser's own switches (odometrykeyframefuser.h:94; offline_odometry.cpp:273-274) on the batched route
+        cfear_fuser_options fo; cfear_default_fuser_options(&fo);
+        fo.soft_constraint = par.soft_constraint ? 1 : 0; fo.use_guess = par.use_guess ? 1 : 0;
+        dev->check(cfear_odometry_set_fuser_options(dev->ctx(), odo, &fo, 1), "cfear_odometry_set_fuser_options");
+      }
       const int piece = 256;
       const size_t sweep = (size_t)A * R;
       void* pinned = nullptr;

@@ -44,10 +44,40 @@ def param_grid(base, **axes):
     return rows
 
 
-def replay_grid(frames, rows, A=None, R=None, gt=None, device=0, piece=256, context_params=None):
+# ... with the fuser's own switches (capi.FuserOptions): soft_constraint is the worker's third loop (utils/worker:40-46: after radar_ccw,
+# before disable_compensate); use_guess is not a loop of the worker and nests inside all of them
+FUSER_GRID_ORDER = GRID_ORDER[:1] + ("soft_constraint",) + GRID_ORDER[1:] + ("use_guess",)
+FUSER_AXES = ("soft_constraint", "use_guess")
+
+
+def fuser_grid(base, base_options=None, **axes):
+    """param_grid with the fuser's soft_constraint and use_guess allowed as axes, in the reference's loop order (soft_constraint between
+    radar_ccw and compensate, use_guess innermost of the worker's axes; other axes inside those, in the order given). base: a
+    capi.Params; base_options: the capi.FuserOptions the axes start from (None: the defaults 0, 1). -> (rows, options): a list of
+    capi.Params and a list of capi.FuserOptions of the same length, job 1 first - what replay_grid(frames, rows, options=options)
+    takes. Pure Python (no device)."""
+    import itertools
+    for k in axes:
+        if k not in FUSER_AXES and not hasattr(base, k):
+            raise AttributeError(k)
+    b_soft, b_guess = (0, 1) if base_options is None else (int(base_options.soft_constraint), int(base_options.use_guess))
+    names = [k for k in FUSER_GRID_ORDER if k in axes] + [k for k in axes if k not in FUSER_GRID_ORDER]
+    rows, options = [], []
+    for values in itertools.product(*[list(axes[k]) for k in names]):
+        p = capi.Params.from_buffer_copy(base)
+        o = capi.FuserOptions(b_soft, b_guess)
+        for k, v in zip(names, values):
+            setattr(o if k in FUSER_AXES else p, k, v)
+        rows.append(p)
+        options.append(o)
+    return rows, options
+
+
+def replay_grid(frames, rows, A=None, R=None, gt=None, device=0, piece=256, context_params=None, options=None):
     """One recording under len(rows) parameter sets in one batched odometry object: frames uint8 [n, A, R], rows a list of capi.Params that
     agree in the object-wide fields (param_grid of one base does). The recording is the single source sweep of every sequence: it is
-    copied and filtered once per sweep. -> dict(poses [n, len(rows), 3], records, drift: per row KITTI drift against gt ([n, 4, 4]
+    copied and filtered once per sweep. options: a capi.FuserOptions for every row or a list of one per row (fuser_grid builds both
+    lists); None: the fuser's defaults. -> dict(poses [n, len(rows), 3], records, drift: per row KITTI drift against gt ([n, 4, 4]
     poses) or None)."""
     frames = np.ascontiguousarray(frames, dtype=np.uint8)
     n, A, R = frames.shape
@@ -59,6 +89,11 @@ def replay_grid(frames, rows, A=None, R=None, gt=None, device=0, piece=256, cont
         odo = ctx.odometry(len(rows))
         odo.set_sequence_params(rows)
         odo.set_sequence_sources(np.zeros(len(rows), dtype=np.int32), 1)
+        if options is not None:
+            opts = options if isinstance(options, capi.FuserOptions) else list(options)
+            if not isinstance(opts, capi.FuserOptions) and len(opts) != len(rows):
+                raise ValueError("replay_grid: %d option sets for %d rows" % (len(opts), len(rows)))
+            odo.set_fuser_options(opts)
         recs = [odo.replay_host(frames[t0:t0 + piece, None]) for t0 in range(0, n, piece)]
         rec = np.concatenate(recs, axis=0)
     finally:

@@ -367,8 +367,10 @@ int cfear_odometry_cov_samples(cfear_ctx* ctx, cfear_odometry* odo, int sequence
  * itself does not run unless cfear_odometry_set_cov_sampling is on). Off by default; poses, covariances and summaries do not change;
  * cfear_odometry_reset keeps the setting. The replay routes do not record. */
 int cfear_odometry_set_surface_recording(cfear_ctx* ctx, cfear_odometry* odo, int enable);
-/* One surface per sequence around its last registration: the recorded scans, poses and itr_, no soft prior (the batched route has
- * none), with one build launch and one evaluation launch for all sequences. d_surface: caller-owned device buffer of n_sequences *
+/* One surface per sequence around its last registration: the recorded scans, poses and itr_ - and, for a sequence whose recorded
+ * registration ran soft (cfear_odometry_set_fuser_options), the prior the fuser passes: Identity66 around the recorded registered pose,
+ * as cfear_get_surface with that prior_cov6 (a sequence without soft_constraint stays prior-free) - with one build launch and one
+ * evaluation launch for all sequences. d_surface: caller-owned device buffer of n_sequences *
  * pixels * pixels doubles (pixels: cfear_surface_dims), sequence q's surface row-major at q * pixels * pixels; unvisited cells NaN,
  * and a sequence without a registration in the last step (its first sweep) or no step since the last reset / replay: all NaN.
  * Optional host outputs of what was evaluated: n_used (n_sequences: scans of the problem, 0 = none), itr_used (n_sequences),
@@ -408,6 +410,33 @@ int cfear_odometry_sequence_params(cfear_ctx* ctx, cfear_odometry* odo, int sequ
  * range: CFEAR_ERR_INVALID, nothing changed. As the table: only before the first sweep since create / reset; reset keeps it.
  * Synchronises the context stream. */
 int cfear_odometry_set_sequence_sources(cfear_ctx* ctx, cfear_odometry* odo, const int32_t* source, int n_sequences, int n_sources);
+/* ---- The fuser's own switches on the batched routes (OdometryKeyframeFuser::Parameters soft_constraint and use_guess,
+ * odometrykeyframefuser.h:94; offline_odometry.cpp:166,273-274; the third loop of the evaluation grid, utils/worker:43), per object or per
+ * sequence. They are not in cfear_params (whose layout is fixed); the defaults are what the batched routes did before: 0, 1. */
+typedef struct cfear_fuser_options {
+  int32_t soft_constraint; /* 1: Register(scans, T, cov, soft_constraints = true) (odometrykeyframefuser.cpp:186): on every sweep that
+                            * registers, mahalanobisDistanceError (n_scan_normal.h:259-290) joins the problem after the residual-count
+                            * check (n_scan_normal.cpp:370-377) - covariance Identity66 (FormatScans, odometrykeyframefuser.cpp:486-491),
+                            * centre the normalised Tguess of the sweep, weight sqrt(cells of the current scan), rebuilt around the same
+                            * centre at every outer iteration. As cfear_register_soft: num_residuals counts three more; final_cost,
+                            * outer_cost, the termination tests and GetCovariance include the prior, and the summary, the sweep records
+                            * and cfear_odometry_covariances report exactly that. The cost sampling (cfear_odometry_set_cov_sampling)
+                            * samples GetCost without the prior (n_scan_normal.cpp:202) and scales with the soft Register's final_cost
+                            * and num_residuals (GetCovarianceScaler, :435-441). */
+  int32_t use_guess;       /* 0: Tguess = T_prev (odometrykeyframefuser.cpp:167-168) instead of T_prev * Tmot (:166): the start of the
+                            * registration, the fallback of AccelerationVelocitySanityCheck (:199) and the centre of the prior.
+                            * Motion compensation still uses Tmot. */
+} cfear_fuser_options;
+void cfear_default_fuser_options(cfear_fuser_options* o); /* soft_constraint 0, use_guess 1 */
+/* rows: n_rows = 1 (every sequence) or the object's n_sequences (row q for sequence q); NULL: back to the defaults. CFEAR_ERR_INVALID
+ * for a value other than 0 or 1 (the message names the row and the field), for any other n_rows, or on an object that has processed a
+ * sweep since cfear_odometry_create / cfear_odometry_reset; nothing changes on failure. cfear_odometry_reset keeps the setting. It is
+ * independent of the parameter table and the source map and works with or without either, on k-strongest and CA-CFAR objects; every
+ * route of the object honours it (cfear_odometry_step_*, cfear_odometry_replay_*, both registration kernels, ODOMETRY_OVERLAP), and the
+ * record behind the cost sampling and cfear_odometry_surface notes that the registration ran soft. Synchronises the context stream. */
+int cfear_odometry_set_fuser_options(cfear_ctx* ctx, cfear_odometry* odo, const cfear_fuser_options* rows, int n_rows);
+/* The options sequence q runs with (the defaults without a call). */
+int cfear_odometry_fuser_options(cfear_ctx* ctx, cfear_odometry* odo, int sequence, cfear_fuser_options* out);
 /* Has any scan of this object been truncated - more oriented surface points than CFEAR_TUNE_MAX_CELLS, or a cloud with more points than the object
  * holds? Synchronises the context stream; returns CFEAR_OK or CFEAR_ERR_CAPACITY (with the message the reading calls give). For callers of the
  * asynchronous cfear_odometry_replay_device, which read their records on the device and never pass through poses / summary / replay_host.
