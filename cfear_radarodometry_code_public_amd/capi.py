@@ -76,6 +76,19 @@ SWEEP_RECORD_DTYPE = np.dtype([("pose", "f8", 3), ("final_cost", "f8"), ("outer_
                                ("n_keyframes", "i4"), ("n_cells", "i4"), ("inner_iterations", "i4", 8)])
 assert SWEEP_RECORD_DTYPE.itemsize == 80
 
+
+
+class Drift(C.Structure):
+    """cfear_drift (include/cfear_hip.h): the KITTI drift of one trajectory with its per-length table (100 ... 800 m)"""
+    _fields_ = [("translation_percent", C.c_double), ("rotation_deg_per_100m", C.c_double),
+                ("translation_percent_by_length", C.c_double * 8), ("rotation_deg_per_100m_by_length", C.c_double * 8),
+                ("segments", C.c_int32), ("segments_by_length", C.c_int32 * 8), ("reserved", C.c_int32)]
+
+
+DRIFT_DTYPE = np.dtype([("translation_percent", "f8"), ("rotation_deg_per_100m", "f8"), ("translation_percent_by_length", "f8", 8),
+                        ("rotation_deg_per_100m_by_length", "f8", 8), ("segments", "i4"), ("segments_by_length", "i4", 8), ("reserved", "i4")])
+assert DRIFT_DTYPE.itemsize == C.sizeof(Drift) == 184
+
 EXPORTS = [
     "cfear_version", "cfear_default_params", "cfear_create", "cfear_destroy", "cfear_last_error",
     "cfear_set_params", "cfear_synchronize", "cfear_tune", "cfear_kstrongest_device", "cfear_kstrongest_host",
@@ -90,6 +103,7 @@ EXPORTS = [
     "cfear_odometry_set_sequence_params", "cfear_odometry_sequence_params", "cfear_odometry_set_sequence_sources",
     "cfear_default_fuser_options", "cfear_odometry_set_fuser_options", "cfear_odometry_fuser_options",
     "cfear_odometry_covariances", "cfear_odometry_status", "cfear_odometry_summary", "cfear_odometry_profile", "cfear_odometry_profile_read", "cfear_odometry_profile_read_stages", "cfear_odometry_phase_times", "cfear_time_kstrongest",
+    "cfear_drift_segments", "cfear_drift_plan_create", "cfear_drift_plan_release", "cfear_drift_device", "cfear_drift_host",
 ]
 
 
@@ -183,6 +197,11 @@ def lib():
         "cfear_odometry_profile_read_stages": (C.c_int, [vp, vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int)]),
         "cfear_odometry_phase_times": (C.c_int, [vp, vp, C.c_int, vp]),
         "cfear_time_kstrongest": (C.c_int, [vp, u8p, C.c_int, u32p, C.c_int, C.c_int, C.POINTER(C.c_double)]),
+        "cfear_drift_segments": (C.c_int, [f64p, C.c_int, i32p, i32p, i32p, C.c_int, C.POINTER(C.c_int)]),
+        "cfear_drift_plan_create": (C.c_int, [vp, f64p, C.c_int, C.POINTER(vp)]),
+        "cfear_drift_plan_release": (None, [vp, vp]),
+        "cfear_drift_device": (C.c_int, [vp, vp, vp, C.c_size_t, C.c_size_t, C.c_int, C.c_int, vp]),
+        "cfear_drift_host": (C.c_int, [vp, vp, vp, C.c_size_t, C.c_size_t, C.c_int, C.c_int, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError if the ABI is incomplete (tests/test_abi.py checks every export)
@@ -200,6 +219,28 @@ def surface_dims(res, width, x0=0.0, y0=0.0):
     if rc != 0:
         raise CfearError("cfear_surface_dims failed rc=%d" % rc)
     return p.value, nx.value, ny.value
+
+
+def _gt34(gt):
+    """ground-truth poses [n, 4, 4] or [n, 3, 4] (or [n, 12]) -> contiguous [n, 12] doubles, the 3x4 row-major form of a KITTI line"""
+    g = np.asarray(gt, dtype=np.float64)
+    g = g.reshape(len(g), -1, 4)[:, :3, :] if g.ndim == 3 else g.reshape(len(g), 3, 4)
+    return np.ascontiguousarray(g).reshape(len(g), 12)
+
+
+def drift_segments(gt):
+    """cfear_drift_segments (host only, no device): the (first, last, length index) triples of the KITTI drift metric for the ground
+    truth gt, in the metric's order -> int32 array [m, 3] (kitti.segments is the numpy statement)"""
+    g = _gt34(gt)
+    m = C.c_int()
+    rc = lib().cfear_drift_segments(g.ctypes.data, len(g), None, None, None, 0, C.byref(m))
+    if rc not in (0, -6):  # (CFEAR_ERR_CAPACITY with the count is the answer to capacity 0)
+        raise CfearError("cfear_drift_segments failed rc=%d" % rc)
+    out = np.zeros((3, max(m.value, 1)), dtype=np.int32)
+    rc = lib().cfear_drift_segments(g.ctypes.data, len(g), out[0].ctypes.data, out[1].ctypes.data, out[2].ctypes.data, m.value, C.byref(m))
+    if rc != 0:
+        raise CfearError("cfear_drift_segments failed rc=%d" % rc)
+    return np.ascontiguousarray(out[:, :m.value].T)
 
 
 def default_params(**kw):
@@ -479,6 +520,14 @@ class Context:
         if self._h:
             self._L.cfear_host_free(self._h, ptr)
 
+    def drift_plan(self, gt):
+        """cfear_drift_plan_create: the segments of the ground truth gt ([n, 4, 4] poses) and what the KITTI drift needs of them, on the
+        device -> DriftPlan (score() evaluates batches of trajectories against it)"""
+        g = _gt34(gt)
+        h = C.c_void_p()
+        self._check(self._L.cfear_drift_plan_create(self._h, g.ctypes.data, len(g), C.byref(h)), "cfear_drift_plan_create")
+        return DriftPlan(self, h, len(g))
+
     def odometry(self, n_sequences, overlap=None, filter_cus=None, max_cells=None, reg_order=None, large_kernel=None):
         """overlap: None = the context's setting; 0 / False = the three kernels in turn on the context stream; n >= 1 = the filter one
         sweep ahead on a low-priority stream, features / registration of n ranges of the sequences on n high-priority streams.
@@ -563,6 +612,69 @@ class Scan:
         self._ctx._check(self._ctx._L.cfear_scan_closest(self._ctx._h, self._h, q.ctypes.data, q.shape[0], float(d),
                                                          idx.ctypes.data), "cfear_scan_closest")
         return idx
+
+
+class DriftPlan:
+    """cfear_drift_plan: one ground truth, ready to score batches of trajectories on the device (Context.drift_plan)"""
+
+    def __init__(self, ctx, h, n_gt):
+        self._ctx, self._h, self.n_gt = ctx, h, int(n_gt)
+
+    def release(self):
+        if self._h and self._ctx._h:
+            self._ctx._L.cfear_drift_plan_release(self._ctx._h, self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+    def score(self, poses, n_sweeps=None, n_sequences=None, sweep_stride=None, seq_stride=None, out=None):
+        """The KITTI drift of B trajectories -> structured array [B] of DRIFT_DTYPE. poses:
+        a numpy float64 array [n, B, 3] of (x, y, theta), or a numpy array [n, B] of SWEEP_RECORD_DTYPE (what replay_host returns): the
+        host route (cfear_drift_host; n_sweeps may shorten the trajectories);
+        a device tensor or address with n_sweeps, n_sequences and the two strides in bytes (cfear_drift_device; for a buffer of sweep
+        records 80 and n_sequences * 80, the defaults; 24 and n_sequences * 24 for packed poses). out: None - the results are copied to
+        the host after the context has been synchronised - or a device tensor / address of n_sequences * 184 bytes: the call only
+        queues the work on the context stream and returns None."""
+        c = self._ctx
+        if isinstance(poses, np.ndarray):
+            a = poses
+            if a.dtype != SWEEP_RECORD_DTYPE:
+                a = np.asarray(a, dtype=np.float64)
+                if a.ndim == 2:
+                    a = a[:, None, :]
+                if a.ndim != 3 or a.shape[2] != 3:
+                    raise ValueError("DriftPlan.score: poses are [n, B, 3] doubles or [n, B] sweep records")
+                a = np.ascontiguousarray(a)
+                n, B, seq = a.shape[0], a.shape[1], 24
+            else:
+                a = np.ascontiguousarray(a if a.ndim == 2 else a[:, None])
+                n, B, seq = a.shape[0], a.shape[1], SWEEP_RECORD_DTYPE.itemsize
+            n = n if n_sweeps is None else int(n_sweeps)
+            if n > a.shape[0]:
+                raise ValueError("DriftPlan.score: n_sweeps %d of %d poses" % (n, a.shape[0]))
+            if n_sequences is not None and int(n_sequences) != B:
+                raise ValueError("DriftPlan.score: n_sequences %d of %d trajectories" % (int(n_sequences), B))
+            res = np.zeros(B, dtype=DRIFT_DTYPE)
+            c._check(c._L.cfear_drift_host(c._h, self._h, a.ctypes.data, B * seq, seq, n, B, res.ctypes.data), "cfear_drift_host")
+            return res
+        if n_sweeps is None or n_sequences is None:
+            raise ValueError("DriftPlan.score: a device buffer needs n_sweeps and n_sequences")
+        B = int(n_sequences)
+        seq = SWEEP_RECORD_DTYPE.itemsize if seq_stride is None else int(seq_stride)
+        sweep = B * seq if sweep_stride is None else int(sweep_stride)
+        if out is not None:
+            c._check(c._L.cfear_drift_device(c._h, self._h, _addr(poses), sweep, seq, int(n_sweeps), B, _addr(out)), "cfear_drift_device")
+            return None
+        import torch
+        d_out = torch.empty(B * DRIFT_DTYPE.itemsize, dtype=torch.uint8, device="cuda:%d" % c.device)
+        torch.cuda.synchronize(d_out.device)  # (the allocator's stream may still use the memory; the context stream writes it)
+        c._check(c._L.cfear_drift_device(c._h, self._h, _addr(poses), sweep, seq, int(n_sweeps), B, d_out.data_ptr()), "cfear_drift_device")
+        c.synchronize()
+        return d_out.cpu().numpy().view(DRIFT_DTYPE).copy()
 
 
 class Odometry:

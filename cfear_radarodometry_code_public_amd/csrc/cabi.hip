@@ -109,6 +109,7 @@ void cfear_destroy(cfear_ctx* ctx) {
   if (ctx->d_slots) (void)hipFree(ctx->d_slots);
   if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
   if (ctx->d_cfar_rows) (void)hipFree(ctx->d_cfar_rows);
+  if (ctx->d_drift) (void)hipFree(ctx->d_drift);
   for (auto& b : ctx->pool) (void)hipFree(b.second);
   for (auto& b : ctx->hpool) (void)hipHostFree(b.second);
   if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);

@@ -73,12 +73,24 @@ def fuser_grid(base, base_options=None, **axes):
     return rows, options
 
 
-def replay_grid(frames, rows, A=None, R=None, gt=None, device=0, piece=256, context_params=None, options=None):
+def drift_dict(row):
+    """one result of capi.DriftPlan.score -> the dict kitti.drift_by_length returns"""
+    return {"translation_percent": float(row["translation_percent"]), "rotation_deg_per_100m": float(row["rotation_deg_per_100m"]),
+            "segments": int(row["segments"]),
+            "by_length": {"length_m": list(kitti.LENGTHS), "translation_percent": [float(v) for v in row["translation_percent_by_length"]],
+                          "rotation_deg_per_100m": [float(v) for v in row["rotation_deg_per_100m_by_length"]],
+                          "segments": [int(v) for v in row["segments_by_length"]]}}
+
+
+def replay_grid(frames, rows, A=None, R=None, gt=None, device=0, piece=256, context_params=None, options=None, drift_on="host"):
     """One recording under len(rows) parameter sets in one batched odometry object: frames uint8 [n, A, R], rows a list of capi.Params that
     agree in the object-wide fields (param_grid of one base does). The recording is the single source sweep of every sequence: it is
     copied and filtered once per sweep. options: a capi.FuserOptions for every row or a list of one per row (fuser_grid builds both
     lists); None: the fuser's defaults. -> dict(poses [n, len(rows), 3], records, drift: per row KITTI drift against gt ([n, 4, 4]
-    poses) or None)."""
+    poses) or None). drift_on: "host" - kitti.drift row by row; "device" - all rows in one cfear_drift_host call against a plan of
+    gt[:n] (capi.DriftPlan), each row's dict then also holds the per-length table as kitti.drift_by_length returns it."""
+    if drift_on not in ("host", "device"):
+        raise ValueError("replay_grid: drift_on is 'host' or 'device'")
     frames = np.ascontiguousarray(frames, dtype=np.uint8)
     n, A, R = frames.shape
     rows = list(rows)
@@ -96,13 +108,22 @@ def replay_grid(frames, rows, A=None, R=None, gt=None, device=0, piece=256, cont
             odo.set_fuser_options(opts)
         recs = [odo.replay_host(frames[t0:t0 + piece, None]) for t0 in range(0, n, piece)]
         rec = np.concatenate(recs, axis=0)
+        poses = np.array(rec["pose"])
+        scored = None
+        if gt is not None and drift_on == "device":
+            plan = ctx.drift_plan(np.asarray(gt)[:n])
+            try:
+                scored = plan.score(poses)
+            finally:
+                plan.release()
     finally:
         if odo is not None:
             odo.release()
         ctx.close()
-    poses = np.array(rec["pose"])
     drift = None
-    if gt is not None:
+    if scored is not None:
+        drift = [drift_dict(r) for r in scored]
+    elif gt is not None:
         drift = [kitti.drift(np.asarray(gt)[:n], kitti.poses_from_xyt(poses[:, q])) for q in range(len(rows))]
     return {"poses": poses, "records": rec, "drift": drift}
 

@@ -485,6 +485,50 @@ int cfear_odometry_replay_device_cov(cfear_ctx* ctx, cfear_odometry* odo, const 
 int cfear_host_alloc(cfear_ctx* ctx, size_t bytes, void** out);
 void cfear_host_free(cfear_ctx* ctx, void* p);
 
+/* ---- KITTI drift of a batch's trajectories on the device: the metric of include/cfear_hip/kitti_metric.hpp (kitti_drift,
+ * kitti_drift_by_length; what the reference's evaluation worker computes per job, launch/oxford/eval/utils/worker:94-98) for every
+ * sequence of a batch at once. Segments: a start every 10 poses, lengths 100 ... 800 m, `last` = the first pose whose cumulative 3-D
+ * path length exceeds dist[first] + len; per segment e = des^-1 * dgt with dgt = gt[first]^-1 * gt[last] (general inverse: 6-decimal
+ * text poses are not exactly orthonormal) and des the same for the planar estimate (x, y, theta); r = acos(clamp(0.5 (trace(e_R) - 1))),
+ * t = |e_t|, the segment contributes r / len and t / len. The totals are the means over all segments, the by-length tables the same
+ * means over the segments of one length (0 for a length without a segment, as the totals are 0 without any). A non-finite pose makes
+ * the totals of ITS row NaN, and the by-length entries of the lengths it touches, exactly as the host metric (its clamp keeps a NaN);
+ * no other row changes. */
+typedef struct cfear_drift {                 /* 184 bytes */
+  double  translation_percent;
+  double  rotation_deg_per_100m;
+  double  translation_percent_by_length[8];   /* 100, 200 ... 800 m */
+  double  rotation_deg_per_100m_by_length[8];
+  int32_t segments;
+  int32_t segments_by_length[8];
+  int32_t reserved;                           /* 0 */
+} cfear_drift;
+typedef struct cfear_drift_plan cfear_drift_plan; /* the segments of one ground truth and their dgt, device resident */
+
+/* The segment list of kitti_drift for n_gt ground-truth poses (gt34: 3x4 row-major, 12 doubles per pose), in its order: start-major,
+ * then length; length_index 0..7 = 100 ... 800 m. Host only (no context, no device). At most `capacity` segments are written (the arrays
+ * may be NULL with capacity 0); *n_segments is the number there are, and the return value CFEAR_ERR_CAPACITY if that is more than
+ * `capacity`. CFEAR_ERR_INVALID for a null gt34 / n_segments, n_gt < 1 or a non-finite entry. */
+int cfear_drift_segments(const double* gt34, int n_gt, int32_t* first, int32_t* last, int32_t* length_index, int capacity, int* n_segments);
+/* The plan of one ground truth: its segment table, dgt and 1 / len per segment on the device. The segments of a replay of
+ * n < n_gt sweeps are exactly the plan's segments with last < n (dist is a prefix sum, last a first crossing), so one plan scores any
+ * shorter replay. CFEAR_ERR_INVALID (the message names the argument) for a null pointer, n_gt < 1 or a non-finite entry. Synchronous. */
+int cfear_drift_plan_create(cfear_ctx* ctx, const double* gt34, int n_gt, cfear_drift_plan** plan);
+void cfear_drift_plan_release(cfear_ctx* ctx, cfear_drift_plan* plan);
+/* Scores n_sequences trajectories of n_sweeps poses against the plan over n = min(n_sweeps, n_gt) poses (n < 2 or no fitting segment:
+ * zeros). The pose of sweep t of sequence q is the 3 doubles (x, y, theta) at d_poses + t * sweep_stride + q * seq_stride (bytes): for a
+ * buffer of cfear_sweep_record as cfear_odometry_replay_device fills it, seq_stride = sizeof(cfear_sweep_record) and sweep_stride =
+ * n_sequences * sizeof(cfear_sweep_record); packed poses have 24 and n_sequences * 24. d_out: n_sequences results in device memory. The
+ * input is only read. Asynchronous on the context stream - behind a preceding cfear_odometry_replay_device with no synchronisation in
+ * between. A row's result is a function of the plan, n_sweeps and that row's poses alone: bit-identical whatever the batch around it,
+ * the strides, or the call. CFEAR_ERR_INVALID (the message names the argument) for a null pointer, a d_poses or a stride that is not a
+ * multiple of 8, seq_stride < 24, n_sequences < 1 or n_sweeps < 0. */
+int cfear_drift_device(cfear_ctx* ctx, const cfear_drift_plan* plan, const void* d_poses, size_t sweep_stride, size_t seq_stride,
+                       int n_sweeps, int n_sequences, cfear_drift* d_out);
+/* The same from / to host memory (stages through the context; synchronises). */
+int cfear_drift_host(cfear_ctx* ctx, const cfear_drift_plan* plan, const void* h_poses, size_t sweep_stride, size_t seq_stride,
+                     int n_sweeps, int n_sequences, cfear_drift* h_out);
+
 /* Filter-kernel timing with HIP events (bench.py roofline leg): enable, run steps, read. filter_seconds is the sum
  * of the durations of the filter launches, each measured on the stream it ran on. The events come from a pool created
  * when profiling is enabled (and grown in blocks), not one hipEventCreate per launch. */
