@@ -94,7 +94,7 @@ int cfear_create(cfear_ctx** out, int device, void* stream, const cfear_params* 
     trig[2 * b] = cos(theta);
     trig[2 * b + 1] = sin(theta);
   }
-  if (hipMalloc(&ctx->d_trig, trig.size() * sizeof(double)) != hipSuccess) { cfear_destroy(ctx); return CFEAR_ERR_NOMEM; }
+  if (ctx->d_trig.ensure(ctx, trig.size(), "hipMalloc trig table") != CFEAR_OK) { cfear_destroy(ctx); return CFEAR_ERR_NOMEM; }
   if (hipMemcpy(ctx->d_trig, trig.data(), trig.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) { cfear_destroy(ctx); return CFEAR_ERR_HIP; }
   *out = ctx;
   return CFEAR_OK;
@@ -104,12 +104,6 @@ void cfear_destroy(cfear_ctx* ctx) {
   if (!ctx) return;
   (void)hipSetDevice(ctx->device);
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-  if (ctx->d_trig) (void)hipFree(ctx->d_trig);
-  if (ctx->d_polar) (void)hipFree(ctx->d_polar);
-  if (ctx->d_slots) (void)hipFree(ctx->d_slots);
-  if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
-  if (ctx->d_cfar_rows) (void)hipFree(ctx->d_cfar_rows);
-  if (ctx->d_drift) (void)hipFree(ctx->d_drift);
   for (auto& b : ctx->pool) (void)hipFree(b.second);
   for (auto& b : ctx->hpool) (void)hipHostFree(b.second);
   if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
@@ -118,7 +112,7 @@ void cfear_destroy(cfear_ctx* ctx) {
   if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
   if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
   if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
-  delete ctx;
+  delete ctx;  // (and with it the device buffers it owns)
 }
 
 const char* cfear_last_error(const cfear_ctx* ctx) { return ctx ? ctx->err.c_str() : "null context"; }
@@ -256,21 +250,8 @@ int cfear_upload_image(cfear_ctx* ctx, void* d_dst, const void* h_src, size_t by
 }
 
 int cfear_ensure_staging(cfear_ctx* ctx, int n_scans) {
-  const size_t pb = (size_t)n_scans * ctx->A * ctx->R + 64;
-  const size_t sb = (size_t)n_scans * ctx->A * ctx->par.k_strongest * sizeof(uint32_t);
-  if (pb > ctx->d_polar_bytes) {
-    if (ctx->d_polar) (void)hipFree(ctx->d_polar);
-    ctx->d_polar = nullptr; ctx->d_polar_bytes = 0;
-    if (hipMalloc(&ctx->d_polar, pb) != hipSuccess) return cfear_fail(ctx, CFEAR_ERR_NOMEM, "hipMalloc polar staging");
-    ctx->d_polar_bytes = pb;
-  }
-  if (sb > ctx->d_slots_bytes) {
-    if (ctx->d_slots) (void)hipFree(ctx->d_slots);
-    ctx->d_slots = nullptr; ctx->d_slots_bytes = 0;
-    if (hipMalloc(&ctx->d_slots, sb) != hipSuccess) return cfear_fail(ctx, CFEAR_ERR_NOMEM, "hipMalloc slot staging");
-    ctx->d_slots_bytes = sb;
-  }
-  return CFEAR_OK;
+  CFEAR_TRY(ctx->d_polar.ensure(ctx, (size_t)n_scans * ctx->A * ctx->R + 64, "hipMalloc polar staging"));
+  return ctx->d_slots.ensure(ctx, (size_t)n_scans * ctx->A * ctx->par.k_strongest, "hipMalloc slot staging");
 }
 
 int cfear_kstrongest_host(cfear_ctx* ctx, const uint8_t* h_polar, int n_scans, uint32_t* h_slots) {

@@ -1036,11 +1036,9 @@ int cfear_filter_cfar_batch_device(cfear_ctx* ctx, const uint8_t* d_polar, int n
   if ((long long)n_scans * ctx->A > 0x7FFFFFFFLL) return cfear_fail(ctx, CFEAR_ERR_UNSUPPORTED, "filter_cfar_batch: too many rows");
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   const size_t need = cfear_cfar_scratch_ints(ctx, (size_t)n_scans);
-  if (need > ctx->cfar_rows_cap) {  // row counts, row bases and hit masks of the whole batch
-    if (ctx->d_cfar_rows) { CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream)); (void)hipFree(ctx->d_cfar_rows); }
-    ctx->d_cfar_rows = nullptr; ctx->cfar_rows_cap = 0;
-    if (hipMalloc(&ctx->d_cfar_rows, sizeof(int) * need) != hipSuccess) return cfear_fail(ctx, CFEAR_ERR_NOMEM, "hipMalloc cfar rows");
-    ctx->cfar_rows_cap = need;
+  if (need > ctx->d_cfar_rows.size()) {  // row counts, row bases and hit masks of the whole batch
+    if (ctx->d_cfar_rows) CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    CFEAR_TRY(ctx->d_cfar_rows.ensure(ctx, need, "hipMalloc cfar rows"));
   }
   return cfear_launch_cfar_batch(ctx, d_polar, n_scans, window_size, nb_guard_cells, false_alarm_rate, max_distance, d_xyi, capacity, d_counts,
                                  ctx->d_cfar_rows, ctx->stream);

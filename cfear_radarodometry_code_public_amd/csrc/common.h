@@ -12,6 +12,45 @@
 
 #define CFEAR_WAVE 64
 
+struct cfear_ctx;
+static inline int cfear_fail(cfear_ctx* c, int code, const char* what, hipError_t e = hipSuccess);
+
+// The owner of one hipMalloc allocation of size() elements: everything an object or the context keeps on the device (the blocks of clouds and
+// scans come from the context's pool instead, see below). It frees when it is released, grown or destroyed, and hipFree waits for the whole
+// device - but when a buffer MAY go is the caller's to know: it drains the streams that can still read the buffer first.
+template <typename T>
+class DevBuf {
+ public:
+  DevBuf() = default;
+  DevBuf(DevBuf&& b) noexcept : p_(b.p_), n_(b.n_) { b.p_ = nullptr; b.n_ = 0; }
+  DevBuf& operator=(DevBuf&& b) noexcept {
+    if (this != &b) { release(); p_ = b.p_; n_ = b.n_; b.p_ = nullptr; b.n_ = 0; }
+    return *this;
+  }
+  ~DevBuf() { release(); }
+  operator T*() const { return p_; }
+  size_t size() const { return n_; }
+  void release() {
+    if (p_) (void)hipFree(p_);
+    p_ = nullptr; n_ = 0;
+  }
+  // room for `count` elements: nothing to do when they fit, a new (with `zero`: zero-filled) allocation otherwise - the old contents are gone.
+  // A failure leaves the buffer empty and is reported as `what`.
+  int ensure(cfear_ctx* ctx, size_t count, const char* what, bool zero = false) {
+    if (count <= n_) return CFEAR_OK;
+    release();
+    if (hipMalloc(&p_, sizeof(T) * count) != hipSuccess) { p_ = nullptr; return cfear_fail(ctx, CFEAR_ERR_NOMEM, what); }
+    n_ = count;
+    const hipError_t e = zero ? hipMemset(p_, 0, sizeof(T) * count) : hipSuccess;
+    if (e != hipSuccess) { release(); return cfear_fail(ctx, CFEAR_ERR_HIP, what, e); }
+    return CFEAR_OK;
+  }
+
+ private:
+  T* p_ = nullptr;
+  size_t n_ = 0;
+};
+
 struct cfear_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -21,20 +60,14 @@ struct cfear_ctx {
   std::string err;
   // per-azimuth (cos, sin) of theta=(b+1)/A*2pi computed on the host with libm so that the
   // polar->Cartesian conversion (radar_filters.cpp:317-330) is bit-identical to a CPU run.
-  double* d_trig = nullptr;  // [A][2]
-  // staging for the host entry points
-  uint8_t* d_polar = nullptr;
-  size_t d_polar_bytes = 0;
-  uint32_t* d_slots = nullptr;
-  size_t d_slots_bytes = 0;
+  DevBuf<double> d_trig;  // [A][2]
+  // staging for the host entry points (these and the three below grow and never shrink)
+  DevBuf<uint8_t> d_polar;
+  DevBuf<uint32_t> d_slots;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  // scratch for the per-call feature / registration kernels
-  void* d_scratch = nullptr;
-  size_t scratch_bytes = 0;
-  int* d_cfar_rows = nullptr;  // row counts / bases of cfear_filter_cfar_batch_device
-  size_t cfar_rows_cap = 0;
-  double* d_drift = nullptr;  // per-block partial sums of cfear_drift_device (drift.hip); grows, never shrinks
-  size_t drift_bytes = 0;
+  DevBuf<unsigned char> d_scratch;  // scratch for the per-call feature / registration kernels
+  DevBuf<int> d_cfar_rows;          // row counts / bases of cfear_filter_cfar_batch_device
+  DevBuf<double> d_drift;           // per-block partial sums of cfear_drift_device (drift.hip)
   // streams of the batched odometry objects of this context (cfear_synchronize waits for them too)
   std::vector<hipStream_t> aux_streams;
   // launch-shape knobs (cfear_tune): filter occupancy variant (5..7 waves per SIMD), rows walked per filter wave,
@@ -66,7 +99,7 @@ struct cfear_ctx {
   bool ev_img_pending = false;
 };
 
-static inline int cfear_fail(cfear_ctx* c, int code, const char* what, hipError_t e = hipSuccess) {
+static inline int cfear_fail(cfear_ctx* c, int code, const char* what, hipError_t e) {
   if (c) {
     char buf[512];
     if (e != hipSuccess)

@@ -140,8 +140,8 @@ std::vector<cfear_host::KittiSegment> segments_of(const double* gt34, int n_gt) 
 
 struct cfear_drift_plan {
   int n_gt = 0, n_segments = 0, n_starts = 0;  // n_starts: starts with a segment (a prefix of 0, 10, 20, ...)
-  DriftSeg* d_segs = nullptr;
-  int32_t* d_start_seg = nullptr;              // [n_starts + 1] first table entry of a start
+  DevBuf<DriftSeg> d_segs;
+  DevBuf<int32_t> d_start_seg;                 // [n_starts + 1] first table entry of a start
   std::vector<int32_t> last_of[NLEN];          // per length: `last` of its segments, ascending with the start
 };
 
@@ -158,13 +158,8 @@ int launch_drift(cfear_ctx* ctx, const cfear_drift_plan* plan, const void* d_pos
   const int n_chunks = (n_starts + CHUNK_STARTS - 1) / CHUNK_STARTS;
   if (n_chunks > MAX_CHUNKS) return cfear_fail(ctx, CFEAR_ERR_UNSUPPORTED, "drift: more than 5242800 ground-truth poses");
   const int tiles = (n_sequences + TILE - 1) / TILE;
-  const size_t need = sizeof(double) * 2 * NLEN * (size_t)n_sequences * (size_t)std::max(n_chunks, 1);
-  if (need > ctx->drift_bytes) {
-    if (ctx->d_drift) (void)hipFree(ctx->d_drift);  // (waits for the launches that use it)
-    ctx->d_drift = nullptr; ctx->drift_bytes = 0;
-    if (hipMalloc(reinterpret_cast<void**>(&ctx->d_drift), need) != hipSuccess) return cfear_fail(ctx, CFEAR_ERR_NOMEM, "hipMalloc drift scratch");
-    ctx->drift_bytes = need;
-  }
+  // (growing frees the old block, which waits for the launches that use it)
+  CFEAR_TRY(ctx->d_drift.ensure(ctx, 2 * NLEN * (size_t)n_sequences * (size_t)std::max(n_chunks, 1), "hipMalloc drift scratch"));
   if (n_chunks > 0)
     hipLaunchKernelGGL(drift_partial_kernel, dim3(tiles, n_chunks), dim3(TILE), 0, ctx->stream, plan->d_segs, plan->d_start_seg,
                        static_cast<const unsigned char*>(d_poses), sweep_stride, seq_stride, n, n_sequences, n_starts, ctx->d_drift);
@@ -238,10 +233,9 @@ int cfear_drift_plan_create(cfear_ctx* ctx, const double* gt34, int n_gt, cfear_
   for (int s = 0; s < p->n_starts && regular; s++)
     for (int i = start_seg[s]; i < start_seg[s + 1]; i++) regular = regular && segs[i].first == s * cfear_host::kKittiStep && segs[i].length_index == i - start_seg[s];
   if (!regular) { delete p; return cfear_fail(ctx, CFEAR_ERR_UNSUPPORTED, "drift_plan_create: irregular segment table"); }
-  const size_t tb = sizeof(DriftSeg) * std::max<size_t>(table.size(), 1), sb = sizeof(int32_t) * start_seg.size();
-  bool ok = hipMalloc(reinterpret_cast<void**>(&p->d_segs), tb) == hipSuccess && hipMalloc(reinterpret_cast<void**>(&p->d_start_seg), sb) == hipSuccess;
+  bool ok = p->d_segs.ensure(ctx, std::max<size_t>(table.size(), 1), "") == CFEAR_OK && p->d_start_seg.ensure(ctx, start_seg.size(), "") == CFEAR_OK;
   ok = ok && (table.empty() || hipMemcpy(p->d_segs, table.data(), sizeof(DriftSeg) * table.size(), hipMemcpyHostToDevice) == hipSuccess);
-  ok = ok && hipMemcpy(p->d_start_seg, start_seg.data(), sb, hipMemcpyHostToDevice) == hipSuccess;
+  ok = ok && hipMemcpy(p->d_start_seg, start_seg.data(), sizeof(int32_t) * start_seg.size(), hipMemcpyHostToDevice) == hipSuccess;
   if (!ok) { cfear_drift_plan_release(ctx, p); return cfear_fail(ctx, CFEAR_ERR_NOMEM, "drift_plan_create: device memory"); }
   *plan = p;
   return CFEAR_OK;
@@ -250,8 +244,6 @@ int cfear_drift_plan_create(cfear_ctx* ctx, const double* gt34, int n_gt, cfear_
 void cfear_drift_plan_release(cfear_ctx* ctx, cfear_drift_plan* plan) {
   if (!plan) return;
   if (ctx) { (void)hipSetDevice(ctx->device); (void)hipStreamSynchronize(ctx->stream); }  // a queued scoring may still read the table
-  if (plan->d_segs) (void)hipFree(plan->d_segs);
-  if (plan->d_start_seg) (void)hipFree(plan->d_start_seg);
   delete plan;
 }
 

@@ -450,43 +450,42 @@ static int check_tie_rule_scans(cfear_ctx* ctx, cfear_scan* const* scans, int n,
 }
 struct cfear_odometry {
   int B = 0, nslots = 0, cap_points = 0, cap_cells = 0, pair_cap = 0;
-  int* d_order = nullptr; unsigned* d_work = nullptr;  // registration workgroups longest first (cfear_tune REGISTRATION_ORDER): see order_kernel
+  DevBuf<int> d_order; DevBuf<unsigned> d_work;  // registration workgroups longest first (cfear_tune REGISTRATION_ORDER): see order_kernel
   bool order_ready = false;  // d_work holds the keys of a registration launch
   bool with_kd = false;  // the scans carry FLANN kd-tree arrays (cfear_tune NN_TIE_RULE = 2 at creation)
   int large_kernel = 0, n_cus = 256;  // cfear_tune LARGE_SUBMAP_KERNEL at creation; compute units of the device
-  int* d_flags = nullptr;  // bit 0: a scan had more cells than cap_cells, bit 1: a cloud had more points than cap_points (only allocated when either can happen)
-  unsigned char* d_scans = nullptr;    // B * nslots flat scan blocks
+  DevBuf<int> d_flags;  // bit 0: a scan had more cells than cap_cells, bit 1: a cloud had more points than cap_points (only allocated when either can happen)
+  DevBuf<unsigned char> d_scans;       // B * nslots flat scan blocks
   size_t scan_stride = 0;              // bytes between consecutive scan slots of d_scans
-  unsigned char* d_scratch = nullptr;  // B scratch blocks
-  BlockScratch* d_scratch_hdr = nullptr;
-  SeqState* d_states = nullptr;
-  double* d_cov_work = nullptr;
-  cfear_reg_summary* d_summaries = nullptr;
-  double* d_poses_out = nullptr;
-  uint32_t* d_slots[2] = {nullptr, nullptr};  // filter output, double-buffered: the filter runs one sweep ahead
-  uint8_t* d_polar = nullptr;  // staging for step_host
+  DevBuf<unsigned char> d_scratch;     // B scratch blocks
+  DevBuf<BlockScratch> d_scratch_hdr;
+  DevBuf<SeqState> d_states;
+  DevBuf<double> d_cov_work;
+  DevBuf<cfear_reg_summary> d_summaries;
+  DevBuf<double> d_poses_out;
+  DevBuf<uint32_t> d_slots[2];  // filter output, double-buffered: the filter runs one sweep ahead
+  DevBuf<uint8_t> d_polar;  // staging for step_host
   // filter_type CA-CFAR (radar_driver.cpp:52-56): the filter's output is a cloud per sequence instead of A * k slots
   int filter = CFEAR_FILTER_KSTRONG;
-  float* d_cloud = nullptr;      // [B][cap_points][3]
-  int* d_cloud_n = nullptr;      // [B] detections per sequence (may exceed cap_points: the cloud keeps the first cap_points)
-  int* d_cfar_rows = nullptr;    // row counts / row bases / hit masks of one sweep (cfear_cfar_scratch_ints)
-  float* rp_cloud[2] = {nullptr, nullptr};  // replay: clouds of a chunk of sweeps, double-buffered like rp_slots
-  int* rp_cloud_n[2] = {nullptr, nullptr};
-  int* rp_cfar_rows = nullptr;   // ... of a chunk (the replay stream runs one filter at a time)
+  DevBuf<float> d_cloud;         // [B][cap_points][3]
+  DevBuf<int> d_cloud_n;         // [B] detections per sequence (may exceed cap_points: the cloud keeps the first cap_points)
+  DevBuf<int> d_cfar_rows;       // row counts / row bases / hit masks of one sweep (cfear_cfar_scratch_ints)
+  DevBuf<float> rp_cloud[2];     // replay: clouds of a chunk of sweeps, double-buffered like rp_slots
+  DevBuf<int> rp_cloud_n[2];
+  DevBuf<int> rp_cfar_rows;      // ... of a chunk (the replay stream runs one filter at a time)
   // cfear_odometry_replay_host: chunks of sweeps are copied and filtered on a stream of their own (rp_stream), two chunks
   // in flight (staging + slots double-buffered), while the context stream runs features -> registration sweep after sweep
   hipStream_t rp_stream = nullptr;
-  uint8_t* rp_polar[2] = {nullptr, nullptr};
-  uint32_t* rp_slots[2] = {nullptr, nullptr};
+  DevBuf<uint8_t> rp_polar[2];
+  DevBuf<uint32_t> rp_slots[2];
   hipEvent_t rp_filt[2] = {nullptr, nullptr}, rp_used[2] = {nullptr, nullptr};  // chunk filtered / chunk consumed by the odometry kernels
   hipEvent_t rp_in = nullptr;  // device-resident frames ready on the context stream
   bool rp_used_pending[2] = {false, false};
   bool rp_ready = false;       // stream + events exist
   int rp_chunk = 0;            // sweeps per chunk the slot buffers are sized for
   int rp_polar_chunk = 0;      // ... and the staging buffers (allocated on the first replay from host memory only)
-  cfear_sweep_record* d_records = nullptr;
-  size_t records_cap = 0;      // records
-  long long* d_phase_times = nullptr;  // optional [B][32] (cfear_odometry_phase_times)
+  DevBuf<cfear_sweep_record> d_records;
+  DevBuf<long long> d_phase_times;  // optional [B][32] (cfear_odometry_phase_times)
   int phase_detail = 1;
   bool wg_only = false;  // the table only receives the workgroups' start / end clocks, from the production kernels
   // The filter of a sweep needs nothing but its input, and it is bound by HBM while features / registration are chains
@@ -517,27 +516,25 @@ struct cfear_odometry {
   std::vector<hipEvent_t> stage_events;   // 3 per profiled step: before features, between, after registration
   // estimate_cov_by_sampling (cfear_odometry_set_cov_sampling): the sampling stage runs after every registration while cov_on
   bool cov_on = false;
-  int cov_m = 0, cov_m_cap = 0;           // samples per sweep (samples_per_axis^3); what d_cov_design / d_cov_costs are sized for
+  int cov_m = 0;                          // samples per sweep (samples_per_axis^3)
   double cov_scaler = 4.0;
-  CovSampleCtx* d_cov_ctx = nullptr;      // [B] what each registration used (register_step_body)
-  double* d_cov_design = nullptr;         // [10][m] pseudo-inverse of the sample design, then [m][3] sample offsets
-  double* d_cov_costs = nullptr;          // [B][m] sampled costs of the last sweep
-  double* d_cov_seq = nullptr;            // cfear_odometry_replay_host_cov: cov_current of every sweep ([n][B][36])
-  size_t cov_seq_cap = 0;
+  DevBuf<CovSampleCtx> d_cov_ctx;         // [B] what each registration used (register_step_body)
+  DevBuf<double> d_cov_design;            // [10][m] pseudo-inverse of the sample design, then [m][3] sample offsets
+  DevBuf<double> d_cov_costs;             // [B][m] sampled costs of the last sweep
+  DevBuf<double> d_cov_seq;               // cfear_odometry_replay_host_cov: cov_current of every sweep ([n][B][36])
   // cost surfaces (cfear_odometry_set_surface_recording / cfear_odometry_surface): the registration records what it used in d_cov_ctx
   // (as for the sampling stage, which does not run unless cov_on)
   bool surf_on = false;
   bool surf_ready = false;  // d_cov_ctx holds the last step's registrations (a step ran with recording since the last reset / replay)
-  SurfHdr* d_surf_hdr = nullptr;     // [B]
-  double* d_surf_coords = nullptr;   // [B][2][pixels]
-  int* d_surf_nxy = nullptr;         // [B][2]
-  int surf_px_cap = 0;               // pixels per side d_surf_coords is sized for
+  DevBuf<SurfHdr> d_surf_hdr;        // [B]
+  DevBuf<double> d_surf_coords;      // [B][2][pixels]
+  DevBuf<int> d_surf_nxy;            // [B][2]
   // per-sequence parameters / shared input sweeps (cfear_odometry_set_sequence_params / _set_sequence_sources)
   std::vector<cfear_params> seq_rows;  // [B] the caller's table; empty: every sequence runs with the context's parameters
   std::vector<int32_t> seq_src;        // [B] the sweep each sequence reads; empty: sweep q for sequence q
   int n_sources = 0;                   // sweeps per step with a source map (0: B)
   std::vector<cfear_fuser_options> fuser_opts;  // [B] cfear_odometry_set_fuser_options; empty: the defaults (no prior, constant-velocity guess)
-  SeqParams* d_seq = nullptr;          // [B] what the kernels read (OdoParams::seq); exists while any of the above does
+  DevBuf<SeqParams> d_seq;             // [B] what the kernels read (OdoParams::seq); exists while any of the above does
   cfear_params seq_par_seen;           // the context's parameters d_seq was built and the rows were checked against
   int seq_zmin = -1;                   // the filter's threshold: the smallest z_min of the rows (-1: the context's)
   long long sweeps = 0;                // sweeps processed since cfear_odometry_create / cfear_odometry_reset
@@ -657,8 +654,7 @@ static int seq_rows_check(cfear_ctx* ctx, const cfear_odometry* o, const cfear_p
 // stream and the object's streams are idle when this is called.
 static int seq_table_upload(cfear_ctx* ctx, cfear_odometry* o) {
   if (o->seq_rows.empty() && o->seq_src.empty() && o->fuser_opts.empty()) {
-    if (o->d_seq) (void)hipFree(o->d_seq);
-    o->d_seq = nullptr; o->seq_zmin = -1;
+    o->d_seq.release(); o->seq_zmin = -1;
     return CFEAR_OK;
   }
   std::vector<SeqParams> t((size_t)o->B);
@@ -668,7 +664,7 @@ static int seq_table_upload(cfear_ctx* ctx, cfear_odometry* o) {
     zmin = std::min(zmin, t[q].z_min);
     if (!o->fuser_opts.empty()) t[q].fuser = (o->fuser_opts[q].soft_constraint ? SEQ_FUSER_SOFT : 0) | (o->fuser_opts[q].use_guess ? 0 : SEQ_FUSER_NO_GUESS);
   }
-  if (!o->d_seq && hipMalloc(&o->d_seq, sizeof(SeqParams) * (size_t)o->B) != hipSuccess) return cfear_fail(ctx, CFEAR_ERR_NOMEM, "hipMalloc sequence parameter table");
+  CFEAR_TRY(o->d_seq.ensure(ctx, t.size(), "hipMalloc sequence parameter table"));
   CFEAR_HIP_CHECK(ctx, hipMemcpy(o->d_seq, t.data(), sizeof(SeqParams) * t.size(), hipMemcpyHostToDevice));
   o->seq_zmin = o->seq_rows.empty() ? -1 : zmin;
   o->seq_par_seen = ctx->par;
@@ -783,14 +779,8 @@ static int ensure_ctx_scratch(cfear_ctx* ctx, int cap_points, BlockScratch* B, C
   const ScratchLayout L = scratch_layout(cap_points, pair_cap);
   const size_t tc_hdr = align_up(L.total + sizeof(CallTail), 256), tc_view = align_up(tc_hdr + sizeof(ScanDev), 256);
   const size_t need = tc_view + sizeof(double) * 8 * (size_t)cap_points + 4096;  // (and some headroom)
-  if (need > ctx->scratch_bytes) {
-    if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
-    ctx->d_scratch = nullptr; ctx->scratch_bytes = 0;
-    if (hipMalloc(&ctx->d_scratch, need) != hipSuccess) return cfear_fail(ctx, CFEAR_ERR_NOMEM, "hipMalloc context scratch");
-    if (hipMemset(ctx->d_scratch, 0, need) != hipSuccess) return cfear_fail(ctx, CFEAR_ERR_HIP, "hipMemset context scratch");  // dense voxel table starts all-zero
-    ctx->scratch_bytes = need;
-  }
-  unsigned char* base = static_cast<unsigned char*>(ctx->d_scratch);
+  CFEAR_TRY(ctx->d_scratch.ensure(ctx, need, "hipMalloc context scratch", true));  // dense voxel table starts all-zero
+  unsigned char* base = ctx->d_scratch;
   *B = scratch_header(base, cap_points, pair_cap);
   if (tail) *tail = reinterpret_cast<CallTail*>(base + L.total);
   if (tc) { tc->hdr = reinterpret_cast<ScanDev*>(base + tc_hdr); tc->view = reinterpret_cast<double*>(base + tc_view); tc->view_cells = cap_points; }
@@ -984,8 +974,7 @@ struct cloud_point_index_idx {
   unsigned int idx, cloud_point_index;
   bool operator<(const cloud_point_index_idx& p) const { return idx < p.idx; }
 };
-int voxel_order_stdsort(cfear_ctx* ctx, const cfear_cloud* cloud, int cap_points, int** d_out /* [2][n]: rank, perm */) {
-  *d_out = nullptr;
+int voxel_order_stdsort(cfear_ctx* ctx, const cfear_cloud* cloud, int cap_points, DevBuf<int>* d_out /* [2][n]: rank, perm; empty for an empty cloud */) {
   int n = 0;
   CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(&n, cloud->d_n, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
   CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
@@ -1010,12 +999,12 @@ int voxel_order_stdsort(cfear_ctx* ctx, const cfear_cloud* cloud, int cap_points
   std::sort(v.begin(), v.end(), std::less<cloud_point_index_idx>());
   std::vector<int> rp(2 * (size_t)n);
   for (int r = 0; r < n; r++) { rp[(size_t)v[(size_t)r].cloud_point_index] = r; rp[(size_t)n + r] = (int)v[(size_t)r].cloud_point_index; }
-  int* d = nullptr;
-  if (hipMalloc(&d, sizeof(int) * rp.size()) != hipSuccess) return cfear_fail(ctx, CFEAR_ERR_NOMEM, "hipMalloc voxel order");
+  DevBuf<int> d;
+  CFEAR_TRY(d.ensure(ctx, rp.size(), "hipMalloc voxel order"));
   hipError_t e = hipMemcpyAsync(d, rp.data(), sizeof(int) * rp.size(), hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // (rp is a local)
-  if (e != hipSuccess) { (void)hipFree(d); return cfear_fail(ctx, CFEAR_ERR_HIP, "voxel order upload", e); }
-  *d_out = d;
+  if (e != hipSuccess) return cfear_fail(ctx, CFEAR_ERR_HIP, "voxel order upload", e);
+  *d_out = std::move(d);
   return n;
 }
 }  // namespace
@@ -1036,7 +1025,7 @@ int cfear_scan_create(cfear_ctx* ctx, const cfear_cloud* cloud, cfear_scan** sca
   { void* blk = nullptr; rc = cfear_pool_alloc(ctx, L.total, &blk, &s->bytes); if (rc != CFEAR_OK) { delete s; return rc; } s->d_block = static_cast<unsigned char*>(blk); }
   const ScanDev h = scan_header(s->d_block, cap, cap, true, ctx->tune_nn_tie == 2);
   ScanDev back;
-  int* d_vorder = nullptr;
+  DevBuf<int> d_vorder;  // (freed on every way out, each of them behind the synchronisation below)
   // the header goes in and comes back through the context's pinned staging (from / to the stack the two small copies are pageable: the runtime
   // stages and waits for each - on the per-sweep route two of the ~15 host round trips of a sweep)
   constexpr size_t HS = (sizeof(ScanDev) + 63) & ~(size_t)63;
@@ -1059,7 +1048,6 @@ int cfear_scan_create(cfear_ctx* ctx, const cfear_cloud* cloud, cfear_scan** sca
   if (e == hipSuccess) e = hipMemcpyAsync(ctx->h_stage + HS, s->d_block, sizeof(back), hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
   if (e == hipSuccess) memcpy(&back, ctx->h_stage + HS, sizeof(back));
-  if (d_vorder) (void)hipFree(d_vorder);
   if (e != hipSuccess) {
     cfear_pool_free(ctx, s->d_block, s->bytes);
     delete s;
@@ -1144,16 +1132,15 @@ int cfear_scan_closest(cfear_ctx* ctx, const cfear_scan* s, const double* qxy, i
   if (!ctx || !s || !qxy || !idx || nq <= 0) return cfear_fail(ctx, CFEAR_ERR_INVALID, "scan_closest: bad argument");
   { cfear_scan* one = const_cast<cfear_scan*>(s); const int trc = check_tie_rule_scans(ctx, &one, 1, "scan_closest"); if (trc != CFEAR_OK) return trc; }
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  double* dq = nullptr; int* di = nullptr;
-  if (hipMalloc(&dq, sizeof(double) * 2 * (size_t)nq) != hipSuccess) return cfear_fail(ctx, CFEAR_ERR_NOMEM, "hipMalloc queries");
-  if (hipMalloc(&di, sizeof(int) * (size_t)nq) != hipSuccess) { (void)hipFree(dq); return cfear_fail(ctx, CFEAR_ERR_NOMEM, "hipMalloc idx"); }
+  DevBuf<double> dq; DevBuf<int> di;
+  CFEAR_TRY(dq.ensure(ctx, 2 * (size_t)nq, "hipMalloc queries"));
+  CFEAR_TRY(di.ensure(ctx, (size_t)nq, "hipMalloc idx"));
   hipError_t e = hipMemcpyAsync(dq, qxy, sizeof(double) * 2 * (size_t)nq, hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess) {
     hipLaunchKernelGGL(closest_kernel, dim3((nq + 255) / 256), dim3(256), 0, ctx->stream, reinterpret_cast<const ScanDev*>(s->d_block), dq, nq, d, di, ctx->tune_nn_tie);
     e = hipMemcpyAsync(idx, di, sizeof(int) * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream);
   }
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  (void)hipFree(dq); (void)hipFree(di);
   if (e != hipSuccess) return cfear_fail(ctx, CFEAR_ERR_HIP, "scan_closest", e);
   return CFEAR_OK;
 }
@@ -1238,8 +1225,8 @@ int cfear_get_cost(cfear_ctx* ctx, cfear_scan* const* scans, int n, const double
   double* d_score = pb.d->cov;
   int* d_nres = reinterpret_cast<int*>(d_score + 1);
   ScanDev** d_ptrs = pb.d->ptrs;
-  double* d_res = nullptr;
-  if (capacity > 0 && hipMalloc(&d_res, sizeof(double) * (size_t)capacity) != hipSuccess) return cfear_fail(ctx, CFEAR_ERR_NOMEM, "hipMalloc residuals");
+  DevBuf<double> d_res;
+  CFEAR_TRY(d_res.ensure(ctx, (size_t)capacity, "hipMalloc residuals"));
   hipError_t e = hipMemcpyAsync(d_ptrs, pb.ptrs, sizeof(void*) * n, hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(d_poses, poses_xyt, sizeof(double) * 3 * n, hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess) {
@@ -1253,7 +1240,6 @@ int cfear_get_cost(cfear_ctx* ctx, cfear_scan* const* scans, int n, const double
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
   if (e == hipSuccess && nres > 0 && capacity > 0)
     e = hipMemcpy(residuals, d_res, sizeof(double) * (size_t)(nres < capacity ? nres : capacity), hipMemcpyDeviceToHost);
-  if (d_res) (void)hipFree(d_res);
   if (e != hipSuccess) return cfear_fail(ctx, CFEAR_ERR_HIP, "get_cost", e);
   *n_residuals = nres;
   if (nres < 0) return cfear_fail(ctx, CFEAR_ERR_EMPTY, "get_cost: too few residuals");  // GetCost returns false (:205-208)
@@ -1300,8 +1286,9 @@ int cfear_get_surface(cfear_ctx* ctx, cfear_scan* const* scans, int n, const dou
   // header, coordinates, their counts and the surface: one allocation per call
   const size_t np = (size_t)pixels * pixels;
   const size_t hdr_b = (sizeof(SurfHdr) + 255) / 256 * 256, crd_b = (sizeof(double) * 2 * pixels + 255) / 256 * 256;
-  unsigned char* d_buf = nullptr;
-  if (hipMalloc(&d_buf, hdr_b + crd_b + 256 + sizeof(double) * np) != hipSuccess) return cfear_fail(ctx, CFEAR_ERR_NOMEM, "hipMalloc surface");
+  DevBuf<unsigned char> buf;
+  CFEAR_TRY(buf.ensure(ctx, hdr_b + crd_b + 256 + sizeof(double) * np, "hipMalloc surface"));
+  unsigned char* d_buf = buf;
   SurfHdr* d_hdr = reinterpret_cast<SurfHdr*>(d_buf);
   double* d_coords = reinterpret_cast<double*>(d_buf + hdr_b);
   int* d_nxy = reinterpret_cast<int*>(d_buf + hdr_b + crd_b);
@@ -1326,7 +1313,6 @@ int cfear_get_surface(cfear_ctx* ctx, cfear_scan* const* scans, int n, const dou
   }
   if (e == hipSuccess) e = hipMemcpyAsync(surface, d_out, sizeof(double) * np, hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  (void)hipFree(d_buf);
   if (e != hipSuccess) return cfear_fail(ctx, CFEAR_ERR_HIP, "get_surface", e);
   if (nx) *nx = nxy[0];
   if (ny) *ny = nxy[1];
@@ -1461,9 +1447,9 @@ int cfear_cov_by_sampling(cfear_ctx* ctx, cfear_scan* const* scans, int n, const
   // device buffers: poses, samples, scan pointers, costs, residual counts, per-sample match arrays
   const size_t bytes = sizeof(double) * (3 * (size_t)n + 3 * (size_t)m + (size_t)m) + sizeof(void*) * (size_t)n + sizeof(int) * (size_t)m +
                        (sizeof(double) * 8 + 3 * sizeof(int)) * (size_t)m * cap + 256;  // (three ints of association scratch per pair: the grouped path, as scratch_layout)
-  unsigned char* d = nullptr;
-  if (hipMalloc(&d, bytes) != hipSuccess) return cfear_fail(ctx, CFEAR_ERR_NOMEM, "hipMalloc cost samples");
-  double* d_match = reinterpret_cast<double*>(d);
+  DevBuf<double> d;
+  CFEAR_TRY(d.ensure(ctx, (bytes + 7) / 8, "hipMalloc cost samples"));
+  double* d_match = d;
   double* d_poses = d_match + 8 * (size_t)m * cap;
   double* d_samples = d_poses + 3 * n;
   double* d_costs = d_samples + 3 * m;
@@ -1481,7 +1467,6 @@ int cfear_cov_by_sampling(cfear_ctx* ctx, cfear_scan* const* scans, int n, const
   if (e == hipSuccess) e = hipMemcpyAsync(costs.data(), d_costs, sizeof(double) * m, hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(nres.data(), d_nres, sizeof(int) * m, hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  (void)hipFree(d);
   if (e != hipSuccess) return cfear_fail(ctx, CFEAR_ERR_HIP, "cov_by_sampling", e);
   double last = 0.0;  // a failed GetCost leaves sample_cost at its previous value (:305: the return value is ignored)
   for (int i = 0; i < m; i++) { if (nres[i] >= 0) last = costs[i]; costs[i] = last; }
@@ -1508,19 +1493,14 @@ void cfear_odometry_destroy(cfear_ctx* ctx, cfear_odometry* o) {
     }
     (void)hipStreamSynchronize(ctx->stream);
   }
-  void* ptrs[] = {o->d_scans, o->d_scratch, o->d_scratch_hdr, o->d_states, o->d_cov_work, o->d_summaries, o->d_poses_out, o->d_slots[0], o->d_slots[1], o->d_polar, o->d_phase_times,
-                  o->rp_polar[0], o->rp_polar[1], o->rp_slots[0], o->rp_slots[1], o->d_records, o->d_flags, o->d_order, o->d_work,
-                  o->d_cloud, o->d_cloud_n, o->d_cfar_rows, o->rp_cloud[0], o->rp_cloud[1], o->rp_cloud_n[0], o->rp_cloud_n[1], o->rp_cfar_rows,
-                  o->d_cov_ctx, o->d_cov_design, o->d_cov_costs, o->d_cov_seq, o->d_surf_hdr, o->d_surf_coords, o->d_surf_nxy, o->d_seq};
   for (hipEvent_t e : {o->rp_filt[0], o->rp_filt[1], o->rp_used[0], o->rp_used[1], o->rp_in}) if (e) (void)hipEventDestroy(e);
   if (o->rp_stream) (void)hipStreamDestroy(o->rp_stream);
-  for (void* p : ptrs) if (p) (void)hipFree(p);
   for (hipEvent_t e : o->pool) (void)hipEventDestroy(e);
   for (hipEvent_t e : {o->ev_in, o->ev_copied, o->ev_filt[0], o->ev_filt[1]}) if (e) (void)hipEventDestroy(e);
   for (auto* v : {&o->ev_free[0], &o->ev_free[1], &o->ev_done}) for (hipEvent_t e : *v) if (e) (void)hipEventDestroy(e);
   if (o->sf) (void)hipStreamDestroy(o->sf);
   for (hipStream_t st : o->so) if (st) (void)hipStreamDestroy(st);
-  delete o;
+  delete o;  // (and with it the device buffers)
 }
 
 int cfear_odometry_reset(cfear_ctx* ctx, cfear_odometry* o) {
@@ -1541,6 +1521,44 @@ int cfear_odometry_reset(cfear_ctx* ctx, cfear_odometry* o) {
   o->surf_ready = false;
   o->sweeps = 0;  // (the parameter table, the source map and the fuser options stay)
   CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  return CFEAR_OK;
+}
+
+// the overflow flags of `o`, all clear: created with the object when a scan can overflow its cells or the filter's clouds their points, by
+// cfear_odometry_step_cloud_device otherwise (the caller's clouds may) when it is first used
+static int odo_ensure_flags(cfear_ctx* ctx, cfear_odometry* o) {
+  if (o->d_flags) return CFEAR_OK;
+  CFEAR_TRY(o->d_flags.ensure(ctx, (size_t)o->B + 1, "hipMalloc odometry state"));
+  CFEAR_HIP_CHECK(ctx, hipMemsetAsync(o->d_flags, 0, sizeof(int) * o->d_flags.size(), ctx->stream));
+  return CFEAR_OK;
+}
+// ... and the [B] records of the registrations (cost sampling and surface recording share them), all 'nothing recorded'. The streams are idle.
+static int odo_ensure_cov_ctx(cfear_ctx* ctx, cfear_odometry* o, const char* what) {
+  return o->d_cov_ctx.ensure(ctx, (size_t)o->B, what, true);
+}
+// the device memory every object has, sized by the fields cfear_odometry_create has set (scratch_bytes: of one sequence's scratch block)
+static int odo_alloc_state(cfear_ctx* ctx, cfear_odometry* o, size_t scratch_bytes) {
+  const size_t B = (size_t)o->B;
+  const char* what = "hipMalloc odometry state";
+  CFEAR_TRY(o->d_scans.ensure(ctx, o->scan_stride * B * o->nslots, what));
+  CFEAR_TRY(o->d_scratch.ensure(ctx, scratch_bytes * B, what, true));  // dense voxel tables start all-zero
+  CFEAR_TRY(o->d_scratch_hdr.ensure(ctx, B, what));
+  CFEAR_TRY(o->d_states.ensure(ctx, B, what));
+  CFEAR_TRY(o->d_cov_work.ensure(ctx, 36 * B, what));
+  CFEAR_TRY(o->d_summaries.ensure(ctx, B, what));
+  CFEAR_TRY(o->d_poses_out.ensure(ctx, 3 * B, what));
+  if (o->filter == CFEAR_FILTER_CACFAR) {
+    CFEAR_TRY(o->d_cloud.ensure(ctx, 3 * B * o->cap_points, what));
+    CFEAR_TRY(o->d_cloud_n.ensure(ctx, B, what));
+    CFEAR_TRY(o->d_cfar_rows.ensure(ctx, cfear_cfar_scratch_ints(ctx, B), what));
+  } else {
+    for (auto& slots : o->d_slots) CFEAR_TRY(slots.ensure(ctx, B * o->cap_points, what));
+  }
+  if (o->cap_cells < o->cap_points || o->filter == CFEAR_FILTER_CACFAR) CFEAR_TRY(odo_ensure_flags(ctx, o));
+  if (ctx->tune_reg_order && o->B >= 2) {
+    CFEAR_TRY(o->d_order.ensure(ctx, B, what));
+    CFEAR_TRY(o->d_work.ensure(ctx, B, what, true));
+  }
   return CFEAR_OK;
 }
 
@@ -1584,30 +1602,9 @@ int cfear_odometry_create(cfear_ctx* ctx, int n_sequences, cfear_odometry** out)
       return cfear_fail(ctx, CFEAR_ERR_NOMEM, msg);
     }
   }
-  bool ok = true;
-  ok = ok && hipMalloc(&o->d_scans, SL.total * (size_t)B * o->nslots) == hipSuccess;
-  ok = ok && hipMalloc(&o->d_scratch, WL.total * (size_t)B) == hipSuccess;
-  ok = ok && hipMemset(o->d_scratch, 0, WL.total * (size_t)B) == hipSuccess;  // dense voxel tables start all-zero
-  ok = ok && hipMalloc(&o->d_scratch_hdr, sizeof(BlockScratch) * (size_t)B) == hipSuccess;
-  ok = ok && hipMalloc(&o->d_states, sizeof(SeqState) * (size_t)B) == hipSuccess;
-  ok = ok && hipMalloc(&o->d_cov_work, sizeof(double) * 36 * (size_t)B) == hipSuccess;
-  ok = ok && hipMalloc(&o->d_summaries, sizeof(cfear_reg_summary) * (size_t)B) == hipSuccess;
-  ok = ok && hipMalloc(&o->d_poses_out, sizeof(double) * 3 * (size_t)B) == hipSuccess;
-  if (o->filter == CFEAR_FILTER_CACFAR) {
-    ok = ok && hipMalloc(&o->d_cloud, sizeof(float) * 3 * (size_t)B * o->cap_points) == hipSuccess;
-    ok = ok && hipMalloc(&o->d_cloud_n, sizeof(int) * (size_t)B) == hipSuccess;
-    ok = ok && hipMalloc(&o->d_cfar_rows, sizeof(int) * cfear_cfar_scratch_ints(ctx, (size_t)B)) == hipSuccess;
-  } else {
-    ok = ok && hipMalloc(&o->d_slots[0], sizeof(uint32_t) * (size_t)B * o->cap_points) == hipSuccess;
-    ok = ok && hipMalloc(&o->d_slots[1], sizeof(uint32_t) * (size_t)B * o->cap_points) == hipSuccess;
-  }
-  // (a sweep's CA-CFAR detections may exceed the points the object holds; cfear_odometry_step_cloud_device allocates the word when first used)
-  if (ok && (o->cap_cells < o->cap_points || o->filter == CFEAR_FILTER_CACFAR)) ok = hipMalloc(&o->d_flags, sizeof(int) * ((size_t)B + 1)) == hipSuccess && hipMemset(o->d_flags, 0, sizeof(int) * ((size_t)B + 1)) == hipSuccess;
-  if (ok && ctx->tune_reg_order && B >= 2)
-    ok = hipMalloc(&o->d_order, sizeof(int) * (size_t)B) == hipSuccess && hipMalloc(&o->d_work, sizeof(unsigned) * (size_t)B) == hipSuccess &&
-         hipMemset(o->d_work, 0, sizeof(unsigned) * (size_t)B) == hipSuccess;
-  if (!ok) { cfear_odometry_destroy(ctx, o); return cfear_fail(ctx, CFEAR_ERR_NOMEM, "hipMalloc odometry state"); }
   o->scan_stride = SL.total;
+  const int arc = odo_alloc_state(ctx, o, WL.total);
+  if (arc != CFEAR_OK) { cfear_odometry_destroy(ctx, o); return arc; }
   std::vector<BlockScratch> hdrs((size_t)B);
   std::vector<ScanDev> scan_hdrs((size_t)B * o->nslots);  // all headers built on the host, uploaded with one strided copy
   for (int q = 0; q < B; q++) {
@@ -1615,7 +1612,7 @@ int cfear_odometry_create(cfear_ctx* ctx, int n_sequences, cfear_odometry** out)
       scan_hdrs[(size_t)q * o->nslots + j] = scan_header(o->d_scans + SL.total * ((size_t)q * o->nslots + j), o->cap_points, o->cap_cells, false, o->with_kd);
     hdrs[q] = scratch_header(o->d_scratch + WL.total * (size_t)q, o->cap_points, o->pair_cap);
   }
-  ok = ok && hipMemcpy2D(o->d_scans, SL.total, scan_hdrs.data(), sizeof(ScanDev), sizeof(ScanDev), scan_hdrs.size(), hipMemcpyHostToDevice) == hipSuccess;
+  bool ok = hipMemcpy2D(o->d_scans, SL.total, scan_hdrs.data(), sizeof(ScanDev), sizeof(ScanDev), scan_hdrs.size(), hipMemcpyHostToDevice) == hipSuccess;
   ok = ok && hipMemcpy(o->d_scratch_hdr, hdrs.data(), sizeof(BlockScratch) * hdrs.size(), hipMemcpyHostToDevice) == hipSuccess;
   if (!ok) { cfear_odometry_destroy(ctx, o); return cfear_fail(ctx, CFEAR_ERR_HIP, "odometry state upload"); }
   const int rc = cfear_odometry_reset(ctx, o);
@@ -1702,10 +1699,7 @@ int cfear_odometry_step_cloud_device(cfear_ctx* ctx, cfear_odometry* o, const fl
   }
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   CFEAR_TRY(odo_join(ctx, o));
-  if (!o->d_flags) {  // counts beyond `capacity` are reported like every other truncation
-    CFEAR_HIP_CHECK(ctx, hipMalloc(&o->d_flags, sizeof(int) * ((size_t)o->B + 1)));
-    CFEAR_HIP_CHECK(ctx, hipMemsetAsync(o->d_flags, 0, sizeof(int) * ((size_t)o->B + 1), ctx->stream));
-  }
+  CFEAR_TRY(odo_ensure_flags(ctx, o));  // counts beyond `capacity` are reported like every other truncation
   return odo_step_clouds(ctx, o, d_xyi, capacity, d_counts, false);
 }
 
@@ -1777,15 +1771,10 @@ int cfear_odometry_phase_times(cfear_ctx* ctx, cfear_odometry* o, int enable, lo
     o->wg_only = enable == 3;
   }
   if (!enable) {
-    if (o->d_phase_times) (void)hipFree(o->d_phase_times);
-    o->d_phase_times = nullptr;
+    o->d_phase_times.release();
     return CFEAR_OK;
   }
-  if (!o->d_phase_times) {
-    if (hipMalloc(&o->d_phase_times, bytes) != hipSuccess) return cfear_fail(ctx, CFEAR_ERR_NOMEM, "hipMalloc phase times");
-    CFEAR_HIP_CHECK(ctx, hipMemset(o->d_phase_times, 0, bytes));
-    return CFEAR_OK;
-  }
+  if (!o->d_phase_times) return o->d_phase_times.ensure(ctx, 32 * (size_t)o->B, "hipMalloc phase times", true);
   if (host_ticks) {
     CFEAR_HIP_CHECK(ctx, hipMemcpy(host_ticks, o->d_phase_times, bytes, hipMemcpyDeviceToHost));
     CFEAR_HIP_CHECK(ctx, hipMemset(o->d_phase_times, 0, bytes));
@@ -1844,7 +1833,7 @@ int cfear_odometry_step_host(cfear_ctx* ctx, cfear_odometry* o, const uint8_t* h
   if (!ctx || !o || !h_polar) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_step_host: bad argument");
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   const size_t bytes = (size_t)odo_sources(o) * ctx->A * ctx->R;  // (cfear_odometry_set_sequence_sources releases a staging buffer of another size)
-  if (!o->d_polar && hipMalloc(&o->d_polar, bytes + 64) != hipSuccess) return cfear_fail(ctx, CFEAR_ERR_NOMEM, "hipMalloc polar batch");
+  CFEAR_TRY(o->d_polar.ensure(ctx, bytes + 64, "hipMalloc polar batch"));
   // the staging buffer is reused: the copy waits for the filter of the previous sweep (its only reader), not for that
   // sweep's features / registration
   if (o->overlap && o->step_no > 0) CFEAR_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream, o->ev_filt[(o->step_no - 1) & 1], 0));
@@ -1887,43 +1876,29 @@ static int replay_ensure(cfear_ctx* ctx, cfear_odometry* o, int chunk, bool stag
   if (chunk > o->rp_chunk) {
     CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(o->rp_stream));
     CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    for (int i = 0; i < 2; i++) {
-      for (void** q : {(void**)&o->rp_slots[i], (void**)&o->rp_cloud[i], (void**)&o->rp_cloud_n[i]}) { if (*q) (void)hipFree(*q); *q = nullptr; }
-      o->rp_used_pending[i] = false;
-    }
-    if (o->rp_cfar_rows) (void)hipFree(o->rp_cfar_rows);
-    o->rp_cfar_rows = nullptr;
-    o->rp_chunk = 0;
+    o->rp_chunk = 0;  // (until every buffer holds `chunk` sweeps)
+    o->rp_used_pending[0] = o->rp_used_pending[1] = false;
     for (int i = 0; i < 2; i++) {
       if (o->filter == CFEAR_FILTER_CACFAR) {  // a cloud of cap_points points + its count per sweep and sequence
-        if (hipMalloc(&o->rp_cloud[i], sizeof(float) * 3 * slots * chunk) != hipSuccess || hipMalloc(&o->rp_cloud_n[i], sizeof(int) * (size_t)o->B * chunk) != hipSuccess)
-          return cfear_fail(ctx, CFEAR_ERR_NOMEM, "hipMalloc replay cloud buffers");
-      } else if (hipMalloc(&o->rp_slots[i], sizeof(uint32_t) * slots * chunk) != hipSuccess) {
-        return cfear_fail(ctx, CFEAR_ERR_NOMEM, "hipMalloc replay slot buffers");
+        CFEAR_TRY(o->rp_cloud[i].ensure(ctx, 3 * slots * chunk, "hipMalloc replay cloud buffers"));
+        CFEAR_TRY(o->rp_cloud_n[i].ensure(ctx, (size_t)o->B * chunk, "hipMalloc replay cloud buffers"));
+      } else {
+        CFEAR_TRY(o->rp_slots[i].ensure(ctx, slots * chunk, "hipMalloc replay slot buffers"));
       }
     }
-    if (o->filter == CFEAR_FILTER_CACFAR && hipMalloc(&o->rp_cfar_rows, sizeof(int) * cfear_cfar_scratch_ints(ctx, (size_t)o->B * chunk)) != hipSuccess)
-      return cfear_fail(ctx, CFEAR_ERR_NOMEM, "hipMalloc replay cfar rows");
+    if (o->filter == CFEAR_FILTER_CACFAR) CFEAR_TRY(o->rp_cfar_rows.ensure(ctx, cfear_cfar_scratch_ints(ctx, (size_t)o->B * chunk), "hipMalloc replay cfar rows"));
     o->rp_chunk = chunk;
   }
   if (staging && chunk > o->rp_polar_chunk) {
     CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(o->rp_stream));
     CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    for (int i = 0; i < 2; i++) {
-      if (o->rp_polar[i]) (void)hipFree(o->rp_polar[i]);
-      o->rp_polar[i] = nullptr;
-    }
     o->rp_polar_chunk = 0;
-    for (int i = 0; i < 2; i++)
-      if (hipMalloc(&o->rp_polar[i], sweep * chunk + 64) != hipSuccess) return cfear_fail(ctx, CFEAR_ERR_NOMEM, "hipMalloc replay staging");
+    for (auto& polar : o->rp_polar) CFEAR_TRY(polar.ensure(ctx, sweep * chunk + 64, "hipMalloc replay staging"));
     o->rp_polar_chunk = chunk;
   }
-  if (n_records > o->records_cap) {
+  if (n_records > o->d_records.size()) {
     CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    if (o->d_records) (void)hipFree(o->d_records);
-    o->d_records = nullptr; o->records_cap = 0;
-    if (hipMalloc(&o->d_records, sizeof(cfear_sweep_record) * n_records) != hipSuccess) return cfear_fail(ctx, CFEAR_ERR_NOMEM, "hipMalloc sweep records");
-    o->records_cap = n_records;
+    CFEAR_TRY(o->d_records.ensure(ctx, n_records, "hipMalloc sweep records"));
   }
   return CFEAR_OK;
 }
@@ -2034,12 +2009,9 @@ int cfear_odometry_replay_host_cov(cfear_ctx* ctx, cfear_odometry* o, const uint
   if (rc != CFEAR_OK) return rc;
   if (records && (rc = replay_ensure(ctx, o, 0, false, (size_t)n_sweeps * o->B)) != CFEAR_OK) return rc;
   const size_t ncov = cov6 ? (size_t)n_sweeps * o->B * 36 : 0;
-  if (ncov > o->cov_seq_cap) {
+  if (ncov > o->d_cov_seq.size()) {
     CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    if (o->d_cov_seq) (void)hipFree(o->d_cov_seq);
-    o->d_cov_seq = nullptr; o->cov_seq_cap = 0;
-    if (hipMalloc(&o->d_cov_seq, sizeof(double) * ncov) != hipSuccess) return cfear_fail(ctx, CFEAR_ERR_NOMEM, "hipMalloc per-sweep covariances");
-    o->cov_seq_cap = ncov;
+    CFEAR_TRY(o->d_cov_seq.ensure(ctx, ncov, "hipMalloc per-sweep covariances"));
   }
   rc = replay_impl(ctx, o, h_frames, false, n_sweeps, records ? o->d_records : nullptr, cov6 ? o->d_cov_seq : nullptr);
   if (rc != CFEAR_OK) return rc;
@@ -2080,17 +2052,9 @@ int cfear_odometry_set_cov_sampling(cfear_ctx* ctx, cfear_odometry* o, int enabl
   cov_sample_design(xy_range, yaw_range, samples_per_axis, offs, A);
   pinv10_svd(m, A.data(), design.data());
   memcpy(design.data() + 10 * (size_t)m, offs.data(), sizeof(double) * 3 * m);
-  if (!o->d_cov_ctx) {
-    CFEAR_HIP_CHECK(ctx, hipMalloc(&o->d_cov_ctx, sizeof(CovSampleCtx) * (size_t)o->B));
-    CFEAR_HIP_CHECK(ctx, hipMemset(o->d_cov_ctx, 0, sizeof(CovSampleCtx) * (size_t)o->B));
-  }
-  if (m > o->cov_m_cap) {
-    for (double** p : {&o->d_cov_design, &o->d_cov_costs}) { if (*p) (void)hipFree(*p); *p = nullptr; }
-    o->cov_m_cap = 0;
-    if (hipMalloc(&o->d_cov_design, sizeof(double) * 13 * (size_t)m) != hipSuccess || hipMalloc(&o->d_cov_costs, sizeof(double) * (size_t)m * o->B) != hipSuccess)
-      return cfear_fail(ctx, CFEAR_ERR_NOMEM, "hipMalloc cost-sampling buffers");
-    o->cov_m_cap = m;
-  }
+  CFEAR_TRY(odo_ensure_cov_ctx(ctx, o, "hipMalloc cost-sampling buffers"));
+  CFEAR_TRY(o->d_cov_design.ensure(ctx, 13 * (size_t)m, "hipMalloc cost-sampling buffers"));
+  CFEAR_TRY(o->d_cov_costs.ensure(ctx, (size_t)m * o->B, "hipMalloc cost-sampling buffers"));
   CFEAR_HIP_CHECK(ctx, hipMemset(o->d_cov_costs, 0, sizeof(double) * (size_t)m * o->B));
   CFEAR_HIP_CHECK(ctx, hipMemcpy(o->d_cov_design, design.data(), sizeof(double) * 13 * (size_t)m, hipMemcpyHostToDevice));
   // no sweep sampled yet under these settings (n = 0: cov_samples reads zeros and 'not sampled')
@@ -2107,8 +2071,7 @@ int cfear_odometry_set_surface_recording(cfear_ctx* ctx, cfear_odometry* o, int 
   if (!o->d_cov_ctx) {
     CFEAR_TRY(odo_join(ctx, o));
     CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    if (hipMalloc(&o->d_cov_ctx, sizeof(CovSampleCtx) * (size_t)o->B) != hipSuccess) return cfear_fail(ctx, CFEAR_ERR_NOMEM, "hipMalloc surface records");
-    CFEAR_HIP_CHECK(ctx, hipMemset(o->d_cov_ctx, 0, sizeof(CovSampleCtx) * (size_t)o->B));
+    CFEAR_TRY(odo_ensure_cov_ctx(ctx, o, "hipMalloc surface records"));
   }
   o->surf_on = true;
   return CFEAR_OK;
@@ -2137,15 +2100,9 @@ int cfear_odometry_surface(cfear_ctx* ctx, cfear_odometry* o, double res, int wi
   }
   CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   const int cap_rc = odo_capacity_check(ctx, o, "odometry_surface");  // (the stream is idle: the surfaces are computed all the same)
-  if (pixels > o->surf_px_cap) {
-    for (void** p : {(void**)&o->d_surf_hdr, (void**)&o->d_surf_coords, (void**)&o->d_surf_nxy}) { if (*p) (void)hipFree(*p); *p = nullptr; }
-    o->surf_px_cap = 0;
-    if (hipMalloc(&o->d_surf_hdr, sizeof(SurfHdr) * (size_t)B) != hipSuccess ||
-        hipMalloc(&o->d_surf_coords, sizeof(double) * 2 * (size_t)pixels * B) != hipSuccess ||
-        hipMalloc(&o->d_surf_nxy, sizeof(int) * 2 * (size_t)B) != hipSuccess)
-      return cfear_fail(ctx, CFEAR_ERR_NOMEM, "hipMalloc surface buffers");
-    o->surf_px_cap = pixels;
-  }
+  CFEAR_TRY(o->d_surf_hdr.ensure(ctx, (size_t)B, "hipMalloc surface buffers"));
+  CFEAR_TRY(o->d_surf_coords.ensure(ctx, 2 * (size_t)pixels * B, "hipMalloc surface buffers"));
+  CFEAR_TRY(o->d_surf_nxy.ensure(ctx, 2 * (size_t)B, "hipMalloc surface buffers"));
   std::vector<double> coords(2 * (size_t)pixels * B, 0.0);
   std::vector<int> nxy(2 * (size_t)B, 0);
   for (int q = 0; q < B; q++) {
@@ -2229,17 +2186,18 @@ int cfear_odometry_set_sequence_sources(cfear_ctx* ctx, cfear_odometry* o, const
   if (rc != CFEAR_OK) { o->seq_src.swap(keep); std::swap(o->n_sources, keep_n); (void)seq_table_upload(ctx, o); return rc; }
   // both parities of the filter-ahead slot buffers hold one slot block per input sweep (nothing is in flight: the streams were joined above)
   {
-    uint32_t* ns[2] = {nullptr, nullptr};
-    const size_t bytes = sizeof(uint32_t) * (size_t)odo_sources(o) * o->cap_points;
-    if (hipMalloc(&ns[0], bytes) != hipSuccess || hipMalloc(&ns[1], bytes) != hipSuccess) {
-      if (ns[0]) (void)hipFree(ns[0]);
+    DevBuf<uint32_t> ns[2];  // the new pair first: a failure leaves the object with the old one (and the old map)
+    const size_t n = (size_t)odo_sources(o) * o->cap_points;
+    const char* what = "hipMalloc filter slot buffers for the source map";
+    if (ns[0].ensure(ctx, n, what) != CFEAR_OK || ns[1].ensure(ctx, n, what) != CFEAR_OK) {
       o->seq_src.swap(keep); std::swap(o->n_sources, keep_n); (void)seq_table_upload(ctx, o);
-      return cfear_fail(ctx, CFEAR_ERR_NOMEM, "hipMalloc filter slot buffers for the source map");
+      return cfear_fail(ctx, CFEAR_ERR_NOMEM, what);
     }
-    for (int i = 0; i < 2; i++) { (void)hipFree(o->d_slots[i]); o->d_slots[i] = ns[i]; o->filt_pending[i] = false; }
+    for (int i = 0; i < 2; i++) { o->d_slots[i] = std::move(ns[i]); o->filt_pending[i] = false; }
   }
   // the staging and chunk buffers are sized per input sweep of a step: released here, allocated again (for the sources) by the next call that needs them
-  for (void** p : {(void**)&o->d_polar, (void**)&o->rp_polar[0], (void**)&o->rp_polar[1], (void**)&o->rp_slots[0], (void**)&o->rp_slots[1]}) { if (*p) (void)hipFree(*p); *p = nullptr; }
+  o->d_polar.release();
+  for (int i = 0; i < 2; i++) { o->rp_polar[i].release(); o->rp_slots[i].release(); }
   o->rp_chunk = 0; o->rp_polar_chunk = 0; o->rp_used_pending[0] = o->rp_used_pending[1] = false;
   return CFEAR_OK;
 }
@@ -2363,9 +2321,8 @@ int cfear_odometry_summary(cfear_ctx* ctx, cfear_odometry* o, int sequence, cfea
     CFEAR_HIP_CHECK(ctx, hipMemcpy(&st, o->d_states + sequence, sizeof(st), hipMemcpyDeviceToHost));
     if (n_keyframes) *n_keyframes = st.nkf;
     if (n_cells) {  // cells of the scan built by the last step
-      const ScanLayout SL = scan_layout(o->cap_points, o->cap_cells, false, o->with_kd);
       ScanDev h;
-      CFEAR_HIP_CHECK(ctx, hipMemcpy(&h, o->d_scans + SL.total * ((size_t)sequence * o->nslots + st.last_slot), sizeof(h), hipMemcpyDeviceToHost));
+      CFEAR_HIP_CHECK(ctx, hipMemcpy(&h, o->d_scans + o->scan_stride * ((size_t)sequence * o->nslots + st.last_slot), sizeof(h), hipMemcpyDeviceToHost));
       *n_cells = h.n_cells;
     }
   }
