@@ -250,10 +250,17 @@ __device__ __forceinline__ void point_regs_to_global(const PointRegs& R, float* 
 
 // slots of one sweep -> compensated cloud (getPeaksFilteredPointCloud, radar_filters.cpp:309-337, + Compensate, utils.cpp:96-107)
 // in S->xyi AND in the registers of the block (PR), with the bounding box. Returns the number of points.
-__device__ inline int cloud_step_block(const uint32_t* __restrict__ slots, int A, int k, const double* __restrict__ trig,
+// K: the slots of a bearing are K apart (the k_strongest the filter ran with), k <= K of them are this cloud's. The filter leaves a bearing's
+// C <= K returns in front, ascending by (intensity, range), and zeros behind them; its k strongest are the slots [max(C - k, 0), C), in the order
+// a k-filter would leave them in. Item t = (bearing b, slot j) of the A * k logical items, row-major as in the reference's loop, is therefore
+// slots[b * K + max(C_b - k, 0) + j] = slots[t + b * (K - k) + max(C_b - k, 0)]: with k < K a pass in front finds every bearing's C by bisection
+// and keeps the offset b * (K - k) + max(C_b - k, 0) in `win` (LDS, win_cap ints; more bearings than that: every lane bisects for itself).
+// Lane <-> item as before, not lane <-> physical slot: the rounds a wave takes and the branch chosen below follow A * k, as they do for an
+// object whose filter ran with k. K == k: the address is t, no pass in front.
+__device__ inline int cloud_step_block(const uint32_t* __restrict__ slots, int A, int k, int K, const double* __restrict__ trig,
                                        float range_res_f, float min_distance_f, int z_min, float* __restrict__ xyi, int cap, int compensate,
                                        double m0, double m1, double m2, int ccw, int* red_i, float* red_f, double* tab,
-                                       int tab_bearings, float bounds[4], PointRegs& PR, bool store = true) {
+                                       int tab_bearings, float bounds[4], PointRegs& PR, bool store = true, int* win = nullptr, int win_cap = 0) {
   // store = false: the caller can do without the cloud in S->xyi when the points are handed over in registers - 58 KB per
   // sweep that the compact feature path never reads back (the general branch below always writes it);
   // point_regs_to_global writes it later for a caller that turns out to need it.
@@ -266,6 +273,27 @@ __device__ inline int cloud_step_block(const uint32_t* __restrict__ slots, int A
   const int min_range_bin = (int)ceil((double)min_distance_f / range_res);  // radar_filters.cpp:315
   const double range_res_half = range_res / 2.0;
   const int items = A * k;
+  const int pad = __builtin_amdgcn_readfirstlane(K - k);  // slots of a bearing that are not this cloud's (the same in every lane: a scalar)
+  // returns of bearing b: they sit in front of its K slots, so the first slot without the valid bit, by bisection
+  auto bearing_count = [&](int b) -> int {
+    int lo = 0, hi = K;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (CFEAR_SLOT_VALID(g_slots[b * K + mid])) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+  };
+  auto* lwin = CFEAR_LDS_PTR(int, win);
+  const bool win_lds = pad != 0 && A <= win_cap;  // block-uniform
+  if (win_lds) {
+    for (int b = threadIdx.x; b < A; b += CFEAR_FEAT_BLOCK) lwin[b] = b * pad + max(bearing_count(b) - k, 0);
+    __syncthreads();
+  }
+  // item t of bearing b (< A) sits at slots[t + window_offset(b)]; only called with pad != 0
+  auto window_offset = [&](int b) -> int {
+    b = min(b, A - 1);
+    return win_lds ? lwin[b] : b * pad + max(bearing_count(b) - k, 0);
+  };
   // z_min: a slot also has to reach this intensity (a sequence's own threshold behind a filter that ran with a lower one; 0: every valid slot).
   // One comparison for both: the valid bit sits right above the intensity byte
   const int valid_z = 256 + z_min;
@@ -304,7 +332,10 @@ __device__ inline int cloud_step_block(const uint32_t* __restrict__ slots, int A
 #pragma unroll
     for (int r = 0; r < CFEAR_PT; r++) {  // the slots are on their way from memory while the table is built
       const int t = (wv * RC + r) * 64 + ln;
-      sv[r] = g_slots[((r < RC) & (t < items)) ? t : 0];
+      const bool inr = (r < RC) & (t < items);
+      int at = inr ? t : 0;
+      if (pad != 0) at += window_offset(inr ? (k > 1 ? (int)__umulhi((unsigned)t, magic) : t) : 0);  // block-uniform branch
+      sv[r] = g_slots[at];
     }
     build_table();
     int wtot = 0;
@@ -376,13 +407,18 @@ __device__ inline int cloud_step_block(const uint32_t* __restrict__ slots, int A
   const bool small = k > 1 && k < 65536 && items < 65536;  // block-uniform: t / k by multiplication (see above)
   const unsigned magic = small ? (unsigned)((0x100000000ull + (unsigned)k - 1u) / (unsigned)k) : 0u;
   const int t_wave = wv * RC * 64;
+  // where item t (< items) sits in the sweep's slots (see above); pad == 0 (block-uniform: no table, or a row with the context's k): t itself
+  auto slot_of = [&](int t) -> int {
+    if (pad == 0) return t;
+    return t + window_offset(small ? (int)__umulhi((unsigned)t, magic) : (int)((unsigned)t / (unsigned)k));
+  };
   int wtot = 0;
   for (int r0 = 0; r0 < RC; r0 += 8) {
     uint32_t sv[8];
 #pragma unroll
     for (int u = 0; u < 8; u++) {
       const int t = t_wave + (r0 + u) * 64 + ln;
-      sv[u] = g_slots[((r0 + u < RC) & (t < items)) ? t : 0];
+      sv[u] = g_slots[((r0 + u < RC) & (t < items)) ? slot_of(t) : 0];
     }
 #pragma unroll
     for (int u = 0; u < 8; u++) {
@@ -409,7 +445,7 @@ __device__ inline int cloud_step_block(const uint32_t* __restrict__ slots, int A
   #pragma unroll
       for (int u = 0; u < 8; u++) {
         const int t = t_wave + (r0 + u) * 64 + ln;
-        sv[u] = g_slots[((r0 + u < RC) & (t < items)) ? t : 0];
+        sv[u] = g_slots[((r0 + u < RC) & (t < items)) ? slot_of(t) : 0];
       }
   #pragma unroll
       for (int u = 0; u < 8; u++) {

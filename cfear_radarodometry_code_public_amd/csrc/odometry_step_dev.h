@@ -230,18 +230,22 @@ __device__ __forceinline__ void features_step_body(unsigned char* lds /* FeatLds
   PointRegs PR;
   // the sequence's own values where it has a row: the sweep it reads, its z_min (applied to the slots of a filter that ran with the smallest
   // z_min of the object: the k strongest above z are the members above z of the k strongest above any z' <= z), compensation, res, weights
+  // ... and its k_strongest: the filter ran with the context's K (OP.k, the stride of a bearing's slots); the k strongest of a bearing are the
+  // last k of the returns it kept (ascending, in front of the bearing's K slots), so the cloud pass reads that window
   FeatureParams fp = OP.fp;
-  int src = q, compensate = OP.compensate, z_min = 0;
+  int src = q, compensate = OP.compensate, z_min = 0, k = OP.k;
   if (const SeqRow row = seq_row(OP, q)) {
-    src = row->source; compensate = row->compensate; z_min = row->z_min;
+    src = row->source; compensate = row->compensate; z_min = row->z_min; k = row->k;
     fp.radius = row->radius; fp.weight_intensity = row->weight_intensity;
   }
   // (the compact feature path works from the registers: the 58 KB of the cloud are only written when somebody reads them)
-  const int n = cloud_step_block(slots_all + (size_t)src * OP.A * OP.k, OP.A, OP.k, trig, OP.fp.range_res, OP.fp.min_distance, z_min,
+  const int n = cloud_step_block(slots_all + (size_t)src * OP.A * OP.k, OP.A, k, OP.k, trig, OP.fp.range_res, OP.fp.min_distance, z_min,
                                  cur->xyi, cur->cap_points, compensate, mot[0], mot[1], mot[2], OP.ccw,
                                  reinterpret_cast<int*>(lds + FeatLdsC::red_i), reinterpret_cast<float*>(lds + FeatLdsC::red_f),
                                  reinterpret_cast<double*>(lds + FeatLdsC::pxy),  // 6 doubles per bearing where the sorted points go later
-                                 (int)(CFEAR_CPT_CAP * 8 / (6 * sizeof(double))), bounds, PR, false);
+                                 (int)(CFEAR_CPT_CAP * 8 / (6 * sizeof(double))), bounds, PR, false,
+                                 reinterpret_cast<int*>(lds + FeatLdsC::vst), (int)((FeatLdsC::pxy - FeatLdsC::vst) / sizeof(int)));  // (free until the feature build)
+
   if (TIMED) { pt.mark(); pt.mark(); }
   CFEAR_STOP_AT(1, );
   features_dispatch(cur, n, fp, B, lds, TIMED ? &pt : nullptr, n > 0 ? bounds : nullptr, true, true, PR, true);  // :161

@@ -606,6 +606,7 @@ static SeqParams seq_row_of(const cfear_params& p, int source) {
   r.compensate = p.compensate; r.use_keyframe = p.use_keyframe;
   r.z_min = (int)(uint8_t)(int)p.z_min;  // as the filter takes it (radar_filters.cpp:198, :212)
   r.source = source;
+  r.k = p.k_strongest;
   return r;
 }
 // may the rows be the sequences of `o` under the context's parameters? The fields that size memory or select a kernel are the object's
@@ -613,8 +614,16 @@ static int seq_rows_check(cfear_ctx* ctx, const cfear_odometry* o, const cfear_p
   const cfear_params& c = ctx->par;
   for (int q = 0; q < n; q++) {
     const cfear_params& r = rows[q];
+    // k_strongest: any k up to the context's K. The filter runs with K and the object is sized for it; a sequence reads the last k of the
+    // returns the filter kept of every bearing (cloud_step_block)
+    if (r.k_strongest < 1 || r.k_strongest > c.k_strongest) {
+      char msg[256];
+      snprintf(msg, sizeof(msg), "%s: row %d: k_strongest = %d must be in 1..%d, the context's k_strongest (the filter runs with it and the object's memory is sized "
+               "for it)", what, q, r.k_strongest, c.k_strongest);
+      return cfear_fail(ctx, CFEAR_ERR_INVALID, msg);
+    }
     const char* f = nullptr;
-    if (r.k_strongest != c.k_strongest) f = "k_strongest";
+    if (o->filter == CFEAR_FILTER_CACFAR && r.k_strongest != c.k_strongest) f = "k_strongest (the CA-CFAR detector has no k)";
     else if (r.cost != c.cost) f = "cost";
     else if (r.submap_scan_size != c.submap_scan_size) f = "submap_scan_size";
     else if (r.filter_type != c.filter_type) f = "filter_type";
@@ -630,9 +639,10 @@ static int seq_rows_check(cfear_ctx* ctx, const cfear_odometry* o, const cfear_p
     else if (r.cfar_max_distance != c.cfar_max_distance) f = "cfar_max_distance";
     else if (o->filter == CFEAR_FILTER_CACFAR && r.z_min != c.z_min) f = "z_min (the CA-CFAR detector's static threshold)";
     if (f) {
-      char msg[320];
+      char msg[400];
       snprintf(msg, sizeof(msg), "%s: row %d differs from the context's parameters in %s, which sizes memory or selects a kernel for the whole object "
-               "(per-sequence: z_min, res, weight_intensity, loss, loss_limit, weight_opt, covar_scale, regularization, compensate, the keyframe rule, the iteration limits)", what, q, f);
+               "(per-sequence: z_min, k_strongest (<= the context's), res, weight_intensity, loss, loss_limit, weight_opt, covar_scale, regularization, compensate, "
+               "the keyframe rule, the iteration limits)", what, q, f);
       return cfear_fail(ctx, CFEAR_ERR_INVALID, msg);
     }
     const char* bad = nullptr;  // the values cfear_set_params would refuse
@@ -1690,6 +1700,13 @@ int cfear_odometry_step_cloud_device(cfear_ctx* ctx, cfear_odometry* o, const fl
   if (!o->seq_src.empty())
     return cfear_fail(ctx, CFEAR_ERR_UNSUPPORTED, "odometry_step_cloud: the object has a source map (cfear_odometry_set_sequence_sources), which the cloud route does not "
                       "read - it takes one cloud per sequence; clear the map (NULL) first");
+  for (size_t q = 0; q < o->seq_rows.size(); q++)
+    if (o->seq_rows[q].k_strongest != ctx->par.k_strongest) {
+      char msg[256];
+      snprintf(msg, sizeof(msg), "odometry_step_cloud: row %d of the object's table has k_strongest = %d, the context %d - a cloud has no slots to take the k strongest "
+               "of; the cloud route runs with rows of the context's k_strongest only", (int)q, o->seq_rows[q].k_strongest, ctx->par.k_strongest);
+      return cfear_fail(ctx, CFEAR_ERR_UNSUPPORTED, msg);
+    }
   CFEAR_TRY(odo_seq_sync(ctx, o, "odometry_step_cloud"));
   if (capacity > o->cap_points) {
     char msg[256];

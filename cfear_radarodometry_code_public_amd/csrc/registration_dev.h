@@ -35,7 +35,9 @@ struct SeqParams {
   int z_min;     // as the filter compares it: (uint8_t)(int)z_min
   int source;    // the sweep of a step's input this sequence reads
   int fuser;     // cfear_fuser_options as the step takes them (cfear_odometry_set_fuser_options): SEQ_FUSER_* bits, 0 = the defaults
+  int k;         // k_strongest of the sequence, 1 .. the context's K: the cloud pass reads the last k of the returns the K-filter kept of every bearing
 };
+static_assert(sizeof(SeqParams) <= 96, "a row of the per-sequence table: 96 bytes at the most");
 constexpr int SEQ_FUSER_SOFT = 1;      // soft_constraint: Register(..., soft_constraints = true) (odometrykeyframefuser.cpp:186)
 constexpr int SEQ_FUSER_NO_GUESS = 2;  // use_guess = 0: Tguess = T_prev (:167-168)
 typedef const __attribute__((address_space(4))) SeqParams* SeqRow;  // (constant address space: never written while a kernel may read it)

@@ -44,6 +44,16 @@ def param_grid(base, **axes):
     return rows
 
 
+def grid_context_params(rows):
+    """The parameters of the context a grid's rows run under: a copy of rows[0] with k_strongest the largest of the rows - the filter runs
+    with it and the object is sized for it, every row takes its own k strongest out of those (cfear_odometry_set_sequence_params). Rows of
+    equal k: rows[0]. Pure Python (no device); `rows` stays as it is."""
+    rows = list(rows)
+    p = capi.Params.from_buffer_copy(rows[0])
+    p.k_strongest = max(int(r.k_strongest) for r in rows)
+    return p
+
+
 # ... with the fuser's own switches (capi.FuserOptions): soft_constraint is the worker's third loop (utils/worker:40-46: after radar_ccw,
 # before disable_compensate); use_guess is not a loop of the worker and nests inside all of them
 FUSER_GRID_ORDER = GRID_ORDER[:1] + ("soft_constraint",) + GRID_ORDER[1:] + ("use_guess",)
@@ -84,7 +94,8 @@ def drift_dict(row):
 
 def replay_grid(frames, rows, A=None, R=None, gt=None, device=0, piece=256, context_params=None, options=None, drift_on="host"):
     """One recording under len(rows) parameter sets in one batched odometry object: frames uint8 [n, A, R], rows a list of capi.Params that
-    agree in the object-wide fields (param_grid of one base does). The recording is the single source sweep of every sequence: it is
+    agree in the object-wide fields (param_grid of one base does; k_strongest may be an axis: the context then runs with the largest,
+    grid_context_params, unless context_params says otherwise). The recording is the single source sweep of every sequence: it is
     copied and filtered once per sweep. options: a capi.FuserOptions for every row or a list of one per row (fuser_grid builds both
     lists); None: the fuser's defaults. -> dict(poses [n, len(rows), 3], records, drift: per row KITTI drift against gt ([n, 4, 4]
     poses) or None). drift_on: "host" - kitti.drift row by row; "device" - all rows in one cfear_drift_host call against a plan of
@@ -95,7 +106,7 @@ def replay_grid(frames, rows, A=None, R=None, gt=None, device=0, piece=256, cont
     n, A, R = frames.shape
     rows = list(rows)
     piece = max(1, int(piece))
-    ctx = capi.Context(context_params if context_params is not None else rows[0], A, R, device=device)
+    ctx = capi.Context(context_params if context_params is not None else grid_context_params(rows), A, R, device=device)
     odo = None
     try:
         odo = ctx.odometry(len(rows))

@@ -387,9 +387,9 @@ int cfear_odometry_surface(cfear_ctx* ctx, cfear_odometry* odo, double res, int 
  * sweep, with the results of running each parameter set on its own.
  *
  * cfear_odometry_set_sequence_params: rows = n_sequences cfear_params, row q for sequence q (n_rows must be the object's n_sequences);
- * NULL: back to the context's parameters for all sequences. Per sequence: z_min, res, weight_intensity, loss, loss_limit, weight_opt,
- * covar_scale, regularization, compensate, use_keyframe, min_keyframe_dist, min_keyframe_rot_deg, max_itr_association, min_itr,
- * max_solver_iterations. Every other field (k_strongest, cost, submap_scan_size, filter_type, range_res, min_distance, downsample_factor,
+ * NULL: back to the context's parameters for all sequences. Per sequence: z_min, k_strongest (1 .. the context's, see below), res,
+ * weight_intensity, loss, loss_limit, weight_opt, covar_scale, regularization, compensate, use_keyframe, min_keyframe_dist,
+ * min_keyframe_rot_deg, max_itr_association, min_itr, max_solver_iterations. Every other field (cost, submap_scan_size, filter_type, range_res, min_distance, downsample_factor,
  * radar_ccw, assoc_radius, cfar_*; with filter_type CA-CFAR also z_min) sizes memory or selects a kernel and must equal the context's value
  * in every row: otherwise CFEAR_ERR_INVALID with a message that names the row and the field, and nothing is changed. Only on an object
  * that has processed no sweep since cfear_odometry_create / cfear_odometry_reset (CFEAR_ERR_INVALID otherwise); cfear_odometry_reset
@@ -399,6 +399,15 @@ int cfear_odometry_surface(cfear_ctx* ctx, cfear_odometry* odo, double res, int 
  * Per-sequence z_min: the k-strongest filter runs once per input sweep with the smallest z_min of the rows and each sequence drops the
  * slots below its own - exact, because intensity is the filter's primary sort key (the k strongest above z are the members above z of
  * the k strongest above any z' <= z). The peaks flag of a slot does depend on the kept set; no batched route reads it.
+ * Per-sequence k_strongest: the context's k_strongest K is what the filter runs with, once per input sweep, and what sizes the object
+ * (the slot buffers, the A * K points of a scan, the default cell capacity); a row may carry any k in 1..K and its sequence then gives,
+ * bit for bit, what an object created under a context with that k_strongest and otherwise equal parameters gives. Exact for the same
+ * reason: the filter keeps a bearing's C <= K largest (intensity, range) keys ascending in front of the bearing's K slots, and the keys are
+ * unique, so the k strongest are slots [max(C - k, 0), C), in the k-filter's own order; a sequence's cloud pass reads that window, and
+ * takes the compact or the general feature path by its own A * k. The cost: every row pays the filter pass and the memory of K - make
+ * the context's k_strongest the largest of the rows, no larger. A row with k_strongest < 1 or > K: CFEAR_ERR_INVALID (the message names
+ * the row and k_strongest); so is a k other than K on a filter_type CA-CFAR object (the detector has no k). While a row's k differs from
+ * K, cfear_odometry_step_cloud_device refuses to run (CFEAR_ERR_UNSUPPORTED: a cloud has no slots to take a window of).
  * Synchronises the context stream. */
 int cfear_odometry_set_sequence_params(cfear_ctx* ctx, cfear_odometry* odo, const cfear_params* rows, int n_rows);
 /* The parameter set sequence q runs with: its row, or the context's parameters without a table. */

@@ -6,7 +6,12 @@
 #   (b) identity table + identity map - the overhead of the lookups
 #   (c) a B-row grid (losses x limits x weights x res x z_min x weight_intensity), every sequence with its own copy of its sweep
 #   (d) the same grid on the shared sources: the filter runs on 64 sweeps per step instead of B, and 64 sweeps per step are resident
-# usage: python tools/gpu_param_grid.py > profiles/param_grid_steps.jsonl
+#   (e) the kstrong_vs_cfar axis (params/kstrong_vs_cfar/oxford-cfear-3-kstrong: k = 1 5 10 20 30 40 50) on the CFEAR-3 preset: the seven k of
+#       every recording as seven sequences of ONE object under K = 50 on the shared sources (7 x sources sequences; the filter runs once per
+#       recording, with k = 50, and 50 slots per bearing are resident for every row)
+#   (f) the same seven values as seven uniform objects, one per k, a sequence per recording (the filter runs once per recording and k)
+# CFEAR_GRID_LEGS: a comma-separated subset of a,b,c,d,e,f (default: all)
+# usage: python tools/gpu_param_grid.py >> profiles/param_grid_steps.jsonl
 import json, os, sys, time
 import numpy as np
 import torch
@@ -95,11 +100,32 @@ def main():
     base = capi.default_params(range_res=bench.RANGE_RES, **bench.PARAMS)
     rows = grid_rows(capi, replay, base, B)
     ident = [base] * B
-    leg(capi, "a_no_table", base, stream, B, S, d_frames, d_pre, idx, None, False, W, K, reps)
-    leg(capi, "b_identity_table", base, stream, B, S, d_frames, d_pre, idx, ident, False, W, K, reps)
-    leg(capi, "a_no_table_again", base, stream, B, S, d_frames, d_pre, idx, None, False, W, K, reps)  # (a)'s own spread between objects
-    leg(capi, "c_grid_replicated_frames", base, stream, B, S, d_frames, d_pre, idx, rows, False, W, K, reps)
-    leg(capi, "d_grid_shared_sources", base, stream, B, S, d_frames, d_pre, idx, rows, True, W, K, reps)
+    legs = os.environ.get("CFEAR_GRID_LEGS", "a,b,c,d,e,f").split(",")
+    if "a" in legs:
+        leg(capi, "a_no_table", base, stream, B, S, d_frames, d_pre, idx, None, False, W, K, reps)
+    if "b" in legs:
+        leg(capi, "b_identity_table", base, stream, B, S, d_frames, d_pre, idx, ident, False, W, K, reps)
+    if "a" in legs:
+        leg(capi, "a_no_table_again", base, stream, B, S, d_frames, d_pre, idx, None, False, W, K, reps)  # (a)'s own spread between objects
+    if "c" in legs:
+        leg(capi, "c_grid_replicated_frames", base, stream, B, S, d_frames, d_pre, idx, rows, False, W, K, reps)
+    if "d" in legs:
+        leg(capi, "d_grid_shared_sources", base, stream, B, S, d_frames, d_pre, idx, rows, True, W, K, reps)
+    # the kstrong_vs_cfar axis on the CFEAR-3 preset (bench.preset_legs cfear3_k40_p2p with k as the axis)
+    ks = [1, 5, 10, 20, 30, 40, 50]
+    cfear3 = capi.default_params(range_res=bench.RANGE_RES, **dict(bench.PARAMS, cost=0, submap_scan_size=4, res=3.0, weight_intensity=1, weight_opt=4))
+    if "e" in legs:
+        krows = replay.param_grid(cfear3, k_strongest=ks)
+        Bk = len(ks) * S
+        kidx = torch.from_numpy(np.arange(Bk) // len(ks)).to(dev)  # sequences 7 r .. 7 r + 6: the seven k of recording r
+        leg(capi, "e_k_grid_shared_sources_K50", replay.grid_context_params(krows), stream, Bk, S, d_frames, d_pre, kidx, [krows[q % len(ks)] for q in range(Bk)], True,
+            W, K, reps)
+    if "f" in legs:
+        sidx = torch.from_numpy(np.arange(S)).to(dev)
+        for k in ks:
+            pk = capi.Params.from_buffer_copy(cfear3)
+            pk.k_strongest = k
+            leg(capi, "f_uniform_object_k%d" % k, pk, stream, S, S, d_frames, d_pre, sidx, None, False, W, K, reps)
 
 
 if __name__ == "__main__":
