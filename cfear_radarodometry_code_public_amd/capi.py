@@ -91,7 +91,7 @@ assert DRIFT_DTYPE.itemsize == C.sizeof(Drift) == 184
 
 EXPORTS = [
     "cfear_version", "cfear_default_params", "cfear_create", "cfear_destroy", "cfear_last_error",
-    "cfear_set_params", "cfear_synchronize", "cfear_tune", "cfear_kstrongest_device", "cfear_kstrongest_host",
+    "cfear_set_params", "cfear_synchronize", "cfear_tune", "cfear_kstrongest_launch_shape", "cfear_kstrongest_device", "cfear_kstrongest_host",
     "cfear_rotate_polar", "cfear_rotate_polar_device", "cfear_filter_polar", "cfear_filter_polar_device", "cfear_filter_cfar", "cfear_filter_cfar_device", "cfear_filter_cfar_batch_device", "cfear_cloud_upload", "cfear_cloud_size",
     "cfear_cloud_download", "cfear_clouds_download", "cfear_cloud_release", "cfear_compensate", "cfear_compensate_pair", "cfear_scan_create",
     "cfear_scan_from_cells", "cfear_scan_release", "cfear_scan_size", "cfear_scan_download_cells", "cfear_scan_closest",
@@ -135,6 +135,7 @@ def lib():
         "cfear_set_params": (C.c_int, [vp, C.POINTER(Params)]),
         "cfear_synchronize": (C.c_int, [vp]),
         "cfear_tune": (C.c_int, [vp, C.c_int, C.c_int]),
+        "cfear_kstrongest_launch_shape": (C.c_int, [vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "cfear_kstrongest_device": (C.c_int, [vp, u8p, C.c_int, u32p]),
         "cfear_kstrongest_host": (C.c_int, [vp, u8p, C.c_int, u32p]),
         "cfear_rotate_polar": (C.c_int, [vp, u8p, C.c_int, C.c_int, u8p]),
@@ -335,6 +336,12 @@ class Context:
         self._tuned[k] = clamp.get(k, lambda x: x)(v)
 
     # ---- stage 1 ----
+    def kstrongest_launch_shape(self, n_scans):
+        """cfear_kstrongest_launch_shape: (rows_per_wave, workgroups, occupancy) of the filter launch for n_scans images under the current knobs"""
+        rows, wgs, occ = C.c_int(), C.c_int(), C.c_int()
+        self._check(self._L.cfear_kstrongest_launch_shape(self._h, int(n_scans), C.byref(rows), C.byref(wgs), C.byref(occ)), "cfear_kstrongest_launch_shape")
+        return rows.value, wgs.value, occ.value
+
     def kstrongest_host(self, polar):
         polar = np.ascontiguousarray(polar, dtype=np.uint8)
         if polar.ndim == 2:

@@ -23,6 +23,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "kstrongest_shape.h"
 
 // tools/build_k1_stop_variants.sh: profile builds whose row loop ends after phase n (1 load + LDS staging, 2 threshold search and
 // candidate masks, 3 candidates to lanes, 4 ranking; 0 = the product kernel); PMC counters of successive variants difference into
@@ -992,6 +993,22 @@ __global__ __launch_bounds__(256, 4) void kstrongest_pair_kernel(const uint8_t* 
 }  // namespace
 
 // Launch-shape knobs live in the context (cfear_tune, include/cfear_hip.h): occupancy variant and rows per wave.
+static cfear_k1_shape launch_shape_of(const cfear_ctx* ctx, int n_scans) {
+  static const bool pair = getenv("CFEAR_K1_PAIR") != nullptr && atoi(getenv("CFEAR_K1_PAIR")) != 0;  // the two-rows-at-once variant (A/B: tools/gpu_time_k1_pair.sh)
+  return cfear_k1_launch_shape(ctx->A, ctx->R, n_scans, ctx->tune_k1_occ, ctx->tune_k1_rows, pair);
+}
+
+int cfear_kstrongest_launch_shape(cfear_ctx* ctx, int n_scans, int* rows_per_wave, int* workgroups, int* occupancy) {
+  if (!ctx) return CFEAR_ERR_INVALID;
+  if (n_scans <= 0) return cfear_fail(ctx, CFEAR_ERR_INVALID, "kstrongest_launch_shape: n_scans <= 0");
+  const cfear_k1_shape s = launch_shape_of(ctx, n_scans);
+  if (s.nch == 0) return cfear_fail(ctx, CFEAR_ERR_UNSUPPORTED, "kstrongest: R > 16357 range bins not supported");
+  if (rows_per_wave) *rows_per_wave = s.rows_per_wave;
+  if (workgroups) *workgroups = (int)s.workgroups;
+  if (occupancy) *occupancy = s.occupancy;
+  return CFEAR_OK;
+}
+
 int cfear_launch_kstrongest(cfear_ctx* ctx, const uint8_t* d_polar, int n_scans, uint32_t* d_slots, hipStream_t stream, int u_zmin_override) {
   const int A = ctx->A, R = ctx->R, k = ctx->par.k_strongest;
   if (!d_polar || !d_slots || n_scans <= 0) return cfear_fail(ctx, CFEAR_ERR_INVALID, "kstrongest: null buffer or n_scans <= 0");
@@ -1001,42 +1018,22 @@ int cfear_launch_kstrongest(cfear_ctx* ctx, const uint8_t* d_polar, int n_scans,
   const long long alloc = n_rows * R;
   // float -> int (radar_filters.cpp:198) -> uchar (:212); a batched odometry object with per-sequence z_min filters with the smallest of them
   const int u_zmin = u_zmin_override >= 0 ? u_zmin_override : (int)(uint8_t)(int)ctx->par.z_min;
-  // one resident wave per SIMD slot (256 CUs x 4 SIMDs x occupancy); each wave walks consecutive rows
-  const int occ_eff = (R + 27 <= 4 * 1024) ? (ctx->tune_k1_occ >= 7 ? 7 : (ctx->tune_k1_occ <= 5 ? 5 : 6)) : (R + 27 <= 8 * 1024 ? 3 : 2);
-  // A wave walks a few consecutive rows (the threshold of one azimuth is the first guess for the next): four rows
-  // per wave measured best from 256-scan to 1024-scan launches (shorter: every row pays the cold threshold search;
-  // longer: fewer, longer workgroups balance worse), six from 1536 scans up (round 3, inside the bench's timed region at 4608
-  // scans: 1041 -> 1014 us, 0.754 -> 0.774 of the HBM peak; 8 and 12 the same, 16 worse at 1536). Small launches spread their
-  // rows over the resident slots.
-  const long long slots_total = 1024LL * occ_eff;
-  int rows_per_wave = (int)((n_rows + slots_total - 1) / slots_total);
-  const int rows_cap = ctx->tune_k1_rows > 0 ? ctx->tune_k1_rows : (n_scans >= 1536 ? 6 : 4);
-  if (rows_per_wave > rows_cap) rows_per_wave = rows_cap;
-  if (rows_per_wave < 1) rows_per_wave = 1;
-  static const bool pair = getenv("CFEAR_K1_PAIR") != nullptr && atoi(getenv("CFEAR_K1_PAIR")) != 0;  // the two-rows-at-once variant (A/B: tools/gpu_time_k1_pair.sh)
-  if (pair && rows_per_wave < 2) rows_per_wave = 2;  // (small launches too: a wave of the variant wants a pair)
-  const long long n_waves = (n_rows + rows_per_wave - 1) / rows_per_wave;
-  const long long blocks = (n_waves + 3) / 4;
-  dim3 grid((unsigned)blocks), block(256);
-  const int occ = ctx->tune_k1_occ;
-  if (pair && R + 27 <= 4 * 1024) {
+  const cfear_k1_shape s = launch_shape_of(ctx, n_scans);  // (kstrongest_shape.h: variant, rows per wave, workgroups)
+  const int rows_per_wave = s.rows_per_wave;
+  dim3 grid((unsigned)s.workgroups), block(256);
+  if (s.nch == 0) return cfear_fail(ctx, CFEAR_ERR_UNSUPPORTED, "kstrongest: R > 16357 range bins not supported");
+  if (s.pair_kernel)
     hipLaunchKernelGGL((kstrongest_pair_kernel<4>), grid, block, 0, stream, d_polar, d_slots, A, R, n_rows, u_zmin, k, alloc, rows_per_wave);
-    CFEAR_HIP_CHECK(ctx, hipGetLastError());
-    return CFEAR_OK;
-  }
-  if (R + 27 <= 4 * 1024) {
-    if (occ >= 7)
-      hipLaunchKernelGGL((kstrongest_kernel<4, 7>), grid, block, 0, stream, d_polar, d_slots, A, R, n_rows, u_zmin, k, alloc, rows_per_wave);
-    else if (occ <= 5)
-      hipLaunchKernelGGL((kstrongest_kernel<4, 5>), grid, block, 0, stream, d_polar, d_slots, A, R, n_rows, u_zmin, k, alloc, rows_per_wave);
-    else
-      hipLaunchKernelGGL((kstrongest_kernel<4, 6>), grid, block, 0, stream, d_polar, d_slots, A, R, n_rows, u_zmin, k, alloc, rows_per_wave);
-  } else if (R + 27 <= 8 * 1024)
+  else if (s.nch == 4 && s.occupancy == 7)
+    hipLaunchKernelGGL((kstrongest_kernel<4, 7>), grid, block, 0, stream, d_polar, d_slots, A, R, n_rows, u_zmin, k, alloc, rows_per_wave);
+  else if (s.nch == 4 && s.occupancy == 5)
+    hipLaunchKernelGGL((kstrongest_kernel<4, 5>), grid, block, 0, stream, d_polar, d_slots, A, R, n_rows, u_zmin, k, alloc, rows_per_wave);
+  else if (s.nch == 4)
+    hipLaunchKernelGGL((kstrongest_kernel<4, 6>), grid, block, 0, stream, d_polar, d_slots, A, R, n_rows, u_zmin, k, alloc, rows_per_wave);
+  else if (s.nch == 8)
     hipLaunchKernelGGL((kstrongest_kernel<8, 3>), grid, block, 0, stream, d_polar, d_slots, A, R, n_rows, u_zmin, k, alloc, rows_per_wave);
-  else if (R + 27 <= 16 * 1024)
-    hipLaunchKernelGGL((kstrongest_kernel<16, 2>), grid, block, 0, stream, d_polar, d_slots, A, R, n_rows, u_zmin, k, alloc, rows_per_wave);
   else
-    return cfear_fail(ctx, CFEAR_ERR_UNSUPPORTED, "kstrongest: R > 16357 range bins not supported");
+    hipLaunchKernelGGL((kstrongest_kernel<16, 2>), grid, block, 0, stream, d_polar, d_slots, A, R, n_rows, u_zmin, k, alloc, rows_per_wave);
   CFEAR_HIP_CHECK(ctx, hipGetLastError());
   return CFEAR_OK;
 }

@@ -133,6 +133,12 @@ enum { CFEAR_TUNE_FILTER_OCCUPANCY = 1, CFEAR_TUNE_FILTER_ROWS_PER_WAVE = 2, CFE
        CFEAR_TUNE_REPLAY_PERSISTENT_MAX = 4, CFEAR_TUNE_FILTER_CUS = 5, CFEAR_TUNE_REPEAT_SHORTCUT = 6, CFEAR_TUNE_MAX_CELLS = 7,
        CFEAR_TUNE_REGISTRATION_ORDER = 8, CFEAR_TUNE_LARGE_SUBMAP_KERNEL = 9, CFEAR_TUNE_NN_TIE_RULE = 10, CFEAR_TUNE_VOXEL_ORDER = 11 };
 int cfear_tune(cfear_ctx* ctx, int key, int value);
+/* The launch shape cfear_kstrongest_device / _host and the batched filters use for n_scans images of this context under its FILTER_OCCUPANCY
+ * and FILTER_ROWS_PER_WAVE knobs (the launcher calls the same arithmetic; no GPU work). One wave per resident slot (1024 SIMDs x occupancy), each
+ * walking rows_per_wave consecutive azimuth rows = min(cap, ceil(n_scans * A / (1024 * occupancy))); the cap is the ROWS_PER_WAVE knob, or 4, or 6
+ * from 1536 scans up (400 x 3360: 6 rows at 4608 scans, 4 at 1535, 1 at 5). workgroups = ceil(ceil(n_scans * A / rows_per_wave) / 4). occupancy =
+ * workgroups per compute unit the kernel is compiled for: the knob clamped to 5..7 up to R = 4069, 3 up to R = 8165, 2 beyond. Any output may be null. */
+int cfear_kstrongest_launch_shape(cfear_ctx* ctx, int n_scans, int* rows_per_wave, int* workgroups, int* occupancy);
 
 /* ---- Stage 1: StructuredKStrongest (radar_filters.cpp:198-298) -----------------------------
  * Packed slot: bits 0..15 range bin | 16..23 intensity | 24 valid | 25 peak (AxialNonMaxSupress).

@@ -144,7 +144,7 @@ def test_register_soft_matches_oracle(oracle, cost, sig):
 def test_scan_from_cells_round_trip_and_tune_knobs(oracle):
     """cfear_scan_from_cells (raw / transformed-copy maps are built on the host and handed over as cells): a scan rebuilt from the
     downloaded cells of another scan answers GetClosestIdx identically and registers identically; cfear_tune rejects unknown
-    keys and its launch-shape knobs do not change results."""
+    keys and its launch-shape knobs change the launch shape and not the results."""
     RRl = np.float32(0.0595238)
     imgs, _ = synth.world_sequence(3, seed=33)
     p = capi.default_params(range_res=RRl, res=3.0, weight_intensity=1, weight_opt=4)
@@ -172,6 +172,26 @@ def test_scan_from_cells_round_trip_and_tune_knobs(oracle):
     for occ, rows in ((5, 1), (6, 8), (7, 4)):
         ctx.tune(capi.TUNE_FILTER_OCCUPANCY, occ); ctx.tune(capi.TUNE_FILTER_ROWS_PER_WAVE, rows)
         assert np.array_equal(ctx.kstrongest_host(imgs[:2]), base)
+    # ... which at two sweeps (800 rows: one per wave whatever the cap) launches one shape three times. Many tiny sweeps on a second context: the
+    # three settings give three launch shapes - 1, 6 (ceil(35861 / 6144) under the cap of 8) and 4 rows per wave -, same slots, the oracle's
+    n, A2, R2 = 5123, 7, 37
+    rng = np.random.default_rng(7)
+    small = rng.integers(0, 256, size=(n * A2, R2), dtype=np.uint8)
+    quiet = (np.arange(n * A2) // 2) % 3 == 0  # two rows below z_min but for a few bins, four uniform rows, in turn
+    small[quiet] = np.where(rng.random((quiet.sum(), R2)) < 0.1, small[quiet], small[quiet] % 60)
+    small = small.reshape(n, A2, R2)
+    exp = np.stack([oracle.filter_polar(small[s], int(p.z_min), p.k_strongest) for s in range(n)])
+    ctx2 = capi.Context(p, A2, R2)
+    knobs = ((5, 1), (6, 8), (7, 4))
+    shapes = []
+    for occ, rows in knobs:
+        ctx2.tune(capi.TUNE_FILTER_OCCUPANCY, occ); ctx2.tune(capi.TUNE_FILTER_ROWS_PER_WAVE, rows)
+        shapes.append(ctx2.kstrongest_launch_shape(n))
+    assert [s[0] for s in shapes] == [1, 6, 4] and len(set(s[1] for s in shapes)) == 3 and [s[2] for s in shapes] == [5, 6, 7]
+    for occ, rows in knobs:
+        ctx2.tune(capi.TUNE_FILTER_OCCUPANCY, occ); ctx2.tune(capi.TUNE_FILTER_ROWS_PER_WAVE, rows)
+        assert np.array_equal(ctx2.kstrongest_host(small), exp)
+    ctx2.close()
     with pytest.raises(capi.CfearError):
         ctx.tune(99, 1)
     with pytest.raises(capi.CfearError):
