@@ -273,7 +273,7 @@ def _addr(a):
     return a.ctypes.data
 
 
-TUNE_FILTER_OCCUPANCY, TUNE_FILTER_ROWS_PER_WAVE, TUNE_ODOMETRY_OVERLAP, TUNE_REPLAY_PERSISTENT_MAX, TUNE_FILTER_CUS, TUNE_REPEAT_SHORTCUT, TUNE_MAX_CELLS, TUNE_REGISTRATION_ORDER, TUNE_LARGE_SUBMAP_KERNEL, TUNE_NN_TIE_RULE, TUNE_VOXEL_ORDER = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11
+TUNE_FILTER_OCCUPANCY, TUNE_FILTER_ROWS_PER_WAVE, TUNE_ODOMETRY_OVERLAP, TUNE_REPLAY_PERSISTENT_MAX, TUNE_FILTER_CUS, TUNE_REPEAT_SHORTCUT, TUNE_MAX_CELLS, TUNE_REGISTRATION_ORDER, TUNE_LARGE_SUBMAP_KERNEL, TUNE_NN_TIE_RULE, TUNE_VOXEL_ORDER, TUNE_FILTER_PEAKS = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12
 TUNE_DEFAULTS = {TUNE_ODOMETRY_OVERLAP: 0, TUNE_FILTER_CUS: 0, TUNE_MAX_CELLS: 0, TUNE_REGISTRATION_ORDER: 1, TUNE_LARGE_SUBMAP_KERNEL: 0}  # include/cfear_hip.h
 
 
@@ -324,7 +324,8 @@ class Context:
 
     def tune(self, key, value):
         """cfear_tune (include/cfear_hip.h): launch-shape knobs - TUNE_FILTER_OCCUPANCY, TUNE_FILTER_ROWS_PER_WAVE, TUNE_ODOMETRY_OVERLAP,
-        TUNE_FILTER_CUS, TUNE_REPLAY_PERSISTENT_MAX, TUNE_REPEAT_SHORTCUT, TUNE_REGISTRATION_ORDER: results do not depend on them - and
+        TUNE_FILTER_CUS, TUNE_REPLAY_PERSISTENT_MAX, TUNE_REPEAT_SHORTCUT, TUNE_REGISTRATION_ORDER: results do not depend on them -,
+        TUNE_FILTER_PEAKS (-1 automatic, 1 / 0: the filter always / never computes the slots' peak flag, bit 25) and
         TUNE_MAX_CELLS, the cell capacity batched odometry objects created afterwards are sized for (an overflow is reported, never silent)"""
         self._check(self._L.cfear_tune(self._h, int(key), int(value)), "cfear_tune")
         # what the library holds after its clamps (csrc/cabi.hip cfear_tune), so that a later restore puts back a value the context really had
@@ -332,7 +333,7 @@ class Context:
         clamp = {TUNE_FILTER_ROWS_PER_WAVE: lambda x: max(x, 0), TUNE_ODOMETRY_OVERLAP: lambda x: min(max(x, 0), 8), TUNE_FILTER_CUS: lambda x: max(x, 0),
                  TUNE_REGISTRATION_ORDER: lambda x: int(x != 0), TUNE_MAX_CELLS: lambda x: max(x, 0), TUNE_REPEAT_SHORTCUT: lambda x: int(x != 0),
                  TUNE_VOXEL_ORDER: lambda x: int(x == 1), TUNE_NN_TIE_RULE: lambda x: x if 0 <= x <= 2 else 0, TUNE_LARGE_SUBMAP_KERNEL: lambda x: x if 0 <= x <= 2 else 0,
-                 TUNE_REPLAY_PERSISTENT_MAX: lambda x: max(x, 0)}
+                 TUNE_REPLAY_PERSISTENT_MAX: lambda x: max(x, 0), TUNE_FILTER_PEAKS: lambda x: -1 if x < 0 else int(x != 0)}
         self._tuned[k] = clamp.get(k, lambda x: x)(v)
 
     # ---- stage 1 ----

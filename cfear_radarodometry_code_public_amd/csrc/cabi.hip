@@ -131,6 +131,7 @@ int cfear_tune(cfear_ctx* ctx, int key, int value) {
     case CFEAR_TUNE_FILTER_OCCUPANCY: ctx->tune_k1_occ = value; return CFEAR_OK;
     case CFEAR_TUNE_FILTER_ROWS_PER_WAVE: ctx->tune_k1_rows = value > 0 ? value : 0; return CFEAR_OK;
     case CFEAR_TUNE_ODOMETRY_OVERLAP: ctx->tune_odo_overlap = value < 0 ? 0 : (value > 8 ? 8 : value); return CFEAR_OK;
+    case CFEAR_TUNE_FILTER_PEAKS: ctx->tune_k1_peaks = value < 0 ? -1 : (value != 0); return CFEAR_OK;
     case CFEAR_TUNE_FILTER_CUS: ctx->tune_filter_cus = value < 0 ? 0 : value; return CFEAR_OK;
     case CFEAR_TUNE_REGISTRATION_ORDER: ctx->tune_reg_order = value != 0; return CFEAR_OK;
     case CFEAR_TUNE_MAX_CELLS: ctx->tune_max_cells = value < 0 ? 0 : value; return CFEAR_OK;
@@ -154,7 +155,7 @@ int cfear_synchronize(cfear_ctx* ctx) {
 int cfear_kstrongest_device(cfear_ctx* ctx, const uint8_t* d_polar, int n_scans, uint32_t* d_slots) {
   if (!ctx) return CFEAR_ERR_INVALID;
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  return cfear_launch_kstrongest(ctx, d_polar, n_scans, d_slots, ctx->stream);
+  return cfear_launch_kstrongest(ctx, d_polar, n_scans, d_slots, ctx->stream, true);
 }
 
 // ---- block pool of the per-call handles (clouds, scans) and the pinned staging of their downloads (common.h) ----
@@ -262,7 +263,7 @@ int cfear_kstrongest_host(cfear_ctx* ctx, const uint8_t* h_polar, int n_scans, u
   const size_t pb = (size_t)n_scans * ctx->A * ctx->R;
   const size_t sb = (size_t)n_scans * ctx->A * ctx->par.k_strongest * sizeof(uint32_t);
   CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_polar, h_polar, pb, hipMemcpyHostToDevice, ctx->stream));
-  rc = cfear_launch_kstrongest(ctx, ctx->d_polar, n_scans, ctx->d_slots, ctx->stream);
+  rc = cfear_launch_kstrongest(ctx, ctx->d_polar, n_scans, ctx->d_slots, ctx->stream, true);
   if (rc != CFEAR_OK) return rc;
   CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(h_slots, ctx->d_slots, sb, hipMemcpyDeviceToHost, ctx->stream));
   CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
@@ -274,12 +275,12 @@ int cfear_time_kstrongest(cfear_ctx* ctx, const uint8_t* d_polar, int n_scans, u
   if (!ctx || !avg_seconds || iters <= 0) return CFEAR_ERR_INVALID;
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   for (int i = 0; i < warmup; i++) {
-    int rc = cfear_launch_kstrongest(ctx, d_polar, n_scans, d_slots, ctx->stream);
+    int rc = cfear_launch_kstrongest(ctx, d_polar, n_scans, d_slots, ctx->stream, true);  // (the caller's buffer: with the flag)
     if (rc != CFEAR_OK) return rc;
   }
   CFEAR_HIP_CHECK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
   for (int i = 0; i < iters; i++) {
-    int rc = cfear_launch_kstrongest(ctx, d_polar, n_scans, d_slots, ctx->stream);
+    int rc = cfear_launch_kstrongest(ctx, d_polar, n_scans, d_slots, ctx->stream, true);  // (the caller's buffer: with the flag)
     if (rc != CFEAR_OK) return rc;
   }
   CFEAR_HIP_CHECK(ctx, hipEventRecord(ctx->ev1, ctx->stream));

@@ -73,6 +73,7 @@ struct cfear_ctx {
   // launch-shape knobs (cfear_tune): filter occupancy variant (5..7 waves per SIMD), rows walked per filter wave,
   // whether a batched odometry object created from now on runs its filter one sweep ahead on a stream of its own
   int tune_k1_occ = 7, tune_k1_rows = 0 /* 0 = by launch size: 4, or 6 from 1536 scans up */, tune_odo_overlap = 0;
+  int tune_k1_peaks = -1;  // FILTER_PEAKS: -1 = the filter computes the peak flag where a caller can see the slots or a peaks cloud, 1 = always, 0 = never
   int tune_filter_cus = 0;  // with ODOMETRY_OVERLAP: compute units reserved for the filter stream (CU-masked streams); 0 = no masks
   int tune_reg_order = 1;  // batched odometry objects created afterwards launch their registration workgroups longest first (keys: the previous sweep's work)
   int tune_max_cells = 0;  // batched odometry: oriented surface points per scan the scan blocks / match scratch are sized for (0 = A * k: every filtered point)
@@ -152,6 +153,7 @@ extern "C" __attribute__((visibility("hidden"))) int cfear_upload_image(cfear_ct
 extern "C" __attribute__((visibility("hidden"))) int cfear_cloud_alloc(cfear_ctx* ctx, int cap, cfear_cloud** out);
 // kstrongest.hip
 __attribute__((visibility("hidden"))) int cfear_launch_kstrongest(cfear_ctx* ctx, const uint8_t* d_polar, int n_scans, uint32_t* d_slots, hipStream_t stream,
+                                                                   bool peaks /* false: slots nobody reads bit 25 of (the batched odometry routes) - written 0, no suppression */,
                                                                    int u_zmin_override = -1 /* >= 0: this threshold instead of the context's z_min */);
 
 // cfar.hip

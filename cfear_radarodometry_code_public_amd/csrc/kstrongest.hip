@@ -245,7 +245,11 @@ __device__ __forceinline__ int tie_position(const uint8_t* win, int head, int R,
   return 0;
 }
 
-template <int NCH, int OCC>
+// PEAKS = false: the instantiation of the batched odometry routes (step, replay), whose cloud pass reads the valid bit, the range and the
+// intensity of a slot and never the peak flag: the row ends at the emit, bit 25 is written 0, and what only the suppression's reads need goes
+// with it - the scan masking of an image's first and last row and the 6 bytes past the row end (every other reader of the window, the
+// candidate's intensity byte and tie_position, stays inside the row). Bits 0..24 are the same in both instantiations.
+template <int NCH, int OCC, bool PEAKS>
 __global__ __launch_bounds__(256, OCC) void kstrongest_kernel(const uint8_t* __restrict__ polar,
                                                             uint32_t* __restrict__ slots, int A, int R,
                                                             long long n_rows, int u_zmin, int k,
@@ -291,24 +295,26 @@ __global__ __launch_bounds__(256, OCC) void kstrongest_kernel(const uint8_t* __r
     const long long row_off = g * (long long)R;
     const long long wstart_off = (row_off - 6) & ~15LL;     // may be -16 for the very first row
     const int head = (int)(row_off - wstart_off);           // 6..21: window offset of range bin 0
-    // chunks [c_lo, c_hi) are inside the allocation and needed (row + 6-byte halo either side)
+    // chunks [c_lo, c_hi) are inside the allocation and needed (row + 6-byte halo either side; without the suppression nothing past the row)
     const int c_lo = wstart_off >= 0 ? 0 : (int)((-wstart_off + 15) >> 4);
-    int c_hi = (head + R + 6 + 15) >> 4;
+    int c_hi = (head + R + (PEAKS ? 6 : 0) + 15) >> 4;
     {
       const long long lim = (alloc_bytes - wstart_off + 15) >> 4;
       if (lim < c_hi) c_hi = (int)lim;
     }
-    const bool edge_row = bearing == 0 || bearing == A - 1;
+    const bool edge_row = PEAKS && (bearing == 0 || bearing == A - 1);  // (the scan masking serves the suppression's halo reads only)
     const uint8_t* const wp = polar + wstart_off;  // wave-uniform
 
-    // ---- load: HBM -> VGPR and LDS (scan-masked on the first/last row, keeps the cross-row halo).
+    // ---- load: HBM -> VGPR and LDS (PEAKS: scan-masked on the first/last row, keeps the cross-row halo; without the suppression there is no
+    // halo to keep - c_hi ends at the row, edge_row is false and every row whose window starts inside the allocation takes the common path).
     // Branch-free: out-of-range chunks read a clamped (valid) address and are zeroed afterwards, so
     // the NCH loads of 1 KiB each are all in flight together.
     uint4 v[NCH];
     if (!edge_row && c_lo == 0) {
       // common case (398 of 400 azimuths): everything the window needs lies inside this scan's image. Chunks past
-      // the halo re-read the last needed chunk (no extra HBM traffic); what they hold is never looked at: the
-      // selection masks them (vtail) and the suppression reads at most 6 bytes past the row.
+      // the halo (PEAKS = false: past the row end) re-read the last needed chunk (no extra HBM traffic); what they hold is never looked
+      // at: the selection masks them (vhead / vtail), win[woff] and tie_position stay inside [head, head + R), and the suppression - the
+      // only reader outside the row, PEAKS only - reads at most 6 bytes past it.
 #pragma unroll
       for (int j = 0; j < NCH; j++) {
         const int cc = min(j * 64 + lane, c_hi - 1);
@@ -523,11 +529,12 @@ __global__ __launch_bounds__(256, OCC) void kstrongest_kernel(const uint8_t* __r
       }
       kept = lane < C && rank < kk;
     }
-    const int mpos = (int)(key & 0xFFFFu);
     K1_STOP_AT(4, key + (uint32_t)rank);
 
     // ---- axial non-max suppression (radar_filters.cpp:238-298) on the kept points ----
     uint32_t peak = 0;
+    if constexpr (PEAKS) {
+    const int mpos = (int)(key & 0xFFFFu);
     const bool interior = mpos >= 3 && mpos < R - 3;  // :251
     uint32_t covered = 0x7Fu;
     const bool edge_points = __ballot(kept && !interior) != 0;  // wave-uniform: a kept point within 3 bins of a row end (rare)
@@ -572,7 +579,7 @@ __global__ __launch_bounds__(256, OCC) void kstrongest_kernel(const uint8_t* __r
       int bv[13];
 #pragma unroll
       for (int t = 0; t < 13; t++) {
-        bv[t] = win[off0 + t];  // 0 <= off0 + t < WIN: head >= 6 and R + 27 <= WIN
+        bv[t] = win[off0 + t];  // 0 <= off0 + t < WIN: head >= 6 and R + 27 <= WIN (PEAKS only: the one read of the 6-byte halo either side of the row)
       }
       int sm[7];  // sm[u] = sum bv[u..u+6] (7-tap box, radar_filters.cpp:258-261)
       sm[0] = ((bv[0] + bv[1]) + (bv[2] + bv[3])) + ((bv[4] + bv[5]) + bv[6]);
@@ -589,6 +596,7 @@ __global__ __launch_bounds__(256, OCC) void kstrongest_kernel(const uint8_t* __r
         if (sm[3 - i] > sm[3] || sm[3] < sm[3 + i]) largest = false;  // :282
       }
       peak = largest ? (1u << 25) : 0u;
+    }
     }
     // ---- emit: ascending (intensity, range), unused slots 0 ----
     uint32_t* out = slots + g * (long long)k;
@@ -1009,7 +1017,18 @@ int cfear_kstrongest_launch_shape(cfear_ctx* ctx, int n_scans, int* rows_per_wav
   return CFEAR_OK;
 }
 
-int cfear_launch_kstrongest(cfear_ctx* ctx, const uint8_t* d_polar, int n_scans, uint32_t* d_slots, hipStream_t stream, int u_zmin_override) {
+// peaks: whether the caller's slots carry the suppression's flag (bit 25); the context's FILTER_PEAKS knob overrides it. (The two-rows-at-once
+// variant below, CFEAR_K1_PAIR=1, exists with the suppression only: under it neither the argument nor the knob applies and bit 25 is always computed.)
+template <int NCH, int OCC>
+static void launch_k1(bool peaks, dim3 grid, hipStream_t stream, const uint8_t* d_polar, uint32_t* d_slots, int A, int R, long long n_rows, int u_zmin, int k,
+                      long long alloc, int rows_per_wave) {
+  if (peaks)
+    hipLaunchKernelGGL((kstrongest_kernel<NCH, OCC, true>), grid, dim3(256), 0, stream, d_polar, d_slots, A, R, n_rows, u_zmin, k, alloc, rows_per_wave);
+  else
+    hipLaunchKernelGGL((kstrongest_kernel<NCH, OCC, false>), grid, dim3(256), 0, stream, d_polar, d_slots, A, R, n_rows, u_zmin, k, alloc, rows_per_wave);
+}
+
+int cfear_launch_kstrongest(cfear_ctx* ctx, const uint8_t* d_polar, int n_scans, uint32_t* d_slots, hipStream_t stream, bool peaks, int u_zmin_override) {
   const int A = ctx->A, R = ctx->R, k = ctx->par.k_strongest;
   if (!d_polar || !d_slots || n_scans <= 0) return cfear_fail(ctx, CFEAR_ERR_INVALID, "kstrongest: null buffer or n_scans <= 0");
   if (k < 1 || k > 64) return cfear_fail(ctx, CFEAR_ERR_UNSUPPORTED, "kstrongest: k_strongest must be in 1..64");
@@ -1020,20 +1039,21 @@ int cfear_launch_kstrongest(cfear_ctx* ctx, const uint8_t* d_polar, int n_scans,
   const int u_zmin = u_zmin_override >= 0 ? u_zmin_override : (int)(uint8_t)(int)ctx->par.z_min;
   const cfear_k1_shape s = launch_shape_of(ctx, n_scans);  // (kstrongest_shape.h: variant, rows per wave, workgroups)
   const int rows_per_wave = s.rows_per_wave;
+  if (ctx->tune_k1_peaks >= 0) peaks = ctx->tune_k1_peaks != 0;
   dim3 grid((unsigned)s.workgroups), block(256);
   if (s.nch == 0) return cfear_fail(ctx, CFEAR_ERR_UNSUPPORTED, "kstrongest: R > 16357 range bins not supported");
   if (s.pair_kernel)
     hipLaunchKernelGGL((kstrongest_pair_kernel<4>), grid, block, 0, stream, d_polar, d_slots, A, R, n_rows, u_zmin, k, alloc, rows_per_wave);
   else if (s.nch == 4 && s.occupancy == 7)
-    hipLaunchKernelGGL((kstrongest_kernel<4, 7>), grid, block, 0, stream, d_polar, d_slots, A, R, n_rows, u_zmin, k, alloc, rows_per_wave);
+    launch_k1<4, 7>(peaks, grid, stream, d_polar, d_slots, A, R, n_rows, u_zmin, k, alloc, rows_per_wave);
   else if (s.nch == 4 && s.occupancy == 5)
-    hipLaunchKernelGGL((kstrongest_kernel<4, 5>), grid, block, 0, stream, d_polar, d_slots, A, R, n_rows, u_zmin, k, alloc, rows_per_wave);
+    launch_k1<4, 5>(peaks, grid, stream, d_polar, d_slots, A, R, n_rows, u_zmin, k, alloc, rows_per_wave);
   else if (s.nch == 4)
-    hipLaunchKernelGGL((kstrongest_kernel<4, 6>), grid, block, 0, stream, d_polar, d_slots, A, R, n_rows, u_zmin, k, alloc, rows_per_wave);
+    launch_k1<4, 6>(peaks, grid, stream, d_polar, d_slots, A, R, n_rows, u_zmin, k, alloc, rows_per_wave);
   else if (s.nch == 8)
-    hipLaunchKernelGGL((kstrongest_kernel<8, 3>), grid, block, 0, stream, d_polar, d_slots, A, R, n_rows, u_zmin, k, alloc, rows_per_wave);
+    launch_k1<8, 3>(peaks, grid, stream, d_polar, d_slots, A, R, n_rows, u_zmin, k, alloc, rows_per_wave);
   else
-    hipLaunchKernelGGL((kstrongest_kernel<16, 2>), grid, block, 0, stream, d_polar, d_slots, A, R, n_rows, u_zmin, k, alloc, rows_per_wave);
+    launch_k1<16, 2>(peaks, grid, stream, d_polar, d_slots, A, R, n_rows, u_zmin, k, alloc, rows_per_wave);
   CFEAR_HIP_CHECK(ctx, hipGetLastError());
   return CFEAR_OK;
 }

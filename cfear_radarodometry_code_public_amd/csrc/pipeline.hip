@@ -853,7 +853,7 @@ int cfear_filter_polar_device(cfear_ctx* ctx, const uint8_t* d_polar, cfear_clou
   if (cloud_peaks) *cloud_peaks = nullptr;
   int rc = cfear_ensure_staging(ctx, 1);
   if (rc != CFEAR_OK) return rc;
-  rc = cfear_launch_kstrongest(ctx, d_polar, 1, ctx->d_slots, ctx->stream);  // radar_driver.cpp:58
+  rc = cfear_launch_kstrongest(ctx, d_polar, 1, ctx->d_slots, ctx->stream, true);  // radar_driver.cpp:58 (with the flag: the peaks cloud reads it)
   if (rc != CFEAR_OK) return rc;
   const int A = ctx->A, k = ctx->par.k_strongest, cap = A * k;
   cfear_cloud *c0 = nullptr, *c1 = nullptr;  // radar_driver.cpp:59-60
@@ -1745,7 +1745,7 @@ int cfear_odometry_step_device(cfear_ctx* ctx, cfear_odometry* o, const uint8_t*
   }
   // radar_driver.cpp:58
   if (o->profile && (rc = odo_timed_event(ctx, o, o->filter_events, sf)) != CFEAR_OK) return rc;
-  rc = cfear_launch_kstrongest(ctx, d_polar, odo_sources(o), o->d_slots[buf], sf, o->seq_zmin);  // (once per source sweep, at the smallest z_min of the rows)
+  rc = cfear_launch_kstrongest(ctx, d_polar, odo_sources(o), o->d_slots[buf], sf, false, o->seq_zmin);  // (once per source sweep, at the smallest z_min of the rows; no peak flag: cloud_step_block does not read it)
   if (rc != CFEAR_OK) return rc;
   if (o->profile && (rc = odo_timed_event(ctx, o, o->filter_events, sf)) != CFEAR_OK) return rc;
   if (o->overlap) {
@@ -1958,7 +1958,7 @@ static int replay_impl_queue(cfear_ctx* ctx, cfear_odometry* o, const uint8_t* f
       src = o->rp_polar[b];
     }
     const int frc = cfar ? odo_launch_cfar(ctx, o, src, cnt * o->B, o->rp_cloud[b], o->rp_cloud_n[b], o->rp_cfar_rows, o->rp_stream)  // radar_driver.cpp:52-56
-                         : cfear_launch_kstrongest(ctx, src, cnt * nsrc, o->rp_slots[b], o->rp_stream, o->seq_zmin);  // radar_driver.cpp:58, pose-independent
+                         : cfear_launch_kstrongest(ctx, src, cnt * nsrc, o->rp_slots[b], o->rp_stream, false, o->seq_zmin);  // radar_driver.cpp:58, pose-independent
     if (frc != CFEAR_OK) return frc;
     CFEAR_HIP_CHECK(ctx, hipEventRecord(o->rp_filt[b], o->rp_stream));
     return CFEAR_OK;

@@ -128,10 +128,17 @@ int cfear_synchronize(cfear_ctx* ctx);
  * and the centroid's last bit, which now and then flips a point across the strict d^2 < r^2 of the radius search - belongs to the sort
  * routine: std::sort up to PCL 1.9 (Ubuntu 18.04), boost integer_sort from 1.10. 0 = by point index (production: what a stable sort gives);
  * 1 = exactly what libstdc++'s std::sort leaves, computed on the host by the same call on the same sequence - per-call scans only
- * (cfear_scan_create; batched odometry objects refuse the mode: it costs a host round trip per scan). */
+ * (cfear_scan_create; batched odometry objects refuse the mode: it costs a host round trip per scan).
+ * FILTER_PEAKS (default -1 = automatic): whether the k-strongest filter runs AxialNonMaxSupress and sets the peak flag, bit 25 of a slot. Automatic:
+ * every entry that hands slots or a peaks cloud to the caller computes it (cfear_kstrongest_device / _host, cfear_time_kstrongest, cfear_filter_polar*);
+ * the filters inside cfear_odometry_step_* / _replay_* do not - their slot buffers are internal and the cloud pass of those routes reads the valid
+ * bit, the range and the intensity only, as the reference's odometry never reads cloud_peaks - and leave the bit 0. 1 = always computed, 0 = never
+ * (the per-call entries included: their peak bits are then 0 and a peaks cloud is empty; for A/B timing and tests). Bits 0..24 do not depend on it. The knob
+ * does not reach the experimental two-rows-at-once kernel (environment CFEAR_K1_PAIR=1), which exists with the suppression only and always sets the bit. */
 enum { CFEAR_TUNE_FILTER_OCCUPANCY = 1, CFEAR_TUNE_FILTER_ROWS_PER_WAVE = 2, CFEAR_TUNE_ODOMETRY_OVERLAP = 3,
        CFEAR_TUNE_REPLAY_PERSISTENT_MAX = 4, CFEAR_TUNE_FILTER_CUS = 5, CFEAR_TUNE_REPEAT_SHORTCUT = 6, CFEAR_TUNE_MAX_CELLS = 7,
-       CFEAR_TUNE_REGISTRATION_ORDER = 8, CFEAR_TUNE_LARGE_SUBMAP_KERNEL = 9, CFEAR_TUNE_NN_TIE_RULE = 10, CFEAR_TUNE_VOXEL_ORDER = 11 };
+       CFEAR_TUNE_REGISTRATION_ORDER = 8, CFEAR_TUNE_LARGE_SUBMAP_KERNEL = 9, CFEAR_TUNE_NN_TIE_RULE = 10, CFEAR_TUNE_VOXEL_ORDER = 11,
+       CFEAR_TUNE_FILTER_PEAKS = 12 };
 int cfear_tune(cfear_ctx* ctx, int key, int value);
 /* The launch shape cfear_kstrongest_device / _host and the batched filters use for n_scans images of this context under its FILTER_OCCUPANCY
  * and FILTER_ROWS_PER_WAVE knobs (the launcher calls the same arithmetic; no GPU work). One wave per resident slot (1024 SIMDs x occupancy), each
@@ -142,7 +149,9 @@ int cfear_kstrongest_launch_shape(cfear_ctx* ctx, int n_scans, int* rows_per_wav
 
 /* ---- Stage 1: StructuredKStrongest (radar_filters.cpp:198-298) -----------------------------
  * Packed slot: bits 0..15 range bin | 16..23 intensity | 24 valid | 25 peak (AxialNonMaxSupress).
- * Per azimuth row k slots in ascending (intensity, range) order, unused slots = 0. */
+ * Per azimuth row k slots in ascending (intensity, range) order, unused slots = 0.
+ * Bit 25 is set in the slots these entry points return. The internal slot buffers of the batched odometry routes (step, replay) are
+ * filtered without the suppression and hold 0 there (cfear_tune FILTER_PEAKS). */
 #define CFEAR_SLOT_RANGE(s) ((int)((s) & 0xFFFFu))
 #define CFEAR_SLOT_INTENSITY(s) ((int)(((s) >> 16) & 0xFFu))
 #define CFEAR_SLOT_VALID(s) ((int)(((s) >> 24) & 1u))
