@@ -8,17 +8,15 @@ source cells against one block of threads, keyframes against one group, tiles ag
 prints what it saw ("[regime] ..."; pytest -rA shows the lines)."""
 import math
 import os
-import re
 
 import numpy as np
 import pytest
 
 import surface_ref
+from match_caps import CSRC, LDS_CAP, REG_BLOCK, _define  # the LDS match array's capacities per cost, one block of source cells
 from cfear_radarodometry_code_public_amd import capi, synth
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "cfear_radarodometry_code_public_amd", "csrc")
 A, R, RR = 400, 3360, np.float32(0.0595238)
 BASE = dict(range_res=RR, k_strongest=12, z_min=60.0, res=3.0, weight_intensity=1, loss_limit=0.1)
 PRIOR = np.diag([0.05 ** 2, 0.04 ** 2, 1.0, 1.0, 1.0, 0.01 ** 2])
@@ -26,17 +24,6 @@ CFAR = dict(window_size=40, nb_guard_cells=10, false_alarm_rate=0.01)
 COST_NAME = {0: "P2P", 1: "P2L", 2: "P2D"}
 
 
-def _define(header, name):
-    m = re.search(r"^#define\s+%s\s+(\d+)\s*(?://.*)?$" % name, open(os.path.join(CSRC, header)).read(), re.M)
-    assert m, name
-    return int(m.group(1))
-
-
-# match_lds_cap(cost) of registration_dev.h: the LDS match array holds 8 doubles x CFEAR_MATCH_LDS_CAP, of which P2D keeps eight
-# arrays, P2L seven and P2P five (match_lds_arrays)
-_LDS_DOUBLES = 8 * _define("registration_dev.h", "CFEAR_MATCH_LDS_CAP")
-LDS_CAP = {2: _LDS_DOUBLES // 8, 1: _LDS_DOUBLES // 7, 0: _LDS_DOUBLES // 5}
-REG_BLOCK = _define("registration_dev.h", "CFEAR_REG_BLOCK")  # BLOCK_R: one block of source cells (association path 1)
 SURF_BLOCK = _define("surface_dev.h", "CFEAR_SURFACE_BLOCK")
 SURF_CHUNK = _define("surface_dev.h", "CFEAR_SURFACE_CHUNK")
 

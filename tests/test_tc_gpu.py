@@ -14,6 +14,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import match_caps
 import tc_ref
 from cfear_radarodometry_code_public_amd import capi, synth
 
@@ -28,7 +29,7 @@ VELS = [(1.0, 0.1, 0.02), (3.5, -0.4, 0.1), (-2.0, 0.5, -0.3)]
 LARGEST = 1  # (3.5, -0.4, 0.1)
 P2P, P2L, P2D = 0, 1, 2
 HUBER, CAUCHY = 1, 2
-MATCH_LDS_CAP = 622  # CFEAR_MATCH_LDS_CAP: residual blocks the LDS match array holds
+MATCH_LDS_CAP = match_caps.LDS_CAP[P2D]  # CFEAR_MATCH_LDS_CAP: residual blocks the LDS match array holds (622)
 
 
 class World:
