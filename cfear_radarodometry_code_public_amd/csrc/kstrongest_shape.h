@@ -5,14 +5,13 @@
 
 struct cfear_k1_shape {
   int nch;            // 16-byte chunk groups of the row window held per lane: 4, 8 or 16 (0: R + 27 > 16 KiB, no kernel)
-  int occupancy;      // launch bound (workgroups per compute unit) of the kernel that runs: 7 / 6 / 5, 3 (nch 8), 2 (nch 16), 4 (the pair variant)
-  bool pair_kernel;   // kstrongest_pair_kernel instead of kstrongest_kernel
+  int occupancy;      // launch bound (workgroups per compute unit) of the kernel that runs: 7 / 6 / 5, 3 (nch 8), 2 (nch 16)
   int rows_per_wave;  // consecutive rows a wave walks
   long long workgroups;  // of 256 threads = four waves
 };
 
-// tune_occ / tune_rows: the context's CFEAR_TUNE_FILTER_OCCUPANCY / CFEAR_TUNE_FILTER_ROWS_PER_WAVE; pair: the CFEAR_K1_PAIR switch
-static inline cfear_k1_shape cfear_k1_launch_shape(int A, int R, int n_scans, int tune_occ, int tune_rows, bool pair) {
+// tune_occ / tune_rows: the context's CFEAR_TUNE_FILTER_OCCUPANCY / CFEAR_TUNE_FILTER_ROWS_PER_WAVE
+static inline cfear_k1_shape cfear_k1_launch_shape(int A, int R, int n_scans, int tune_occ, int tune_rows) {
   cfear_k1_shape s;
   const long long n_rows = (long long)n_scans * A;
   s.nch = R + 27 <= 4 * 1024 ? 4 : (R + 27 <= 8 * 1024 ? 8 : (R + 27 <= 16 * 1024 ? 16 : 0));
@@ -28,9 +27,7 @@ static inline cfear_k1_shape cfear_k1_launch_shape(int A, int R, int n_scans, in
   const int rows_cap = tune_rows > 0 ? tune_rows : (n_scans >= 1536 ? 6 : 4);
   if (rows_per_wave > rows_cap) rows_per_wave = rows_cap;
   if (rows_per_wave < 1) rows_per_wave = 1;
-  if (pair && rows_per_wave < 2) rows_per_wave = 2;  // (small launches too: a wave of the variant wants a pair)
-  s.pair_kernel = pair && s.nch == 4;  // (the variant exists for the 4 KiB window only; longer rows keep the rows per wave it asked for)
-  s.occupancy = s.pair_kernel ? 4 : occ_eff;
+  s.occupancy = occ_eff;
   s.rows_per_wave = rows_per_wave;
   const long long n_waves = (n_rows + rows_per_wave - 1) / rows_per_wave;
   s.workgroups = (n_waves + 3) / 4;

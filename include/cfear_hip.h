@@ -133,8 +133,7 @@ int cfear_synchronize(cfear_ctx* ctx);
  * every entry that hands slots or a peaks cloud to the caller computes it (cfear_kstrongest_device / _host, cfear_time_kstrongest, cfear_filter_polar*);
  * the filters inside cfear_odometry_step_* / _replay_* do not - their slot buffers are internal and the cloud pass of those routes reads the valid
  * bit, the range and the intensity only, as the reference's odometry never reads cloud_peaks - and leave the bit 0. 1 = always computed, 0 = never
- * (the per-call entries included: their peak bits are then 0 and a peaks cloud is empty; for A/B timing and tests). Bits 0..24 do not depend on it. The knob
- * does not reach the experimental two-rows-at-once kernel (environment CFEAR_K1_PAIR=1), which exists with the suppression only and always sets the bit. */
+ * (the per-call entries included: their peak bits are then 0 and a peaks cloud is empty; for A/B timing and tests). Bits 0..24 do not depend on it. */
 enum { CFEAR_TUNE_FILTER_OCCUPANCY = 1, CFEAR_TUNE_FILTER_ROWS_PER_WAVE = 2, CFEAR_TUNE_ODOMETRY_OVERLAP = 3,
        CFEAR_TUNE_REPLAY_PERSISTENT_MAX = 4, CFEAR_TUNE_FILTER_CUS = 5, CFEAR_TUNE_REPEAT_SHORTCUT = 6, CFEAR_TUNE_MAX_CELLS = 7,
        CFEAR_TUNE_REGISTRATION_ORDER = 8, CFEAR_TUNE_LARGE_SUBMAP_KERNEL = 9, CFEAR_TUNE_NN_TIE_RULE = 10, CFEAR_TUNE_VOXEL_ORDER = 11,

@@ -1,8 +1,6 @@
 """GPU parity: HIP k-strongest + peaks (through the C ABI) vs the CPU oracle, bit-exact.
 
 Reference behaviour: radar_filters.cpp:209-298."""
-import os
-
 import numpy as np
 import pytest
 
@@ -139,7 +137,6 @@ def test_kept_points_at_the_row_ends(oracle, R, k):
 # cfear_kstrongest_launch_shape); the wave carries the selection threshold (Tprev) and its place in the scan from row to row. Every case above
 # has at most 2000 rows: one row per wave, a fresh threshold, no scan boundary inside a wave. The cases below reach r rows with many tiny
 # scans (n_rows > (r - 1) * 1024 * occupancy), assert the r they meant through the read-back and then compare bit for bit with the oracle.
-PAIR = os.environ.get("CFEAR_K1_PAIR", "0") not in ("", "0")  # the child run of test_two_rows_at_once_variant_is_bit_exact
 
 # (n_scans, occupancy knob, rows knob, rows per wave) at A = 7 (and any R up to 4069): n_rows = 7 n in ((r - 1) * 1024 * occ, r * 1024 * occ],
 # and no multiple of 4 r: the last wave and the last workgroup are partial. 7 against 5 or 8 rows puts the scan wrap at every phase of a wave.
@@ -166,8 +163,7 @@ def run_rows(oracle, img, k, z_min, settings, partial=True):
             got_rows, wgs, got_occ = ctx.kstrongest_launch_shape(n)
             assert got_rows == rows, "meant %d rows per wave, the launch has %d (A=%d R=%d n=%d occ=%s cap=%s)" % (rows, got_rows, A, R, n, occ, cap)
             assert wgs == ceil_div(ceil_div(n * A, rows), 4)
-            if not PAIR:
-                assert got_occ == ((7 if occ is None else occ) if R + 27 <= 4096 else (3 if R + 27 <= 8192 else 2))
+            assert got_occ == ((7 if occ is None else occ) if R + 27 <= 4096 else (3 if R + 27 <= 8192 else 2))
             if partial:
                 assert (n * A) % (rows * 4) != 0
             got = ctx.kstrongest_host(img[:n])
@@ -442,34 +438,19 @@ def test_launch_shape_read_back(hip_lib):
     """cfear_kstrongest_launch_shape on a context, against the shapes include/cfear_hip.h states (tests/test_filter_shape_cpu.py: the same
     arithmetic without a GPU)"""
     ctx = capi.Context(capi.default_params(), 400, 3360)
-    lo = 2 if PAIR else 1  # (the pair variant never gives a wave fewer than two rows)
-    assert [ctx.kstrongest_launch_shape(n)[:2] for n in (4608, 1535, 1536, 5)] == [(6, 76800), (4, 38375), (6, 25600), (lo, 500 // lo)]
-    for cap, rows in ((1, lo), (3, 3), (8, 8), (300, 258)):
+    assert [ctx.kstrongest_launch_shape(n)[:2] for n in (4608, 1535, 1536, 5)] == [(6, 76800), (4, 38375), (6, 25600), (1, 500)]
+    for cap, rows in ((1, 1), (3, 3), (8, 8), (300, 258)):
         ctx.tune(capi.TUNE_FILTER_ROWS_PER_WAVE, cap)
-        assert ctx.kstrongest_launch_shape(4608)[0] == rows and ctx.kstrongest_launch_shape(5)[0] == lo
+        assert ctx.kstrongest_launch_shape(4608)[0] == rows and ctx.kstrongest_launch_shape(5)[0] == 1
     ctx.tune(capi.TUNE_FILTER_ROWS_PER_WAVE, 0)
-    if not PAIR:
-        for knob, occ in ((4, 5), (5, 5), (6, 6), (7, 7), (9, 7)):
-            ctx.tune(capi.TUNE_FILTER_OCCUPANCY, knob)
-            assert ctx.kstrongest_launch_shape(64)[2] == occ
+    for knob, occ in ((4, 5), (5, 5), (6, 6), (7, 7), (9, 7)):
+        ctx.tune(capi.TUNE_FILTER_OCCUPANCY, knob)
+        assert ctx.kstrongest_launch_shape(64)[2] == occ
     with pytest.raises(capi.CfearError):
         ctx.kstrongest_launch_shape(0)
     ctx.close()
     for R, occ in ((5000, 3), (9000, 2)):
         ctx = capi.Context(capi.default_params(), 9, R)
-        assert ctx.kstrongest_launch_shape(9) == (lo, ceil_div(ceil_div(81, lo), 4), occ)
+        assert ctx.kstrongest_launch_shape(9) == (1, ceil_div(81, 4), occ)
         ctx.close()
 
-
-def test_two_rows_at_once_variant_is_bit_exact(tmp_path):
-    """kstrongest_pair_kernel (csrc/kstrongest.hip, round 6: the phases after the selection once per pair of rows; off by default because it is slower -
-    DESIGN.md Appendix A.1) is selected by CFEAR_K1_PAIR=1, read once per process: a child process runs this file's bit-exactness cases under the switch."""
-    import os
-    import subprocess
-    import sys
-    env = dict(os.environ, CFEAR_K1_PAIR="1")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(root, "tests", "test_kstrongest_gpu.py"), "-x", "-q", "-m", "gpu",
-                        "-k", "not two_rows_at_once", "-p", "no:cacheprovider"], env=env, cwd=root, capture_output=True, text=True, timeout=1200)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    assert " passed" in r.stdout and "failed" not in r.stdout
