@@ -46,6 +46,14 @@ class FuserOptions(C.Structure):
         return "FuserOptions(soft_constraint=%d, use_guess=%d)" % (self.soft_constraint, self.use_guess)
 
 
+class SeqShape(C.Structure):
+    """cfear_seq_shape (include/cfear_hip.h): the cost metric and the submap_scan_size of one sequence of a batched odometry object"""
+    _fields_ = [("cost", C.c_int32), ("submap_scan_size", C.c_int32)]
+
+    def __repr__(self):
+        return "SeqShape(cost=%d, submap_scan_size=%d)" % (self.cost, self.submap_scan_size)
+
+
 class Cell(C.Structure):
     _fields_ = [
         ("mean", C.c_double * 2), ("cov", C.c_double * 3), ("normal", C.c_double * 2),
@@ -102,6 +110,7 @@ EXPORTS = [
     "cfear_surface_dims", "cfear_get_surface", "cfear_odometry_set_surface_recording", "cfear_odometry_surface",
     "cfear_odometry_set_sequence_params", "cfear_odometry_sequence_params", "cfear_odometry_set_sequence_sources",
     "cfear_default_fuser_options", "cfear_odometry_set_fuser_options", "cfear_odometry_fuser_options",
+    "cfear_odometry_set_sequence_shapes", "cfear_odometry_sequence_shape",
     "cfear_odometry_covariances", "cfear_odometry_status", "cfear_odometry_summary", "cfear_odometry_profile", "cfear_odometry_profile_read", "cfear_odometry_profile_read_stages", "cfear_odometry_phase_times", "cfear_time_kstrongest",
     "cfear_drift_segments", "cfear_drift_plan_create", "cfear_drift_plan_release", "cfear_drift_device", "cfear_drift_host",
 ]
@@ -186,6 +195,8 @@ def lib():
         "cfear_odometry_set_sequence_params": (C.c_int, [vp, vp, vp, C.c_int]),
         "cfear_odometry_sequence_params": (C.c_int, [vp, vp, C.c_int, C.POINTER(Params)]),
         "cfear_odometry_set_sequence_sources": (C.c_int, [vp, vp, i32p, C.c_int, C.c_int]),
+        "cfear_odometry_set_sequence_shapes": (C.c_int, [vp, vp, vp, C.c_int]),
+        "cfear_odometry_sequence_shape": (C.c_int, [vp, vp, C.c_int, C.POINTER(SeqShape)]),
         "cfear_default_fuser_options": (None, [C.POINTER(FuserOptions)]),
         "cfear_odometry_set_fuser_options": (C.c_int, [vp, vp, vp, C.c_int]),
         "cfear_odometry_fuser_options": (C.c_int, [vp, vp, C.c_int, C.POINTER(FuserOptions)]),
@@ -782,6 +793,24 @@ class Odometry:
         self._ctx._check(self._ctx._L.cfear_odometry_set_sequence_sources(self._ctx._h, self._h, src.ctypes.data, int(src.size), ns),
                          "cfear_odometry_set_sequence_sources")
         self.n_sources = ns
+
+    def set_sequence_shapes(self, shapes):
+        """shapes: one SeqShape (or (cost, submap_scan_size) pair) per sequence - the cost metric and the submap size it runs with, any
+        submap_scan_size up to the context's - or None for the context's values again (cfear_odometry_set_sequence_shapes). Before the first
+        sweep since creation / reset(), and before a parameter table whose rows carry these values."""
+        fn, c = self._ctx._L.cfear_odometry_set_sequence_shapes, self._ctx
+        if shapes is None:
+            c._check(fn(c._h, self._h, None, 0), "cfear_odometry_set_sequence_shapes")
+            return
+        shapes = [s if isinstance(s, SeqShape) else SeqShape(int(s[0]), int(s[1])) for s in shapes]
+        arr = (SeqShape * len(shapes))(*shapes)
+        c._check(fn(c._h, self._h, C.cast(arr, C.c_void_p), len(shapes)), "cfear_odometry_set_sequence_shapes")
+
+    def sequence_shape(self, q):
+        """the SeqShape sequence q runs with (cfear_odometry_sequence_shape)"""
+        s = SeqShape()
+        self._ctx._check(self._ctx._L.cfear_odometry_sequence_shape(self._ctx._h, self._h, int(q), C.byref(s)), "cfear_odometry_sequence_shape")
+        return s
 
     def set_fuser_options(self, rows):
         """rows: one FuserOptions for every sequence, a list of one per sequence, or None for the defaults again

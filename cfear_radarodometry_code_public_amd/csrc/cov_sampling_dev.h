@@ -179,7 +179,7 @@ __device__ inline void cov_sample_body(unsigned char* lds, int q, const OdoParam
           if (tid == 0) {  // waves in order: a fixed summation order
             double tot = 0.0; int M = 0;
             for (int w = 0; w < CFEAR_REG_BLOCK / 64; w++) { tot += s_cost[w]; M += s_cnt[w]; }
-            const int nres = M * ((OP.rp.cost == CFEAR_COST_P2L) ? 1 : 2);
+            const int nres = M * ((sh->rp.cost == CFEAR_COST_P2L) ? 1 : 2);  // (the sequence's cost: seq_reg_params above)
             if (nres > 1) last = tot;  // GetCost false for <= 1 residuals (:205-208)
             costs[k] = last;
           }

@@ -402,7 +402,9 @@ __device__ __forceinline__ void register_step_body(unsigned char* lds /* RegLds:
       int m = nkf;
       st->ring[m] = cur_slot; st->kf_pose[m] = Tcurrent; m++;
       int freed;
-      if (m > OP.submap) {
+      // the ring's length is the sequence's own where it has a row (cfear_odometry_set_sequence_shapes; a row without shapes carries the
+      // context's): s_q <= OP.submap keyframes live in slots 0 .. s_q of the OP.submap + 1 the sequence has
+      if (m > (row ? (row->shape >> 2) : OP.submap)) {
         freed = st->ring[0];
         for (int i = 0; i + 1 < m; i++) { st->ring[i] = st->ring[i + 1]; st->kf_pose[i] = st->kf_pose[i + 1]; }
         m--;

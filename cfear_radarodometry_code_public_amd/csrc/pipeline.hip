@@ -21,6 +21,7 @@
 #include "odometry_step_dev.h"
 #include "cov_sampling_dev.h"
 #include "surface_dev.h"
+#include "seq_groups.h"
 
 namespace {
 
@@ -311,6 +312,42 @@ __global__ __launch_bounds__(1024) void order_kernel(const unsigned* work, int B
   __syncthreads();
   for (int i = tid; i < B; i += 1024) order[atomicAdd(&hist[255 - min(255, (int)((float)work[i] * scale))], 1u)] = i;
 }
+// The same order for an object whose sequences run in groups (cfear_odometry_set_sequence_shapes: one registration launch per group,
+// seq_groups.h): the counting sort segmented by group. group[i] in 0 .. CFEAR_SEQ_GROUPS - 1 is sequence i's group; the buckets are
+// (group, 256 keys scaled by the group's own largest), scanned in that order, so group g's permutation lands in the segment of `order`
+// its launch reads - the segments lie in group order and hold exactly the group's sequences (cfear_seq_groups::offset / count), and the
+// positions handed out are 0 .. B - 1 whatever `work` holds.
+__global__ __launch_bounds__(1024) void order_groups_kernel(const unsigned* work, int B, const int* group, int* order) {
+  constexpr int NB = 256 * CFEAR_SEQ_GROUPS;
+  static_assert(NB % 64 == 0, "the scan deals the buckets to one wave");
+  __shared__ unsigned hist[NB], gmax[CFEAR_SEQ_GROUPS];
+  const int tid = threadIdx.x;
+  for (int i = tid; i < NB; i += 1024) hist[i] = 0u;
+  if (tid < CFEAR_SEQ_GROUPS) gmax[tid] = 1u;
+  __syncthreads();
+  for (int i = tid; i < B; i += 1024) atomicMax(&gmax[min(max(group[i], 0), CFEAR_SEQ_GROUPS - 1)], work[i]);
+  __syncthreads();
+  auto bucket = [&](int i) -> int {
+    const int g = min(max(group[i], 0), CFEAR_SEQ_GROUPS - 1);
+    return 256 * g + 255 - min(255, (int)((float)work[i] * (255.0f / (float)gmax[g])));  // bucket 0 of a group = the most work
+  };
+  for (int i = tid; i < B; i += 1024) atomicAdd(&hist[bucket(i)], 1u);
+  __syncthreads();
+  if (tid < 64) {  // exclusive scan of the counts: NB / 64 consecutive buckets per lane, a wave scan across the lanes
+    constexpr int PER = NB / 64;
+    unsigned v = 0u;
+    for (int j = 0; j < PER; j++) v += hist[PER * tid + j];
+    unsigned incl = v;
+    for (int o = 1; o < 64; o <<= 1) { const unsigned u = (unsigned)__shfl_up((int)incl, o); if (tid >= o) incl += u; }
+    unsigned ex = incl - v;
+    for (int j = 0; j < PER; j++) { const unsigned c = hist[PER * tid + j]; hist[PER * tid + j] = ex; ex += c; }
+  }
+  __syncthreads();
+  for (int i = tid; i < B; i += 1024) {
+    const unsigned at = atomicAdd(&hist[bucket(i)], 1u);
+    if (at < (unsigned)B) order[at] = i;  // (always: B sequences were counted)
+  }
+}
 // ---- host-side helpers ---------------------------------------------------------------------------
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
@@ -537,6 +574,11 @@ struct cfear_odometry {
   DevBuf<SeqParams> d_seq;             // [B] what the kernels read (OdoParams::seq); exists while any of the above does
   cfear_params seq_par_seen;           // the context's parameters d_seq was built and the rows were checked against
   int seq_zmin = -1;                   // the filter's threshold: the smallest z_min of the rows (-1: the context's)
+  // per-sequence cost and submap size (cfear_odometry_set_sequence_shapes): the registration stage runs as one launch per group
+  std::vector<cfear_seq_shape> seq_shapes;  // [B]; empty: every sequence runs with the context's cost and submap_scan_size
+  cfear_seq_groups groups;             // the launch groups of seq_shapes (seq_groups.h), built with the device table
+  DevBuf<int> d_group_list;            // [B] groups.list: what OdoParams::order points into until a sweep's work keys exist
+  DevBuf<int> d_seq_group;             // [B] groups.group (order_groups_kernel)
   long long sweeps = 0;                // sweeps processed since cfear_odometry_create / cfear_odometry_reset
 };
 static int odo_sources(const cfear_odometry* o) { return o->n_sources > 0 ? o->n_sources : o->B; }
@@ -596,7 +638,7 @@ static OdoParams odo_params(const cfear_ctx* ctx, const cfear_odometry* o) {
 }
 
 // ---- per-sequence parameters (the grids of utils/worker:26-99 as sequences of one object) ------------------------------------------
-static SeqParams seq_row_of(const cfear_params& p, int source) {
+static SeqParams seq_row_of(const cfear_params& p, int source, int cost, int submap) {
   SeqParams r;
   memset(&r, 0, sizeof(r));
   r.loss_limit = p.loss_limit; r.covar_scale = p.covar_scale; r.regularization = p.regularization;
@@ -607,13 +649,17 @@ static SeqParams seq_row_of(const cfear_params& p, int source) {
   r.z_min = (int)(uint8_t)(int)p.z_min;  // as the filter takes it (radar_filters.cpp:198, :212)
   r.source = source;
   r.k = p.k_strongest;
+  r.shape = seq_shape_pack(cost, submap);
   return r;
 }
 // may the rows be the sequences of `o` under the context's parameters? The fields that size memory or select a kernel are the object's
-static int seq_rows_check(cfear_ctx* ctx, const cfear_odometry* o, const cfear_params* rows, int n, const char* what) {
+// shapes: [n] the cost / submap_scan_size row q must carry (cfear_odometry_set_sequence_shapes), null: the context's
+static const cfear_seq_shape* odo_shapes(const cfear_odometry* o) { return o->seq_shapes.empty() ? nullptr : o->seq_shapes.data(); }
+static int seq_rows_check(cfear_ctx* ctx, const cfear_odometry* o, const cfear_params* rows, int n, const char* what, const cfear_seq_shape* shapes) {
   const cfear_params& c = ctx->par;
   for (int q = 0; q < n; q++) {
     const cfear_params& r = rows[q];
+    const int want_cost = shapes ? shapes[q].cost : c.cost, want_submap = shapes ? shapes[q].submap_scan_size : c.submap_scan_size;
     // k_strongest: any k up to the context's K. The filter runs with K and the object is sized for it; a sequence reads the last k of the
     // returns the filter kept of every bearing (cloud_step_block)
     if (r.k_strongest < 1 || r.k_strongest > c.k_strongest) {
@@ -624,8 +670,8 @@ static int seq_rows_check(cfear_ctx* ctx, const cfear_odometry* o, const cfear_p
     }
     const char* f = nullptr;
     if (o->filter == CFEAR_FILTER_CACFAR && r.k_strongest != c.k_strongest) f = "k_strongest (the CA-CFAR detector has no k)";
-    else if (r.cost != c.cost) f = "cost";
-    else if (r.submap_scan_size != c.submap_scan_size) f = "submap_scan_size";
+    else if (r.cost != want_cost) f = shapes ? "cost (the sequence's shape says otherwise: cfear_odometry_set_sequence_shapes)" : "cost";
+    else if (r.submap_scan_size != want_submap) f = shapes ? "submap_scan_size (the sequence's shape says otherwise: cfear_odometry_set_sequence_shapes)" : "submap_scan_size";
     else if (r.filter_type != c.filter_type) f = "filter_type";
     else if (r.range_res != c.range_res) f = "range_res";
     else if (r.min_distance != c.min_distance) f = "min_distance";
@@ -639,9 +685,9 @@ static int seq_rows_check(cfear_ctx* ctx, const cfear_odometry* o, const cfear_p
     else if (r.cfar_max_distance != c.cfar_max_distance) f = "cfar_max_distance";
     else if (o->filter == CFEAR_FILTER_CACFAR && r.z_min != c.z_min) f = "z_min (the CA-CFAR detector's static threshold)";
     if (f) {
-      char msg[400];
+      char msg[640];
       snprintf(msg, sizeof(msg), "%s: row %d differs from the context's parameters in %s, which sizes memory or selects a kernel for the whole object "
-               "(per-sequence: z_min, k_strongest (<= the context's), res, weight_intensity, loss, loss_limit, weight_opt, covar_scale, regularization, compensate, "
+               "(cost and submap_scan_size per sequence: cfear_odometry_set_sequence_shapes; per-sequence: z_min, k_strongest (<= the context's), res, weight_intensity, loss, loss_limit, weight_opt, covar_scale, regularization, compensate, "
                "the keyframe rule, the iteration limits)", what, q, f);
       return cfear_fail(ctx, CFEAR_ERR_INVALID, msg);
     }
@@ -663,14 +709,29 @@ static int seq_rows_check(cfear_ctx* ctx, const cfear_odometry* o, const cfear_p
 // (re)builds the device table from the rows (or the context's parameters), the source map and the fuser options; frees it when none is set. The context
 // stream and the object's streams are idle when this is called.
 static int seq_table_upload(cfear_ctx* ctx, cfear_odometry* o) {
-  if (o->seq_rows.empty() && o->seq_src.empty() && o->fuser_opts.empty()) {
+  if (o->seq_shapes.empty()) { o->groups = cfear_seq_groups(); o->d_group_list.release(); o->d_seq_group.release(); }
+  if (o->seq_rows.empty() && o->seq_src.empty() && o->fuser_opts.empty() && o->seq_shapes.empty()) {
     o->d_seq.release(); o->seq_zmin = -1;
     return CFEAR_OK;
+  }
+  if (!o->seq_shapes.empty()) {  // the launch groups of the registration stage and their static list (launch_register_kernel)
+    std::vector<int> cost((size_t)o->B), sub((size_t)o->B);
+    for (int q = 0; q < o->B; q++) { cost[q] = o->seq_shapes[q].cost; sub[q] = o->seq_shapes[q].submap_scan_size; }
+    cfear_seq_groups G;
+    if (!cfear_seq_groups_build(cost.data(), sub.data(), o->B, CFEAR_STEP_SMALL_SCANS, G))
+      return cfear_fail(ctx, CFEAR_ERR_INVALID, "sequence shapes: a cost or submap_scan_size that is none");  // (refused by the caller before: never reached)
+    CFEAR_TRY(o->d_group_list.ensure(ctx, (size_t)o->B, "hipMalloc sequence group list"));
+    CFEAR_TRY(o->d_seq_group.ensure(ctx, (size_t)o->B, "hipMalloc sequence group list"));
+    CFEAR_HIP_CHECK(ctx, hipMemcpy(o->d_group_list, G.list.data(), sizeof(int) * (size_t)o->B, hipMemcpyHostToDevice));
+    CFEAR_HIP_CHECK(ctx, hipMemcpy(o->d_seq_group, G.group.data(), sizeof(int) * (size_t)o->B, hipMemcpyHostToDevice));
+    o->groups = G;
+    o->order_ready = false;  // (no sweep since create / reset: nothing was recorded)
   }
   std::vector<SeqParams> t((size_t)o->B);
   int zmin = 255;
   for (int q = 0; q < o->B; q++) {
-    t[q] = seq_row_of(o->seq_rows.empty() ? ctx->par : o->seq_rows[q], o->seq_src.empty() ? q : o->seq_src[q]);
+    t[q] = seq_row_of(o->seq_rows.empty() ? ctx->par : o->seq_rows[q], o->seq_src.empty() ? q : o->seq_src[q],
+                      o->seq_shapes.empty() ? ctx->par.cost : o->seq_shapes[q].cost, o->seq_shapes.empty() ? ctx->par.submap_scan_size : o->seq_shapes[q].submap_scan_size);
     zmin = std::min(zmin, t[q].z_min);
     if (!o->fuser_opts.empty()) t[q].fuser = (o->fuser_opts[q].soft_constraint ? SEQ_FUSER_SOFT : 0) | (o->fuser_opts[q].use_guess ? 0 : SEQ_FUSER_NO_GUESS);
   }
@@ -684,7 +745,7 @@ static int seq_table_upload(cfear_ctx* ctx, cfear_odometry* o) {
 // (loud, never silent) and the table follows them
 static int odo_seq_sync(cfear_ctx* ctx, cfear_odometry* o, const char* what) {
   if (!o->d_seq || memcmp(&o->seq_par_seen, &ctx->par, sizeof(cfear_params)) == 0) return CFEAR_OK;
-  if (!o->seq_rows.empty()) CFEAR_TRY(seq_rows_check(ctx, o, o->seq_rows.data(), o->B, what));
+  if (!o->seq_rows.empty()) CFEAR_TRY(seq_rows_check(ctx, o, o->seq_rows.data(), o->B, what, odo_shapes(o)));
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   CFEAR_TRY(odo_join(ctx, o));
   CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
@@ -699,7 +760,42 @@ static int seq_fresh_check(cfear_ctx* ctx, const cfear_odometry* o, const char* 
 }
 // the registration step kernel of a sweep. register_step.hip holds the production instantiations (one per cost metric, registrations of
 // up to CFEAR_STEP_SMALL_SCANS scans: a bigger LDS match array); a larger submap runs the instantiation of this file (any cost, 64 scans)
+// the registration kernel of `count` sequences that are not small (8 .. 63 keyframes), see launch_register_kernel. n_large / max_submap: what
+// the choice between the two shapes looks at
+static void launch_register_not_small(const OdoParams& P, int count, hipStream_t st, cfear_odometry* o, int n_large, int max_submap) {
+  const bool large = o->large_kernel == 2 || (o->large_kernel == 0 && (n_large <= o->n_cus || max_submap >= 24));
+  if (large) {
+    cfear_launch_register_step_large(P, count, st, o->d_states, o->d_scratch_hdr, o->d_cov_work, o->d_summaries, o->d_poses_out);
+    return;
+  }
+  CFEAR_LAUNCH_REG_BY_COST(register_step64_kernel, P, count, st, o->d_states, o->d_scratch_hdr, o->d_cov_work, o->d_summaries, o->d_poses_out);
+}
+// ... of an object with per-sequence shapes (cfear_odometry_set_sequence_shapes): one launch per non-empty group (cost, small or not), each on
+// the production instantiation of its cost, over the group's segment of the list (seq_groups.h). Whole-batch launches only (an object with
+// overlap streams takes no shapes). The sequences that are not small run ONE shape, chosen by today's rule from their number and their
+// largest submap; cfear_seq_group() alone decides who is small: register_step_kernel's per-scan LDS arrays hold CFEAR_STEP_SMALL_SCANS scans.
+static void launch_register_groups(const OdoParams& P_in, hipStream_t st, cfear_odometry* o) {
+  const cfear_seq_groups& G = o->groups;
+  const int* list = o->d_group_list;
+  if (o->d_order) {  // cfear_tune REGISTRATION_ORDER: longest first inside every group, from the second sweep on
+    if (o->order_ready) {
+      hipLaunchKernelGGL(order_groups_kernel, dim3(1), dim3(1024), 0, st, o->d_work, o->B, o->d_seq_group, o->d_order);
+      list = o->d_order;
+    }
+    o->order_ready = true;
+  }
+  for (int g = 0; g < CFEAR_SEQ_GROUPS; g++) {
+    if (G.count[g] <= 0) continue;
+    OdoParams P = P_in;
+    P.rp.cost = cfear_seq_groups::cost_of(g);  // selects the instantiation (the kernel itself takes the cost from the sequence's row)
+    P.order = list + G.offset[g];
+    if (cfear_seq_groups::small_of(g)) cfear_launch_register_step_small(P, G.count[g], st, o->d_states, o->d_scratch_hdr, o->d_cov_work, o->d_summaries, o->d_poses_out);
+    else launch_register_not_small(P, G.count[g], st, o, G.n_large, G.max_large_submap);
+  }
+}
 static void launch_register_kernel(const OdoParams& P_in, int count, hipStream_t st, cfear_odometry* o) {
+  const bool shaped = !o->seq_shapes.empty();
+  if (shaped && o->groups.n_launches > 1) { launch_register_groups(P_in, st, o); return; }
   OdoParams P = P_in;
   if (o->d_order && count == o->B && P.seq0 == 0) {  // (whole-batch launches only: the sub-batches of the overlap mode keep their ranges)
     if (o->order_ready) {
@@ -708,22 +804,26 @@ static void launch_register_kernel(const OdoParams& P_in, int count, hipStream_t
     }
     o->order_ready = true;  // this launch records the keys of the next one
   }
-  if (P.submap + 1 <= CFEAR_STEP_SMALL_SCANS) {
+  // shapes that form one group: one launch as without them, on the kernel of the group's cost and size (not of the context's)
+  bool small = P.submap + 1 <= CFEAR_STEP_SMALL_SCANS;
+  int n_large = count, max_submap = P.submap;
+  if (shaped) {
+    int g = 0;
+    while (g + 1 < CFEAR_SEQ_GROUPS && o->groups.count[g] == 0) g++;
+    P.rp.cost = cfear_seq_groups::cost_of(g); small = cfear_seq_groups::small_of(g);
+    n_large = o->groups.n_large; max_submap = o->groups.max_large_submap;
+  }
+  if (small) {
     cfear_launch_register_step_small(P, count, st, o->d_states, o->d_scratch_hdr, o->d_cov_work, o->d_summaries, o->d_poses_out);
     return;
   }
   // a larger submap (8 .. 63 keyframes). Few sequences - at most one per compute unit - or a very large submap (>= 24 keyframes):
   // register_step_large.hip, a unit's threads and LDS for each registration (2 x faster per registration at fifty keyframes); otherwise the
-  // production shape compiled for 64 scans, three workgroups per unit. In aggregate both shapes are bound by the same thing, the vector
+  // production shape compiled for 64 scans, three workgroups per unit (one instantiation per cost metric there too: a ten- or fifty-keyframe
+  // submap evaluates thousands of residual blocks 30-80 times per registration). In aggregate both shapes are bound by the same thing, the vector
   // instructions of the evaluation and the association (0.7-0.8 of the issue slots at fifty keyframes), so they differ by
   // < 10 % at 768 sequences and the small shape is the better one at ten keyframes. cfear_tune LARGE_SUBMAP_KERNEL forces either.
-  const bool large = o->large_kernel == 2 || (o->large_kernel == 0 && (count <= o->n_cus || P.submap >= 24));
-  if (large) {
-    cfear_launch_register_step_large(P, count, st, o->d_states, o->d_scratch_hdr, o->d_cov_work, o->d_summaries, o->d_poses_out);
-    return;
-  }
-  // one instantiation per cost metric here too: a ten- or fifty-keyframe submap evaluates thousands of residual blocks 30-80 times per registration
-  CFEAR_LAUNCH_REG_BY_COST(register_step64_kernel, P, count, st, o->d_states, o->d_scratch_hdr, o->d_cov_work, o->d_summaries, o->d_poses_out);
+  launch_register_not_small(P, count, st, o, n_large, max_submap);
 }
 // ... and behind it, on the same stream, the cost-sampling stage (estimate_cov_by_sampling) and / or the copy of every sequence's cov_current
 // (the replay's per-sweep covariances): before the next sweep's features kernel may reuse a slot the registration read
@@ -2105,6 +2205,14 @@ int cfear_odometry_surface(cfear_ctx* ctx, cfear_odometry* o, double res, int wi
     if (rc == CFEAR_ERR_INVALID) return cfear_fail(ctx, rc, "odometry_surface: res must be finite and > 0, width >= 0");
     if (rc != CFEAR_OK) return cfear_fail(ctx, rc, "odometry_surface: more than CFEAR_SURFACE_MAX_SIDE pixels per side");
   }
+  for (size_t q = 1; q < o->seq_shapes.size(); q++)
+    if (o->seq_shapes[q].cost != o->seq_shapes[0].cost) {
+      char msg[320];
+      snprintf(msg, sizeof(msg), "odometry_surface: the sequences' shapes differ in cost (sequence 0: %d, sequence %d: %d; cfear_odometry_set_sequence_shapes) - the "
+               "evaluation is one launch per cost metric over all problems; surfaces run under shapes of one cost (any submap_scan_size)",
+               (int)o->seq_shapes[0].cost, (int)q, (int)o->seq_shapes[q].cost);
+      return cfear_fail(ctx, CFEAR_ERR_UNSUPPORTED, msg);
+    }
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   CFEAR_TRY(odo_seq_sync(ctx, o, "odometry_surface"));
   CFEAR_TRY(odo_join(ctx, o));
@@ -2148,7 +2256,9 @@ int cfear_odometry_surface(cfear_ctx* ctx, cfear_odometry* o, double res, int wi
     CFEAR_HIP_CHECK(ctx, hipMemsetAsync(o->d_surf_hdr, 0, sizeof(SurfHdr) * (size_t)B, ctx->stream));
   }
   if (!CFEAR_SURFACE_NAIVE || !o->surf_ready) {
-    launch_surface_eval(OP.rp, B, o->d_surf_hdr, o->d_surf_coords, o->d_surf_nxy, pixels, d_surface, ctx->stream);
+    RegParams eval_rp = OP.rp;
+    if (!o->seq_shapes.empty()) eval_rp.cost = o->seq_shapes[0].cost;  // (one cost: checked above)
+    launch_surface_eval(eval_rp, B, o->d_surf_hdr, o->d_surf_coords, o->d_surf_nxy, pixels, d_surface, ctx->stream);
     CFEAR_HIP_CHECK(ctx, hipGetLastError());
   }
   return cap_rc;
@@ -2158,7 +2268,7 @@ int cfear_odometry_surface(cfear_ctx* ctx, cfear_odometry* o, double res, int wi
 int cfear_odometry_set_sequence_params(cfear_ctx* ctx, cfear_odometry* o, const cfear_params* rows, int n_rows) {
   if (!ctx || !o || (rows && n_rows != o->B)) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_set_sequence_params: bad argument (n_rows must be the object's n_sequences)");
   CFEAR_TRY(seq_fresh_check(ctx, o, "odometry_set_sequence_params"));
-  if (rows) CFEAR_TRY(seq_rows_check(ctx, o, rows, n_rows, "odometry_set_sequence_params"));
+  if (rows) CFEAR_TRY(seq_rows_check(ctx, o, rows, n_rows, "odometry_set_sequence_params", odo_shapes(o)));
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   CFEAR_TRY(odo_join(ctx, o));
   CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
@@ -2173,6 +2283,7 @@ int cfear_odometry_set_sequence_params(cfear_ctx* ctx, cfear_odometry* o, const 
 int cfear_odometry_sequence_params(cfear_ctx* ctx, cfear_odometry* o, int sequence, cfear_params* out) {
   if (!ctx || !o || !out || sequence < 0 || sequence >= o->B) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_sequence_params: bad argument");
   *out = o->seq_rows.empty() ? ctx->par : o->seq_rows[(size_t)sequence];
+  if (!o->seq_shapes.empty()) { out->cost = o->seq_shapes[(size_t)sequence].cost; out->submap_scan_size = o->seq_shapes[(size_t)sequence].submap_scan_size; }
   return CFEAR_OK;
 }
 
@@ -2216,6 +2327,46 @@ int cfear_odometry_set_sequence_sources(cfear_ctx* ctx, cfear_odometry* o, const
   o->d_polar.release();
   for (int i = 0; i < 2; i++) { o->rp_polar[i].release(); o->rp_slots[i].release(); }
   o->rp_chunk = 0; o->rp_polar_chunk = 0; o->rp_used_pending[0] = o->rp_used_pending[1] = false;
+  return CFEAR_OK;
+}
+
+// ---- per-sequence cost metric and submap size (utils/worker:49-52) --------------------------------------------------------------------
+int cfear_odometry_set_sequence_shapes(cfear_ctx* ctx, cfear_odometry* o, const cfear_seq_shape* shapes, int n_rows) {
+  if (!ctx || !o || (shapes && n_rows != o->B)) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_set_sequence_shapes: bad argument (n_rows must be the object's n_sequences)");
+  if (shapes && o->overlap)
+    return cfear_fail(ctx, CFEAR_ERR_UNSUPPORTED, "odometry_set_sequence_shapes: the object runs its sequences as index ranges on overlap streams (cfear_tune "
+                      "ODOMETRY_OVERLAP at creation); shapes run as one registration launch per group of sequences and are for objects without them");
+  CFEAR_TRY(seq_fresh_check(ctx, o, "odometry_set_sequence_shapes"));
+  const int S = o->nslots - 1;  // the submap_scan_size the object is sized for
+  for (int q = 0; shapes && q < n_rows; q++) {
+    char msg[256];
+    if (shapes[q].cost != CFEAR_COST_P2P && shapes[q].cost != CFEAR_COST_P2L && shapes[q].cost != CFEAR_COST_P2D) {
+      snprintf(msg, sizeof(msg), "odometry_set_sequence_shapes: row %d: cost = %d is no cost metric (CFEAR_COST_P2P / _P2L / _P2D)", q, (int)shapes[q].cost);
+      return cfear_fail(ctx, CFEAR_ERR_INVALID, msg);
+    }
+    if (shapes[q].submap_scan_size < 1 || shapes[q].submap_scan_size > S) {
+      snprintf(msg, sizeof(msg), "odometry_set_sequence_shapes: row %d: submap_scan_size = %d must be in 1..%d, the submap_scan_size the object was created "
+               "with (its scan slots and scratch are sized for it)", q, (int)shapes[q].submap_scan_size, S);
+      return cfear_fail(ctx, CFEAR_ERR_INVALID, msg);
+    }
+  }
+  // a table whose rows would then disagree with their shapes (NULL: with the context's values again)
+  if (!o->seq_rows.empty()) CFEAR_TRY(seq_rows_check(ctx, o, o->seq_rows.data(), o->B, "odometry_set_sequence_shapes", shapes));
+  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  CFEAR_TRY(odo_join(ctx, o));
+  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  std::vector<cfear_seq_shape> keep;
+  if (shapes) keep.assign(shapes, shapes + n_rows);
+  o->seq_shapes.swap(keep);
+  const int rc = seq_table_upload(ctx, o);
+  if (rc != CFEAR_OK) { const std::string err = ctx->err; o->seq_shapes.swap(keep); (void)seq_table_upload(ctx, o); ctx->err = err; }  // (the previous shapes)
+  return rc;
+}
+
+int cfear_odometry_sequence_shape(cfear_ctx* ctx, cfear_odometry* o, int sequence, cfear_seq_shape* out) {
+  if (!ctx || !o || !out || sequence < 0 || sequence >= o->B) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_sequence_shape: bad argument");
+  if (o->seq_shapes.empty()) { out->cost = ctx->par.cost; out->submap_scan_size = ctx->par.submap_scan_size; }
+  else *out = o->seq_shapes[(size_t)sequence];
   return CFEAR_OK;
 }
 

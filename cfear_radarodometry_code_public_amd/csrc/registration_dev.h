@@ -36,14 +36,18 @@ struct SeqParams {
   int source;    // the sweep of a step's input this sequence reads
   int fuser;     // cfear_fuser_options as the step takes them (cfear_odometry_set_fuser_options): SEQ_FUSER_* bits, 0 = the defaults
   int k;         // k_strongest of the sequence, 1 .. the context's K: the cloud pass reads the last k of the returns the K-filter kept of every bearing
+  int shape;     // cost | submap_scan_size << 2 of the sequence (cfear_odometry_set_sequence_shapes; the context's without shapes): packed, the
+                 // cost needs 2 bits and the keyframes 6, and one int is what the row's 96 bytes had left
 };
 static_assert(sizeof(SeqParams) <= 96, "a row of the per-sequence table: 96 bytes at the most");
+constexpr int seq_shape_pack(int cost, int submap) { return (cost & 3) | (submap << 2); }
 constexpr int SEQ_FUSER_SOFT = 1;      // soft_constraint: Register(..., soft_constraints = true) (odometrykeyframefuser.cpp:186)
 constexpr int SEQ_FUSER_NO_GUESS = 2;  // use_guess = 0: Tguess = T_prev (:167-168)
 typedef const __attribute__((address_space(4))) SeqParams* SeqRow;  // (constant address space: never written while a kernel may read it)
 // the registration's parameters of a sequence with a row (null: P stays what the context gave)
 __device__ __forceinline__ void seq_reg_params(RegParams& P, SeqRow row) {
   if (!row) return;
+  P.cost = row->shape & 3;
   P.loss = row->loss; P.weight_opt = row->weight_opt;
   P.loss_limit = row->loss_limit; P.covar_scale = row->covar_scale; P.regularization = row->regularization;
   P.max_outer = row->max_outer; P.min_itr = row->min_itr; P.max_inner = row->max_inner;

@@ -46,12 +46,25 @@ def param_grid(base, **axes):
 
 def grid_context_params(rows):
     """The parameters of the context a grid's rows run under: a copy of rows[0] with k_strongest the largest of the rows - the filter runs
-    with it and the object is sized for it, every row takes its own k strongest out of those (cfear_odometry_set_sequence_params). Rows of
-    equal k: rows[0]. Pure Python (no device); `rows` stays as it is."""
+    with it and the object is sized for it, every row takes its own k strongest out of those (cfear_odometry_set_sequence_params) - and
+    submap_scan_size the largest of the rows: the object's scan slots and scratch are sized for it, every row keeps a ring of its own
+    length (grid_shapes, cfear_odometry_set_sequence_shapes). The cost is rows[0]'s. Rows of equal k and submap size: rows[0]. Pure
+    Python (no device); `rows` stays as it is."""
     rows = list(rows)
     p = capi.Params.from_buffer_copy(rows[0])
     p.k_strongest = max(int(r.k_strongest) for r in rows)
+    p.submap_scan_size = max(int(r.submap_scan_size) for r in rows)
     return p
+
+
+def grid_shapes(rows, context_params):
+    """The capi.SeqShape of every row (its cost and submap_scan_size) - what Odometry.set_sequence_shapes takes before the table of a grid
+    with cost or submap_scan_size among its axes (utils/worker:49-52) - or None when every row equals context_params in both fields (no
+    shapes needed). Pure Python (no device)."""
+    rows = list(rows)
+    if all(int(r.cost) == int(context_params.cost) and int(r.submap_scan_size) == int(context_params.submap_scan_size) for r in rows):
+        return None
+    return [capi.SeqShape(int(r.cost), int(r.submap_scan_size)) for r in rows]
 
 
 # ... with the fuser's own switches (capi.FuserOptions): soft_constraint is the worker's third loop (utils/worker:40-46: after radar_ccw,
@@ -94,8 +107,9 @@ def drift_dict(row):
 
 def replay_grid(frames, rows, A=None, R=None, gt=None, device=0, piece=256, context_params=None, options=None, drift_on="host"):
     """One recording under len(rows) parameter sets in one batched odometry object: frames uint8 [n, A, R], rows a list of capi.Params that
-    agree in the object-wide fields (param_grid of one base does; k_strongest may be an axis: the context then runs with the largest,
-    grid_context_params, unless context_params says otherwise). The recording is the single source sweep of every sequence: it is
+    agree in the object-wide fields (param_grid of one base does; k_strongest and submap_scan_size may be axes: the context then runs with
+    the largest of each, grid_context_params, unless context_params says otherwise; so may cost: rows that differ from the context in cost
+    or submap_scan_size run under their own shapes, grid_shapes). The recording is the single source sweep of every sequence: it is
     copied and filtered once per sweep. options: a capi.FuserOptions for every row or a list of one per row (fuser_grid builds both
     lists); None: the fuser's defaults. -> dict(poses [n, len(rows), 3], records, drift: per row KITTI drift against gt ([n, 4, 4]
     poses) or None). drift_on: "host" - kitti.drift row by row; "device" - all rows in one cfear_drift_host call against a plan of
@@ -106,10 +120,14 @@ def replay_grid(frames, rows, A=None, R=None, gt=None, device=0, piece=256, cont
     n, A, R = frames.shape
     rows = list(rows)
     piece = max(1, int(piece))
-    ctx = capi.Context(context_params if context_params is not None else grid_context_params(rows), A, R, device=device)
+    cpar = context_params if context_params is not None else grid_context_params(rows)
+    ctx = capi.Context(cpar, A, R, device=device)
     odo = None
     try:
         odo = ctx.odometry(len(rows))
+        shapes = grid_shapes(rows, cpar)
+        if shapes is not None:
+            odo.set_sequence_shapes(shapes)
         odo.set_sequence_params(rows)
         odo.set_sequence_sources(np.zeros(len(rows), dtype=np.int32), 1)
         if options is not None:

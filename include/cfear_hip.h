@@ -403,7 +403,8 @@ int cfear_odometry_surface(cfear_ctx* ctx, cfear_odometry* odo, double res, int 
  * cfear_odometry_set_sequence_params: rows = n_sequences cfear_params, row q for sequence q (n_rows must be the object's n_sequences);
  * NULL: back to the context's parameters for all sequences. Per sequence: z_min, k_strongest (1 .. the context's, see below), res,
  * weight_intensity, loss, loss_limit, weight_opt, covar_scale, regularization, compensate, use_keyframe, min_keyframe_dist,
- * min_keyframe_rot_deg, max_itr_association, min_itr, max_solver_iterations. Every other field (cost, submap_scan_size, filter_type, range_res, min_distance, downsample_factor,
+ * min_keyframe_rot_deg, max_itr_association, min_itr, max_solver_iterations; cost and submap_scan_size through
+ * cfear_odometry_set_sequence_shapes below, whose values a row must then carry. Every other field (cost, submap_scan_size, filter_type, range_res, min_distance, downsample_factor,
  * radar_ccw, assoc_radius, cfar_*; with filter_type CA-CFAR also z_min) sizes memory or selects a kernel and must equal the context's value
  * in every row: otherwise CFEAR_ERR_INVALID with a message that names the row and the field, and nothing is changed. Only on an object
  * that has processed no sweep since cfear_odometry_create / cfear_odometry_reset (CFEAR_ERR_INVALID otherwise); cfear_odometry_reset
@@ -433,6 +434,35 @@ int cfear_odometry_sequence_params(cfear_ctx* ctx, cfear_odometry* odo, int sequ
  * range: CFEAR_ERR_INVALID, nothing changed. As the table: only before the first sweep since create / reset; reset keeps it.
  * Synchronises the context stream. */
 int cfear_odometry_set_sequence_sources(cfear_ctx* ctx, cfear_odometry* odo, const int32_t* source, int n_sequences, int n_sources);
+/* ---- Per-sequence cost metric and submap size: loops 6 and 7 of the evaluation grid (utils/worker:49-52, cost_type and submap_scan_size;
+ * params/submap_keyframes/submap_keyframe_cfear-3 is P2P P2L P2D x 1 .. 10) as sequences of one object. Both fields select a kernel, and
+ * submap_scan_size sizes memory too, so cfear_odometry_set_sequence_params alone keeps refusing rows that differ from the context in
+ * them; they are set by a call of their own. */
+typedef struct cfear_seq_shape {
+  int32_t cost;             /* CFEAR_COST_P2P / _P2L / _P2D */
+  int32_t submap_scan_size; /* 1 .. the context's submap_scan_size */
+} cfear_seq_shape;
+/* shapes[q]: the cost metric and the submap_scan_size sequence q runs with (n_rows must be the object's n_sequences); NULL: every sequence
+ * back to the context's values. The context's submap_scan_size S sizes the object and stays what sizes it - S + 1 scan slots per sequence,
+ * the residual-block scratch of S keyframes: a sequence with s <= S keeps a ring of s keyframes in slots 0 .. s of its S + 1 and gives, bit
+ * for bit, what the only sequence of an object created under a context with that cost and submap_scan_size gives (where both run the same
+ * kernel shape; the 512-thread kernel of large submaps sums an evaluation's partial results in another order than the 256-thread ones).
+ * The cost: every sequence pays the slots and the scratch of S - make the context's submap_scan_size the largest of the rows, no larger -
+ * and a sweep's registration stage is one launch per (cost, submap of up to 7 keyframes or more) present among the shapes, six at the
+ * most, each on the kernel an object of that cost and size runs; shapes that form one group launch once.
+ * Once shapes are set, cfear_odometry_set_sequence_params compares row q's cost and submap_scan_size with shapes[q] instead of the
+ * context's (a disagreement: CFEAR_ERR_INVALID, row and field named, nothing changed), and cfear_odometry_sequence_params(q) reports
+ * shapes[q]'s two values. Setting shapes while a table exists whose rows would then disagree is CFEAR_ERR_INVALID too.
+ * CFEAR_ERR_INVALID (row and field named) for a submap_scan_size < 1 or > S or an unknown cost, for n_rows other than n_sequences, and on
+ * an object that has processed a sweep since cfear_odometry_create / cfear_odometry_reset; CFEAR_ERR_UNSUPPORTED on an object created with
+ * cfear_tune ODOMETRY_OVERLAP streams (their sub-batches are index ranges). Nothing changes on failure. cfear_odometry_reset keeps the
+ * shapes. Every batched route honours them - the step entry points (host, device, cloud), both replay shapes, CA-CFAR objects, source
+ * maps, per-sequence k_strongest and z_min, the fuser options, the cost-sampling covariance - except cfear_odometry_surface while the
+ * shapes differ in COST (CFEAR_ERR_UNSUPPORTED: its evaluation is one launch per cost over all problems); shapes that differ only in
+ * submap_scan_size work there. Synchronises the context stream. */
+int cfear_odometry_set_sequence_shapes(cfear_ctx* ctx, cfear_odometry* odo, const cfear_seq_shape* shapes, int n_rows);
+/* The shape sequence q runs with: shapes[q], or the context's cost and submap_scan_size without shapes. */
+int cfear_odometry_sequence_shape(cfear_ctx* ctx, cfear_odometry* odo, int sequence, cfear_seq_shape* out);
 /* ---- The fuser's own switches on the batched routes (OdometryKeyframeFuser::Parameters soft_constraint and use_guess,
  * odometrykeyframefuser.h:94; offline_odometry.cpp:166,273-274; the third loop of the evaluation grid, utils/worker:43), per object or per
  * sequence. They are not in cfear_params (whose layout is fixed); the defaults are what the batched routes did before: 0, 1. */

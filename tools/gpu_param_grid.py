@@ -10,7 +10,12 @@
 #       every recording as seven sequences of ONE object under K = 50 on the shared sources (7 x sources sequences; the filter runs once per
 #       recording, with k = 50, and 50 slots per bearing are resident for every row)
 #   (f) the same seven values as seven uniform objects, one per k, a sequence per recording (the filter runs once per recording and k)
-# CFEAR_GRID_LEGS: a comma-separated subset of a,b,c,d,e,f (default: all)
+#   (g) the reference's params/submap_keyframes/submap_keyframe_cfear-3 (cost_type P2P P2L P2D x submap_scan_size 1 .. 10, utils/worker:49-52) on the
+#       CFEAR-3 preset: the 30 points of every recording as 30 sequences of ONE object under submap_scan_size 10 on the shared sources
+#       (cfear_odometry_set_sequence_shapes; 30 x sources sequences: every row pays the 11 scan slots and the scratch of ten keyframes, and the
+#       registration stage is up to six launches per sweep, one per (cost, up to 7 keyframes or more))
+#   (h) the same 30 points as 30 uniform objects, one per (cost, submap_scan_size), a sequence per recording; the last line sums them
+# CFEAR_GRID_LEGS: a comma-separated subset of a,b,c,d,e,f,g,h (default: all)
 # usage: python tools/gpu_param_grid.py >> profiles/param_grid_steps.jsonl
 import json, os, sys, time
 import numpy as np
@@ -25,11 +30,13 @@ def grid_rows(capi, replay, base, B):
     return [rows[q % len(rows)] for q in range(B)]
 
 
-def leg(capi, name, ctx_params, stream, B, S, d_frames, d_pre, idx, rows, shared, W, K, reps):
+def leg(capi, name, ctx_params, stream, B, S, d_frames, d_pre, idx, rows, shared, W, K, reps, shapes=None):
     """d_frames: [frames, S, A, R] resident sweeps of the S sources; shared: the object reads them through a source map, otherwise every
     sequence gets its own copy ([frames, B, A, R], gathered here, resident for the leg)"""
     ctx = capi.Context(ctx_params, bench.A, bench.R, device=0, stream=stream)
     odo = ctx.odometry(B)
+    if shapes is not None:
+        odo.set_sequence_shapes(shapes)
     if rows is not None:
         odo.set_sequence_params(rows)
     frames = d_frames.shape[0]
@@ -81,6 +88,7 @@ def leg(capi, name, ctx_params, stream, B, S, d_frames, d_pre, idx, rows, shared
     odo.release(); ctx.close()
     del d_in, d_tmp
     torch.cuda.empty_cache()
+    return out
 
 
 def main():
@@ -100,7 +108,7 @@ def main():
     base = capi.default_params(range_res=bench.RANGE_RES, **bench.PARAMS)
     rows = grid_rows(capi, replay, base, B)
     ident = [base] * B
-    legs = os.environ.get("CFEAR_GRID_LEGS", "a,b,c,d,e,f").split(",")
+    legs = os.environ.get("CFEAR_GRID_LEGS", "a,b,c,d,e,f,g,h").split(",")
     if "a" in legs:
         leg(capi, "a_no_table", base, stream, B, S, d_frames, d_pre, idx, None, False, W, K, reps)
     if "b" in legs:
@@ -126,6 +134,22 @@ def main():
             pk = capi.Params.from_buffer_copy(cfear3)
             pk.k_strongest = k
             leg(capi, "f_uniform_object_k%d" % k, pk, stream, S, S, d_frames, d_pre, sidx, None, False, W, K, reps)
+    # the submap_keyframes sweep on the CFEAR-3 preset: cost x submap_scan_size, 30 points
+    srows = replay.param_grid(cfear3, cost=[0, 1, 2], submap_scan_size=range(1, 11))
+    if "g" in legs:
+        Bs = len(srows) * S
+        gidx = torch.from_numpy(np.arange(Bs) // len(srows)).to(dev)  # sequences 30 r .. 30 r + 29: the thirty points of recording r
+        cpar = replay.grid_context_params(srows)
+        grows = [srows[q % len(srows)] for q in range(Bs)]
+        leg(capi, "g_cost_submap_grid_shared_sources_S10", cpar, stream, Bs, S, d_frames, d_pre, gidx, grows, True, W, K, reps, shapes=replay.grid_shapes(grows, cpar))
+    if "h" in legs:
+        sidx = torch.from_numpy(np.arange(S)).to(dev)
+        outs = [leg(capi, "h_uniform_object_cost%d_s%d" % (r.cost, r.submap_scan_size), r, stream, S, S, d_frames, d_pre, sidx, None, False, W, K, reps) for r in srows]
+        total = {"leg": "h_sum_of_30_uniform_objects", "sequences": len(srows) * S, "input_sweeps_per_step": len(srows) * S,
+                 "resident_input_MB_per_step": sum(o["resident_input_MB_per_step"] for o in outs)}
+        for k in ("step_us", "filter_us", "features_us", "registration_us"):
+            total[k] = float(sum(o[k] for o in outs))
+        print(json.dumps(total), flush=True)
 
 
 if __name__ == "__main__":
