@@ -54,6 +54,25 @@ class SeqShape(C.Structure):
         return "SeqShape(cost=%d, submap_scan_size=%d)" % (self.cost, self.submap_scan_size)
 
 
+class SeqDetector(C.Structure):
+    """cfear_seq_detector (include/cfear_hip.h): the CA-CFAR detector of one cloud of Context.filter_cfar_grid or of one sequence of a
+    filter_type CA-CFAR batched odometry object (Odometry.set_sequence_detectors)"""
+    _fields_ = [("window_size", C.c_int32), ("nb_guard_cells", C.c_int32), ("false_alarm_rate", C.c_float), ("z_min", C.c_float)]
+
+    def __repr__(self):
+        return "SeqDetector(window_size=%d, nb_guard_cells=%d, false_alarm_rate=%g, z_min=%g)" % (
+            self.window_size, self.nb_guard_cells, self.false_alarm_rate, self.z_min)
+
+
+def detector_array(dets):
+    """a list of SeqDetector / (window_size, nb_guard_cells, false_alarm_rate, z_min) tuples -> a ctypes array of SeqDetector (handed on as it
+    is when it already is one: a caller that repeats a large grid builds it once)"""
+    if isinstance(dets, C.Array) and dets._type_ is SeqDetector:
+        return dets
+    dets = [d if isinstance(d, SeqDetector) else SeqDetector(int(d[0]), int(d[1]), float(d[2]), float(d[3])) for d in dets]
+    return (SeqDetector * len(dets))(*dets)
+
+
 class Cell(C.Structure):
     _fields_ = [
         ("mean", C.c_double * 2), ("cov", C.c_double * 3), ("normal", C.c_double * 2),
@@ -100,7 +119,7 @@ assert DRIFT_DTYPE.itemsize == C.sizeof(Drift) == 184
 EXPORTS = [
     "cfear_version", "cfear_default_params", "cfear_create", "cfear_destroy", "cfear_last_error",
     "cfear_set_params", "cfear_synchronize", "cfear_tune", "cfear_kstrongest_launch_shape", "cfear_kstrongest_device", "cfear_kstrongest_host",
-    "cfear_rotate_polar", "cfear_rotate_polar_device", "cfear_filter_polar", "cfear_filter_polar_device", "cfear_filter_cfar", "cfear_filter_cfar_device", "cfear_filter_cfar_batch_device", "cfear_cloud_upload", "cfear_cloud_size",
+    "cfear_rotate_polar", "cfear_rotate_polar_device", "cfear_filter_polar", "cfear_filter_polar_device", "cfear_filter_cfar", "cfear_filter_cfar_device", "cfear_filter_cfar_batch_device", "cfear_filter_cfar_grid_device", "cfear_cloud_upload", "cfear_cloud_size",
     "cfear_cloud_download", "cfear_clouds_download", "cfear_cloud_release", "cfear_compensate", "cfear_compensate_pair", "cfear_scan_create",
     "cfear_scan_from_cells", "cfear_scan_release", "cfear_scan_size", "cfear_scan_download_cells", "cfear_scan_closest",
     "cfear_register", "cfear_register_soft", "cfear_register_time_continuous", "cfear_get_cost", "cfear_cov_by_sampling", "cfear_odometry_create", "cfear_odometry_destroy", "cfear_odometry_reset",
@@ -111,6 +130,7 @@ EXPORTS = [
     "cfear_odometry_set_sequence_params", "cfear_odometry_sequence_params", "cfear_odometry_set_sequence_sources",
     "cfear_default_fuser_options", "cfear_odometry_set_fuser_options", "cfear_odometry_fuser_options",
     "cfear_odometry_set_sequence_shapes", "cfear_odometry_sequence_shape",
+    "cfear_odometry_set_sequence_detectors", "cfear_odometry_sequence_detector",
     "cfear_odometry_covariances", "cfear_odometry_status", "cfear_odometry_summary", "cfear_odometry_profile", "cfear_odometry_profile_read", "cfear_odometry_profile_read_stages", "cfear_odometry_phase_times", "cfear_time_kstrongest",
     "cfear_drift_segments", "cfear_drift_plan_create", "cfear_drift_plan_release", "cfear_drift_device", "cfear_drift_host",
 ]
@@ -154,6 +174,7 @@ def lib():
         "cfear_filter_cfar": (C.c_int, [vp, u8p, C.c_int, C.c_int, C.c_float, C.c_double, C.POINTER(vp)]),
         "cfear_filter_cfar_device": (C.c_int, [vp, u8p, C.c_int, C.c_int, C.c_float, C.c_double, C.POINTER(vp)]),
         "cfear_filter_cfar_batch_device": (C.c_int, [vp, u8p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_double, f32p, C.c_int, i32p]),
+        "cfear_filter_cfar_grid_device": (C.c_int, [vp, u8p, C.c_int, vp, i32p, C.c_int, C.c_double, f32p, C.c_int, i32p]),
         "cfear_cloud_upload": (C.c_int, [vp, f32p, C.c_int, C.POINTER(vp)]),
         "cfear_cloud_size": (C.c_int, [vp, vp, C.POINTER(C.c_int)]),
         "cfear_cloud_download": (C.c_int, [vp, vp, f32p, C.c_int, C.POINTER(C.c_int)]),
@@ -197,6 +218,8 @@ def lib():
         "cfear_odometry_set_sequence_sources": (C.c_int, [vp, vp, i32p, C.c_int, C.c_int]),
         "cfear_odometry_set_sequence_shapes": (C.c_int, [vp, vp, vp, C.c_int]),
         "cfear_odometry_sequence_shape": (C.c_int, [vp, vp, C.c_int, C.POINTER(SeqShape)]),
+        "cfear_odometry_set_sequence_detectors": (C.c_int, [vp, vp, vp, C.c_int, i32p, C.c_int]),
+        "cfear_odometry_sequence_detector": (C.c_int, [vp, vp, C.c_int, C.POINTER(SeqDetector)]),
         "cfear_default_fuser_options": (None, [C.POINTER(FuserOptions)]),
         "cfear_odometry_set_fuser_options": (C.c_int, [vp, vp, vp, C.c_int]),
         "cfear_odometry_fuser_options": (C.c_int, [vp, vp, C.c_int, C.POINTER(FuserOptions)]),
@@ -406,6 +429,18 @@ class Context:
             rc = self._L.cfear_filter_cfar_device(self._h, _addr(polar), *args)
         self._check(rc, "cfear_filter_cfar")
         return Cloud(self, c)
+
+    def filter_cfar_grid(self, d_polar, n_sources, dets, source, d_xyi, capacity, d_counts, max_distance=400.0):
+        """Several CA-CFAR detectors over shared device-resident images in one pass (cfear_filter_cfar_grid_device): cloud c is the
+        detections of image source[c] (None: image c) under dets[c] (SeqDetector or (window, guard, rate, z_min) tuples) -> d_xyi
+        [len(dets), capacity, 3] float32, d_counts [len(dets)] int32 on the device. Asynchronous on the context stream."""
+        arr = detector_array(dets)
+        src = None if source is None else np.ascontiguousarray(source, dtype=np.int32)
+        if src is not None and src.size != len(arr):
+            raise ValueError("filter_cfar_grid: %d detectors, %d sources" % (len(arr), src.size))
+        self._check(self._L.cfear_filter_cfar_grid_device(self._h, _addr(d_polar), int(n_sources), C.cast(arr, C.c_void_p), src.ctypes.data if src is not None else None,
+                                                          len(arr), float(max_distance), _addr(d_xyi), int(capacity), _addr(d_counts)),
+                    "cfear_filter_cfar_grid_device")
 
     def filter_cfar_batch(self, d_polar, n_scans, d_xyi, capacity, d_counts, window_size=10, nb_guard_cells=20, false_alarm_rate=0.01, max_distance=400.0):
         """CA-CFAR over n_scans device-resident sweeps; d_xyi [n_scans, capacity, 3] float32 and d_counts [n_scans] int32 on the device"""
@@ -811,6 +846,35 @@ class Odometry:
         s = SeqShape()
         self._ctx._check(self._ctx._L.cfear_odometry_sequence_shape(self._ctx._h, self._h, int(q), C.byref(s)), "cfear_odometry_sequence_shape")
         return s
+
+    def set_sequence_detectors(self, dets, source=None, n_sources=None):
+        """dets: one SeqDetector (or (window_size, nb_guard_cells, false_alarm_rate, z_min) tuple) per sequence of a filter_type CA-CFAR
+        object; source[q]: the input sweep sequence q reads (None: one sweep per sequence) - afterwards step_host / step_device / the
+        replays take n_sources sweeps per step, staged once each, every distinct (sweep, detector) decided once. dets None: the
+        context's detector and one sweep per sequence again (cfear_odometry_set_sequence_detectors). Before the first sweep since
+        creation / reset()."""
+        fn, c = self._ctx._L.cfear_odometry_set_sequence_detectors, self._ctx
+        if dets is None:
+            c._check(fn(c._h, self._h, None, 0, None, 0), "cfear_odometry_set_sequence_detectors")
+            self.n_sources = self.B
+            return
+        arr = detector_array(dets)
+        if source is None:
+            c._check(fn(c._h, self._h, C.cast(arr, C.c_void_p), len(arr), None, 0), "cfear_odometry_set_sequence_detectors")
+            self.n_sources = self.B
+            return
+        src = np.ascontiguousarray(source, dtype=np.int32)
+        ns = int(n_sources) if n_sources is not None else int(src.max()) + 1
+        if src.size != len(arr):
+            raise ValueError("set_sequence_detectors: %d detectors, %d sources" % (len(arr), src.size))
+        c._check(fn(c._h, self._h, C.cast(arr, C.c_void_p), len(arr), src.ctypes.data, ns), "cfear_odometry_set_sequence_detectors")
+        self.n_sources = ns
+
+    def sequence_detector(self, q):
+        """the SeqDetector sequence q runs with (cfear_odometry_sequence_detector)"""
+        d = SeqDetector()
+        self._ctx._check(self._ctx._L.cfear_odometry_sequence_detector(self._ctx._h, self._h, int(q), C.byref(d)), "cfear_odometry_sequence_detector")
+        return d
 
     def set_fuser_options(self, rows):
         """rows: one FuserOptions for every sequence, a list of one per sequence, or None for the defaults again

@@ -111,6 +111,7 @@ void cfear_destroy(cfear_ctx* ctx) {
   if (ctx->ev_img) (void)hipEventDestroy(ctx->ev_img);
   if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
   if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
+  cfear_cfar_grid_destroy(ctx->cfar_grid);
   if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;  // (and with it the device buffers it owns)
 }

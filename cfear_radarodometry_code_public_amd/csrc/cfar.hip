@@ -10,6 +10,8 @@
 //   cfar_row_scan_kernel  row counts -> row offsets of every image (the output cloud is row-major over (azimuth, range bin) like
 //                       the reference's push_back order);
 //   cfar_emit_kernel    a wave per four rows walks their masks and writes the points (the intensity is a gather of the hit bytes).
+// cfear_filter_cfar_grid_device runs SEVERAL detectors over shared source images with cfar_detect_grid_kernel: the row staged and the prefix built once,
+// every distinct (source, detector) decided against it, the emit pass (cfar_emit_grid_kernel) with an indirection from clouds to masks.
 // The decision replays the reference's double arithmetic (sum / N per window, (t + f) / 2, scaling * mean, I^2 > threshold; an empty
 // window gives 0/0 = NaN and no detection) - but only where it has to: with z_min = 20 (the reference's own CA-CFAR preset,
 // params/kstrong_vs_cfar/oxford-cfear-3-ca-cfar:27) nearly every bin passes the static test, and two double divisions per bin made
@@ -21,7 +23,11 @@
 #include <math.h>
 #include <stdlib.h>
 
+#include <cmath>
+#include <new>
+
 #include "blockops.h"
+#include "cfar_grid.h"
 #include "common.h"
 
 namespace {
@@ -285,6 +291,101 @@ __global__ __launch_bounds__(CFAR_BLOCK) void cfar_detect_fast_kernel(const uint
   if (lane == 0) red_i[32 + wv] = cnt;
   __syncthreads();
   if (tid == 0) row_count[grow] = red_i[32] + red_i[33] + red_i[34] + red_i[35];
+}
+
+// ---- several detectors against ONE prefix sum (cfear_filter_cfar_grid_device; the detector grid of params/kstrong_vs_cfar/oxford-cfear-3-ca-cfar) ----
+// The prefix sum of squares of a row depends on none of window, guard, rate and static threshold, and building it is about half of
+// cfar_detect_fast_kernel's row. Same launch shape here - one 256-thread workgroup per row of a SOURCE image, the row staged as dwords, thread t the
+// bins [TB t, TB t + TB), v_dot4 and one block scan - and then a wave-uniform loop over the detections asked of that source (cfar_grid.h: the pairs
+// pair_begin[s] .. pair_begin[s + 1] of source s): each takes its window, guard, scaling, pre-test constant and smallest intensity from a device table
+// and runs cfar_four_trips as it is, and writes the row's hit mask and count of the pair. The range gate (ilo / ihi) is the launch's.
+// The flat prefix array is padded by the largest guard + window of the LAUNCH (rounded to 4), zeros in front and the row total behind, and reaches to
+// `rr`, the row length rounded up to the 256 bins a wave's four trips cover, + that pad: every read of every set stays inside it. (18.4 KB at 3360
+// bins and a reach of 510: eight rows in flight per compute unit, the 32 waves a unit holds.)
+struct CfarGridSet {
+  int window, guard;
+  int iv_min;      // smallest intensity with (double)I > the set's static threshold (256: none)
+  float kf;        // scaling / (2 w) in float
+  double scaling;
+};
+template <int TB /* bins per thread of the prefix pass: 16 or 32 */>
+__global__ __launch_bounds__(CFAR_BLOCK) void cfar_detect_grid_kernel(const uint8_t* __restrict__ polar, CfarParams P, int pad, int rr, int nsrc, int n_pairs,
+                                                                      const int* __restrict__ pair_begin, const CfarGridSet* __restrict__ sets,
+                                                                      int* __restrict__ row_count, uint32_t* __restrict__ mask) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t cfar_lds[];  // prefix[-pad .. rr + pad + 3]
+  __shared__ int red_i[64];
+  typedef __attribute__((address_space(3))) uint32_t l_u32;
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  typedef uint32_t u32x4a __attribute__((ext_vector_type(4), aligned(4)));
+  typedef __attribute__((address_space(3))) u32x4 l_u32x4;
+  typedef __attribute__((address_space(1))) const uint32_t g_cu32;
+  typedef __attribute__((address_space(1))) const u32x4a g_cu32x4;
+  constexpr int ND = TB / 4, NB = CFAR_BLOCK * TB;  // dwords per thread, bins the segments cover
+  const int R = P.R, tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  l_u32* const prefix = (l_u32*)cfar_lds + pad;
+  const int grow = blockIdx.x, ndw = R >> 2, top = rr + pad;  // (top: the last index a read can ask for; a multiple of 4)
+  g_cu32* src = (g_cu32*)(polar + (long long)grow * R);
+  uint32_t seg[ND];
+  if (ND * tid + ND <= ndw) {
+#pragma unroll
+    for (int j = 0; j < ND; j += 4) {
+      const u32x4 v = __builtin_nontemporal_load((g_cu32x4*)(src + ND * tid + j));
+      seg[j] = v.x; seg[j + 1] = v.y; seg[j + 2] = v.z; seg[j + 3] = v.w;
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < ND; j++) seg[j] = ND * tid + j < ndw ? __builtin_nontemporal_load(src + ND * tid + j) : 0u;
+  }
+  uint32_t s = 0;
+#pragma unroll
+  for (int j = 0; j < ND; j++) s = __builtin_amdgcn_udot4(seg[j], seg[j], s, false);
+  for (int i = tid; i < pad; i += CFAR_BLOCK) prefix[-pad + i] = 0u;
+  int tot;
+  uint32_t o = (uint32_t)block_exclusive_scan<CFAR_BLOCK>((int)s, red_i, &tot);
+#pragma unroll
+  for (int j = 0; j < ND; j++) {
+    const uint32_t d = seg[j], b0 = d & 0xFFu, b1 = (d >> 8) & 0xFFu, b2 = (d >> 16) & 0xFFu, b3 = d >> 24;
+    u32x4 v;
+    v.x = o; o += b0 * b0; v.y = o; o += b1 * b1; v.z = o; o += b2 * b2; v.w = o; o += b3 * b3;
+    if (TB * tid + 4 * j <= top) *(l_u32x4*)(prefix + TB * tid + 4 * j) = v;  // (bins >= R are zeros: prefix[R ..] = the row total; the array ends at top + 3)
+  }
+  for (int i = NB + tid; i <= top; i += CFAR_BLOCK) prefix[i] = (uint32_t)tot;
+  __syncthreads();
+  // ---- the detections asked of this source, one after the other against the same prefix ----
+  const int img = grow / P.A, az = grow - img * P.A, step = img / nsrc, source = img - step * nsrc;
+  const int p0 = pair_begin[source], p1 = pair_begin[source + 1];
+  const int ntrips = (R + 63) >> 6;
+  constexpr int ITERS = TB / 4;
+  for (int p = p0; p < p1; p++) {
+    const CfarGridSet S = sets[p];
+    CfarParams Q = P;
+    Q.window = S.window; Q.guard = S.guard; Q.scaling = S.scaling; Q.kf = S.kf; Q.iv_min = S.iv_min;
+    const float kf_hi = Q.kf * 1.000002f, kf_lo = Q.kf * 0.999998f, kscale = Q.kf * (float)Q.window;
+    const int iv_min2 = Q.iv_min * Q.iv_min;
+    const size_t orow = ((size_t)step * n_pairs + p) * P.A + az;  // the row of the pair's image of masks
+    int cnt = 0;
+    uint32_t acc = 0;
+    if (4 * wv < ntrips) cfar_four_trips<0, TB>(Q, prefix, 4 * wv, ntrips, lane, kf_lo, kf_hi, kscale, iv_min2, acc, cnt);
+    if (4 * (wv + 4) < ntrips) cfar_four_trips<1, TB>(Q, prefix, 4 * (wv + 4), ntrips, lane, kf_lo, kf_hi, kscale, iv_min2, acc, cnt);
+    if (4 * (wv + 8) < ntrips) cfar_four_trips<2, TB>(Q, prefix, 4 * (wv + 8), ntrips, lane, kf_lo, kf_hi, kscale, iv_min2, acc, cnt);
+    if (4 * (wv + 12) < ntrips) cfar_four_trips<3, TB>(Q, prefix, 4 * (wv + 12), ntrips, lane, kf_lo, kf_hi, kscale, iv_min2, acc, cnt);
+    if constexpr (ITERS > 4) {
+      if (4 * (wv + 16) < ntrips) cfar_four_trips<4, TB>(Q, prefix, 4 * (wv + 16), ntrips, lane, kf_lo, kf_hi, kscale, iv_min2, acc, cnt);
+      if (4 * (wv + 20) < ntrips) cfar_four_trips<5, TB>(Q, prefix, 4 * (wv + 20), ntrips, lane, kf_lo, kf_hi, kscale, iv_min2, acc, cnt);
+      if (4 * (wv + 24) < ntrips) cfar_four_trips<6, TB>(Q, prefix, 4 * (wv + 24), ntrips, lane, kf_lo, kf_hi, kscale, iv_min2, acc, cnt);
+      if (4 * (wv + 28) < ntrips) cfar_four_trips<7, TB>(Q, prefix, 4 * (wv + 28), ntrips, lane, kf_lo, kf_hi, kscale, iv_min2, acc, cnt);
+    }
+    {  // lane 8 k + 2 u + h holds half h of trip 4 (wv + 4 k) + u
+      const int trip = 4 * (wv + 4 * (lane >> 3)) + ((lane >> 1) & 3);
+      if (lane < 8 * ITERS && trip < ntrips) mask[orow * P.mask_words + 2 * trip + (lane & 1)] = acc;
+    }
+    // (the waves' counts take turns in two sets of four words: one barrier per detection - the set after the next writes these words again, and
+    // thread 0 has read them before it reaches the barrier in between)
+    const int slot = 32 + 4 * ((p - p0) & 1);
+    if (lane == 0) red_i[slot + wv] = cnt;
+    __syncthreads();
+    if (tid == 0) row_count[orow] = red_i[slot] + red_i[slot + 1] + red_i[slot + 2] + red_i[slot + 3];
+  }
 }
 
 
@@ -738,6 +839,57 @@ __global__ __launch_bounds__(CFAR_BLOCK) void cfar_emit_kernel(const uint8_t* __
   }
 }
 
+// ... with an indirection between the clouds and the masks (cfear_filter_cfar_grid_device): cloud c = step * n_clouds + q is emitted from the masks of
+// the detection it asked for and the bytes of its source image, to xyi + c * cap * 3; its true count goes to d_counts[c]. The images of masks lie
+// [step][pair] (the shared kernel) or [set][step][source] (one launch of a one-detector kernel per set over all sources).
+struct CfarGridMap {
+  const int* cloud_pair; const int* cloud_set; const int* cloud_src;  // [n_clouds]
+  int n_clouds, nsrc, n_pairs, n_img;  // n_img: source images of the launch (steps x nsrc)
+  int per_set;                         // the masks lie [set][step][source]
+};
+__global__ __launch_bounds__(CFAR_BLOCK) void cfar_emit_grid_kernel(const uint8_t* __restrict__ polar, CfarParams P, CfarGridMap M, const double* __restrict__ trig,
+                                                                    const int* __restrict__ row_count, const int* __restrict__ row_base,
+                                                                    const int* __restrict__ totals, const uint32_t* __restrict__ mask, float* __restrict__ xyi,
+                                                                    int cap, int* __restrict__ d_counts, long long rows /* clouds x A */) {
+  const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const long long g0 = ((long long)blockIdx.x * (CFAR_BLOCK / 64) + wv) * CFAR_EMIT_ROWS;
+  if (g0 >= rows) return;
+  int cnt[CFAR_EMIT_ROWS], base[CFAR_EMIT_ROWS], az[CFAR_EMIT_ROWS], any = 0;
+  long long mrow[CFAR_EMIT_ROWS], irow[CFAR_EMIT_ROWS], cloud[CFAR_EMIT_ROWS];
+#pragma unroll
+  for (int r = 0; r < CFAR_EMIT_ROWS; r++) {
+    const bool valid = g0 + r < rows;
+    const long long gr = valid ? g0 + r : g0;
+    const long long c = gr / P.A, step = c / M.n_clouds;
+    const int q = (int)(c - step * M.n_clouds);
+    const int src = M.cloud_src[q];
+    const long long blk = M.per_set ? (long long)M.cloud_set[q] * M.n_img + step * M.nsrc + src : step * M.n_pairs + M.cloud_pair[q];
+    az[r] = (int)(gr - c * P.A);
+    cloud[r] = c;
+    mrow[r] = blk * P.A + az[r];
+    irow[r] = (step * M.nsrc + src) * P.A + az[r];
+    if (valid && az[r] == 0 && lane == 0) d_counts[c] = totals[blk];
+    cnt[r] = valid ? row_count[mrow[r]] : 0;
+    base[r] = valid ? row_base[mrow[r]] : 0;
+    any |= cnt[r];
+  }
+  if (!any) return;
+  const int wpl = (P.mask_words + 63) >> 6;  // consecutive mask words per lane
+  const int w0 = min(P.mask_words, lane * wpl), w1 = min(P.mask_words, w0 + wpl);
+  for (int r = 0; r < CFAR_EMIT_ROWS; r++) {
+    if (!cnt[r]) continue;  // (wave-uniform)
+    const uint32_t* mr = mask + (size_t)mrow[r] * P.mask_words;
+    int c = 0;
+    for (int k = w0; k < w1; k++) c += __popc(mr[k]);
+    int o = wave_inclusive_scan(c) - c + base[r];
+    if (c == 0) continue;
+    const double cos_t = trig[2 * az[r]], sin_t = trig[2 * az[r] + 1];  // theta = (az + 1) / A * 2 pi, host libm (cfar.cpp:40)
+    const uint8_t* row = polar + irow[r] * P.R;
+    float* out = xyi + 3 * (size_t)cloud[r] * cap;
+    for (int k = w0; k < w1; k++) o = cfar_emit_word(mr[k], k, o, cap, row, P.range_res, cos_t, sin_t, out);
+  }
+}
+
 // exclusive scan of the A row counts of image blockIdx.x (one workgroup per image); total -> d_total[blockIdx.x]
 __global__ __launch_bounds__(1024) void cfar_row_scan_kernel(const int* __restrict__ row_count, int A, int* __restrict__ row_base,
                                                              int* __restrict__ d_total) {
@@ -1021,7 +1173,165 @@ __attribute__((visibility("hidden"))) int cfear_launch_cfar_batch(cfear_ctx* ctx
   return CFEAR_OK;
 }
 
+// ---- several detectors over shared source images (cfar_grid.h) -----------------------------------------------------------------------
+struct cfear_cfar_grid {
+  cfear_cfar_grid_plan plan;
+  std::vector<cfear_seq_detector> dets;  // what it was built from (cfear_filter_cfar_grid_device keeps a grid while the next call asks for the same)
+  std::vector<int32_t> source;           // empty: cloud c reads source c
+  bool shared = false;                   // the rows take cfar_detect_grid_kernel (else: the one-detector kernels once per set)
+  DevBuf<int> d_tab;                     // pair_begin [n_sources + 1], cloud_pair, cloud_set, cloud_src [n_clouds each]
+  DevBuf<CfarGridSet> d_sets;            // [n_pairs] the detector of every pair
+};
+namespace {
+int cfar_iv_min(float z_min) {  // smallest intensity with (double)I > static_threshold (256: none), cfar.cpp:45
+  int m = 256;
+  for (int v = 255; v >= 0; v--) if ((double)v > (double)z_min) m = v;
+  return m;
+}
+// the kernel parameters of one detector of a grid: the context's, with the detector's own static threshold
+int cfar_params_det(cfear_ctx* ctx, const cfear_seq_detector& d, double max_distance, CfarParams* out) {
+  CFEAR_TRY(cfar_params(ctx, d.window_size, d.nb_guard_cells, d.false_alarm_rate, max_distance, out));
+  out->iv_min = cfar_iv_min(d.z_min);
+  return CFEAR_OK;
+}
+size_t cfar_grid_blocks(const cfear_cfar_grid* g, size_t n_steps) {  // images of masks of a launch
+  return g->shared ? n_steps * (size_t)g->plan.n_pairs() : (size_t)g->plan.n_sets() * n_steps * (size_t)g->plan.n_sources;
+}
+}  // namespace
+
+__attribute__((visibility("hidden"))) void cfear_cfar_grid_destroy(cfear_cfar_grid* g) { delete g; }
+
+__attribute__((visibility("hidden"))) int cfear_cfar_grid_create(cfear_ctx* ctx, const cfear_seq_detector* dets, const int32_t* source, int n_clouds, int n_sources,
+                                                                 const char* what, cfear_cfar_grid** out) {
+  *out = nullptr;
+  char msg[256];
+  if (!dets || n_clouds < 1 || n_sources < 1 || (!source && n_sources != n_clouds)) {
+    snprintf(msg, sizeof(msg), "%s: bad argument (detectors, clouds >= 1, sources >= 1; without a source map as many sources as clouds)", what);
+    return cfear_fail(ctx, CFEAR_ERR_INVALID, msg);
+  }
+  for (int c = 0; c < n_clouds; c++) {
+    const cfear_seq_detector& d = dets[c];
+    msg[0] = 0;
+    if (d.window_size < 1) snprintf(msg, sizeof(msg), "%s: row %d: window_size = %d must be >= 1", what, c, (int)d.window_size);
+    else if (d.nb_guard_cells < 0) snprintf(msg, sizeof(msg), "%s: row %d: nb_guard_cells = %d must be >= 0", what, c, (int)d.nb_guard_cells);
+    else if (!(d.false_alarm_rate > 0.f) || !std::isfinite(d.false_alarm_rate))
+      snprintf(msg, sizeof(msg), "%s: row %d: false_alarm_rate = %g must be finite and > 0", what, c, (double)d.false_alarm_rate);
+    else if (!std::isfinite(d.z_min)) snprintf(msg, sizeof(msg), "%s: row %d: z_min must be finite", what, c);
+    else if (source && (source[c] < 0 || source[c] >= n_sources))
+      snprintf(msg, sizeof(msg), "%s: row %d: source = %d is outside [0, %d)", what, c, (int)source[c], n_sources);
+    if (msg[0]) return cfear_fail(ctx, CFEAR_ERR_INVALID, msg);
+  }
+  cfear_cfar_grid* g = new (std::nothrow) cfear_cfar_grid();
+  if (!g) return cfear_fail(ctx, CFEAR_ERR_NOMEM, "cfar grid alloc");
+  auto fail = [&](int rc) { delete g; return rc; };
+  if (!cfear_cfar_grid_plan_build(dets, source, n_clouds, n_sources, g->plan)) {
+    snprintf(msg, sizeof(msg), "%s: a source outside [0, %d)", what, n_sources);  // (refused above: never reached)
+    return fail(cfear_fail(ctx, CFEAR_ERR_INVALID, msg));
+  }
+  g->dets.assign(dets, dets + n_clouds);
+  if (source) g->source.assign(source, source + n_clouds);
+  const cfear_cfar_grid_plan& G = g->plan;
+  std::vector<CfarParams> SP((size_t)G.n_sets());
+  for (int k = 0; k < G.n_sets(); k++) {  // (what the one-detector entry points refuse: more than 16384 bins, a window beyond 2^20)
+    const int rc = cfar_params_det(ctx, G.sets[(size_t)k], 400.0, &SP[(size_t)k]);
+    if (rc != CFEAR_OK) return fail(rc);
+  }
+  g->shared = (ctx->R & 3) == 0 && ctx->R <= CFAR_BLOCK * 32 && G.max_reach <= 2048;
+  std::vector<int> tab;
+  tab.insert(tab.end(), G.pair_begin.begin(), G.pair_begin.end());
+  tab.insert(tab.end(), G.cloud_pair.begin(), G.cloud_pair.end());
+  tab.insert(tab.end(), G.cloud_set.begin(), G.cloud_set.end());
+  tab.insert(tab.end(), G.cloud_src.begin(), G.cloud_src.end());
+  std::vector<CfarGridSet> sets((size_t)G.n_pairs());
+  for (int p = 0; p < G.n_pairs(); p++) {
+    const CfarParams& P = SP[(size_t)G.pair_set[(size_t)p]];
+    CfarGridSet& S = sets[(size_t)p];
+    S.window = P.window; S.guard = P.guard; S.iv_min = P.iv_min; S.kf = P.kf; S.scaling = P.scaling;
+  }
+  if (hipSetDevice(ctx->device) != hipSuccess) return fail(cfear_fail(ctx, CFEAR_ERR_HIP, "hipSetDevice"));
+  if (g->d_tab.ensure(ctx, tab.size(), "hipMalloc cfar grid tables") != CFEAR_OK || g->d_sets.ensure(ctx, sets.size(), "hipMalloc cfar grid tables") != CFEAR_OK)
+    return fail(CFEAR_ERR_NOMEM);
+  if (hipMemcpy(g->d_tab, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(g->d_sets, sets.data(), sizeof(CfarGridSet) * sets.size(), hipMemcpyHostToDevice) != hipSuccess)
+    return fail(cfear_fail(ctx, CFEAR_ERR_HIP, "cfar grid table upload"));
+  *out = g;
+  return CFEAR_OK;
+}
+
+// ints of row scratch a grid launch of n_steps sweeps needs: row counts, row bases, totals and hit masks of every image of masks
+__attribute__((visibility("hidden"))) size_t cfear_cfar_grid_scratch_ints(const cfear_ctx* ctx, const cfear_cfar_grid* g, size_t n_steps) {
+  const size_t per_row = 2 + 2 * (size_t)((ctx->R + 63) / 64);
+  const size_t blocks = cfar_grid_blocks(g, n_steps);
+  return blocks * (size_t)ctx->A * per_row + blocks;
+}
+
+__attribute__((visibility("hidden"))) int cfear_launch_cfar_grid(cfear_ctx* ctx, const cfear_cfar_grid* g, const uint8_t* d_polar, int n_steps, double max_distance,
+                                                                 float* d_xyi, int capacity, int* d_counts, int* d_rows, hipStream_t stream) {
+  const cfear_cfar_grid_plan& G = g->plan;
+  if ((reinterpret_cast<uintptr_t>(d_polar) & 3) != 0) return cfear_fail(ctx, CFEAR_ERR_INVALID, "filter_cfar_grid: polar buffer must be 4-byte aligned");
+  const size_t n_img = (size_t)n_steps * G.n_sources, blocks = cfar_grid_blocks(g, (size_t)n_steps), clouds = (size_t)n_steps * G.n_clouds;
+  if (n_img * ctx->A > 0x7FFFFFFFULL || blocks * ctx->A > 0x7FFFFFFFULL || clouds * ctx->A > 0x7FFFFFFFULL)
+    return cfear_fail(ctx, CFEAR_ERR_UNSUPPORTED, "filter_cfar_grid: too many rows");
+  CfarParams P;  // the launch's: the range gate, the rows and their masks (window, guard, scaling and static threshold are each set's)
+  CFEAR_TRY(cfar_params_det(ctx, G.sets[0], max_distance, &P));
+  const size_t mask_rows = blocks * P.A;
+  int* d_count = d_rows; int* d_base = d_count + mask_rows; int* d_tot = d_base + mask_rows;
+  uint32_t* d_mask = reinterpret_cast<uint32_t*>(d_tot + blocks);
+  const int* tab = g->d_tab;
+  if (g->shared) {
+    const int pad = (G.max_reach + 3) & ~3, rr = (P.R + 255) & ~255;
+    const size_t lds = sizeof(uint32_t) * ((size_t)pad + rr + pad + 4);
+    if (P.R <= CFAR_BLOCK * 16)
+      hipLaunchKernelGGL((cfar_detect_grid_kernel<16>), dim3((unsigned)(n_img * P.A)), dim3(CFAR_BLOCK), lds, stream, d_polar, P, pad, rr, G.n_sources, G.n_pairs(), tab,
+                         static_cast<const CfarGridSet*>(g->d_sets), d_count, d_mask);
+    else
+      hipLaunchKernelGGL((cfar_detect_grid_kernel<32>), dim3((unsigned)(n_img * P.A)), dim3(CFAR_BLOCK), lds, stream, d_polar, P, pad, rr, G.n_sources, G.n_pairs(), tab,
+                         static_cast<const CfarGridSet*>(g->d_sets), d_count, d_mask);
+  } else {
+    const size_t set_rows = n_img * P.A;
+    for (int k = 0; k < G.n_sets(); k++) {
+      CfarParams Pk;
+      CFEAR_TRY(cfar_params_det(ctx, G.sets[(size_t)k], max_distance, &Pk));
+      CFEAR_TRY(cfar_launch_detect(ctx, Pk, d_polar, set_rows, d_count + k * set_rows, d_mask + k * set_rows * P.mask_words, stream));
+    }
+  }
+  hipLaunchKernelGGL(cfar_row_scan_kernel, dim3((unsigned)blocks), dim3(1024), 0, stream, d_count, P.A, d_base, d_tot);
+  CfarGridMap M;
+  M.cloud_pair = tab + G.n_sources + 1; M.cloud_set = M.cloud_pair + G.n_clouds; M.cloud_src = M.cloud_set + G.n_clouds;
+  M.n_clouds = G.n_clouds; M.nsrc = G.n_sources; M.n_pairs = G.n_pairs(); M.n_img = (int)n_img; M.per_set = g->shared ? 0 : 1;
+  const size_t rows = clouds * P.A;
+  hipLaunchKernelGGL(cfar_emit_grid_kernel, dim3((unsigned)((rows + 4 * CFAR_EMIT_ROWS - 1) / (4 * CFAR_EMIT_ROWS))), dim3(CFAR_BLOCK), 0, stream, d_polar, P, M, ctx->d_trig,
+                     d_count, d_base, d_tot, d_mask, d_xyi, capacity, d_counts, (long long)rows);
+  CFEAR_HIP_CHECK(ctx, hipGetLastError());
+  return CFEAR_OK;
+}
+
 extern "C" {
+
+int cfear_filter_cfar_grid_device(cfear_ctx* ctx, const uint8_t* d_polar, int n_sources, const cfear_seq_detector* dets, const int32_t* source, int n_clouds,
+                                  double max_distance, float* d_xyi, int capacity, int* d_counts) {
+  if (!ctx || !d_polar || !d_xyi || !d_counts || !dets || n_sources <= 0 || n_clouds <= 0 || capacity <= 0)
+    return cfear_fail(ctx, CFEAR_ERR_INVALID, "filter_cfar_grid: bad argument");
+  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  cfear_cfar_grid* g = ctx->cfar_grid;
+  const bool same = g && (int)g->dets.size() == n_clouds && g->plan.n_sources == n_sources && g->source.empty() == (source == nullptr) &&
+                    memcmp(g->dets.data(), dets, sizeof(cfear_seq_detector) * (size_t)n_clouds) == 0 &&
+                    (!source || memcmp(g->source.data(), source, sizeof(int32_t) * (size_t)n_clouds) == 0);
+  if (!same) {  // (a kernel in flight may read the previous call's tables)
+    cfear_cfar_grid* ng = nullptr;
+    CFEAR_TRY(cfear_cfar_grid_create(ctx, dets, source, n_clouds, n_sources, "filter_cfar_grid", &ng));
+    const hipError_t e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) { cfear_cfar_grid_destroy(ng); return cfear_fail(ctx, CFEAR_ERR_HIP, "filter_cfar_grid", e); }
+    cfear_cfar_grid_destroy(ctx->cfar_grid);
+    ctx->cfar_grid = g = ng;
+  }
+  const size_t need = cfear_cfar_grid_scratch_ints(ctx, g, 1);
+  if (need > ctx->d_cfar_rows.size()) {
+    if (ctx->d_cfar_rows) CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    CFEAR_TRY(ctx->d_cfar_rows.ensure(ctx, need, "hipMalloc cfar rows"));
+  }
+  return cfear_launch_cfar_grid(ctx, g, d_polar, 1, max_distance, d_xyi, capacity, d_counts, ctx->d_cfar_rows, ctx->stream);
+}
 
 int cfear_filter_cfar_device(cfear_ctx* ctx, const uint8_t* d_polar, int window_size, int nb_guard_cells, float false_alarm_rate,
                              double max_distance, cfear_cloud** cloud) {

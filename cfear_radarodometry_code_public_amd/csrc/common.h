@@ -67,6 +67,7 @@ struct cfear_ctx {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   DevBuf<unsigned char> d_scratch;  // scratch for the per-call feature / registration kernels
   DevBuf<int> d_cfar_rows;          // row counts / bases of cfear_filter_cfar_batch_device
+  struct cfear_cfar_grid* cfar_grid = nullptr;  // the plan and tables of the last cfear_filter_cfar_grid_device call (kept while the next call's dets / source equal them)
   DevBuf<double> d_drift;           // per-block partial sums of cfear_drift_device (drift.hip)
   // streams of the batched odometry objects of this context (cfear_synchronize waits for them too)
   std::vector<hipStream_t> aux_streams;
@@ -161,6 +162,18 @@ __attribute__((visibility("hidden"))) int cfear_launch_cfar_batch(cfear_ctx* ctx
                                                                   float false_alarm_rate, double max_distance, float* d_xyi, int capacity, int* d_counts,
                                                                   int* d_rows /* cfear_cfar_scratch_ints(ctx, n_scans) ints */, hipStream_t stream);
 __attribute__((visibility("hidden"))) size_t cfear_cfar_scratch_ints(const cfear_ctx* ctx, size_t n_scans);
+// ... several detectors over shared source images (cfar_grid.h): the plan of a (dets, source) pair and its tables on the device. `what`
+// prefixes the message of a refused value (CFEAR_ERR_INVALID: the cloud and the field named). The streams that read a grid are idle when
+// it is destroyed.
+struct cfear_cfar_grid;
+__attribute__((visibility("hidden"))) int cfear_cfar_grid_create(cfear_ctx* ctx, const cfear_seq_detector* dets, const int32_t* source, int n_clouds, int n_sources,
+                                                                 const char* what, cfear_cfar_grid** out);
+__attribute__((visibility("hidden"))) void cfear_cfar_grid_destroy(cfear_cfar_grid* g);
+__attribute__((visibility("hidden"))) size_t cfear_cfar_grid_scratch_ints(const cfear_ctx* ctx, const cfear_cfar_grid* g, size_t n_steps);
+// n_steps sweeps of g's n_sources images each -> n_steps x n_clouds clouds (step-major) of `capacity` points each and their true counts
+__attribute__((visibility("hidden"))) int cfear_launch_cfar_grid(cfear_ctx* ctx, const cfear_cfar_grid* g, const uint8_t* d_polar, int n_steps, double max_distance,
+                                                                 float* d_xyi, int capacity, int* d_counts,
+                                                                 int* d_rows /* cfear_cfar_grid_scratch_ints(ctx, g, n_steps) ints */, hipStream_t stream);
 
 // scans (keyframes + current) the batched registration kernels of register_step.hip are compiled for: pipeline.hip launches them
 // when submap_scan_size + 1 fits, its own 64-scan instantiation otherwise

@@ -579,6 +579,11 @@ struct cfear_odometry {
   cfear_seq_groups groups;             // the launch groups of seq_shapes (seq_groups.h), built with the device table
   DevBuf<int> d_group_list;            // [B] groups.list: what OdoParams::order points into until a sweep's work keys exist
   DevBuf<int> d_seq_group;             // [B] groups.group (order_groups_kernel)
+  // per-sequence CA-CFAR detectors over shared sweeps (cfear_odometry_set_sequence_detectors): the filter stage runs cfear_launch_cfar_grid. The
+  // clouds stay one per sequence, so seq_src stays empty (SeqParams::source is the k-strongest routes'); n_sources is the grid's with a source map
+  std::vector<cfear_seq_detector> seq_dets;  // [B]; empty: every sequence runs the context's detector
+  cfear_cfar_grid* det_grid = nullptr;       // the plan and device tables of seq_dets and their source map
+  bool det_map = false;                      // the detectors came with a source map
   long long sweeps = 0;                // sweeps processed since cfear_odometry_create / cfear_odometry_reset
 };
 static int odo_sources(const cfear_odometry* o) { return o->n_sources > 0 ? o->n_sources : o->B; }
@@ -654,11 +659,16 @@ static SeqParams seq_row_of(const cfear_params& p, int source, int cost, int sub
 }
 // may the rows be the sequences of `o` under the context's parameters? The fields that size memory or select a kernel are the object's
 // shapes: [n] the cost / submap_scan_size row q must carry (cfear_odometry_set_sequence_shapes), null: the context's
+// dets: [n] the detector row q must carry on a CA-CFAR object (cfear_odometry_set_sequence_detectors), null: the context's
 static const cfear_seq_shape* odo_shapes(const cfear_odometry* o) { return o->seq_shapes.empty() ? nullptr : o->seq_shapes.data(); }
-static int seq_rows_check(cfear_ctx* ctx, const cfear_odometry* o, const cfear_params* rows, int n, const char* what, const cfear_seq_shape* shapes) {
+static const cfear_seq_detector* odo_dets(const cfear_odometry* o) { return o->seq_dets.empty() ? nullptr : o->seq_dets.data(); }
+static int seq_rows_check(cfear_ctx* ctx, const cfear_odometry* o, const cfear_params* rows, int n, const char* what, const cfear_seq_shape* shapes,
+                          const cfear_seq_detector* dets) {
   const cfear_params& c = ctx->par;
   for (int q = 0; q < n; q++) {
     const cfear_params& r = rows[q];
+    const int want_window = dets ? dets[q].window_size : c.cfar_window_size, want_guard = dets ? dets[q].nb_guard_cells : c.cfar_nb_guard_cells;
+    const float want_rate = dets ? dets[q].false_alarm_rate : c.cfar_false_alarm_rate, want_z = dets ? dets[q].z_min : c.z_min;
     const int want_cost = shapes ? shapes[q].cost : c.cost, want_submap = shapes ? shapes[q].submap_scan_size : c.submap_scan_size;
     // k_strongest: any k up to the context's K. The filter runs with K and the object is sized for it; a sequence reads the last k of the
     // returns the filter kept of every bearing (cloud_step_block)
@@ -678,12 +688,13 @@ static int seq_rows_check(cfear_ctx* ctx, const cfear_odometry* o, const cfear_p
     else if (r.downsample_factor != c.downsample_factor) f = "downsample_factor";
     else if (r.radar_ccw != c.radar_ccw) f = "radar_ccw";
     else if (r.assoc_radius != c.assoc_radius) f = "assoc_radius";
-    else if (r.cfar_window_size != c.cfar_window_size) f = "cfar_window_size";
-    else if (r.cfar_nb_guard_cells != c.cfar_nb_guard_cells) f = "cfar_nb_guard_cells";
-    else if (r.cfar_false_alarm_rate != c.cfar_false_alarm_rate) f = "cfar_false_alarm_rate";
+    else if (r.cfar_window_size != want_window) f = dets ? "cfar_window_size (the sequence's detector says otherwise: cfear_odometry_set_sequence_detectors)" : "cfar_window_size";
+    else if (r.cfar_nb_guard_cells != want_guard) f = dets ? "cfar_nb_guard_cells (the sequence's detector says otherwise: cfear_odometry_set_sequence_detectors)" : "cfar_nb_guard_cells";
+    else if (r.cfar_false_alarm_rate != want_rate) f = dets ? "cfar_false_alarm_rate (the sequence's detector says otherwise: cfear_odometry_set_sequence_detectors)" : "cfar_false_alarm_rate";
     else if (r.cfar_max_points != c.cfar_max_points) f = "cfar_max_points";
     else if (r.cfar_max_distance != c.cfar_max_distance) f = "cfar_max_distance";
-    else if (o->filter == CFEAR_FILTER_CACFAR && r.z_min != c.z_min) f = "z_min (the CA-CFAR detector's static threshold)";
+    else if (o->filter == CFEAR_FILTER_CACFAR && r.z_min != want_z)
+      f = dets ? "z_min (the sequence's detector says otherwise: cfear_odometry_set_sequence_detectors)" : "z_min (the CA-CFAR detector's static threshold)";
     if (f) {
       char msg[640];
       snprintf(msg, sizeof(msg), "%s: row %d differs from the context's parameters in %s, which sizes memory or selects a kernel for the whole object "
@@ -745,7 +756,7 @@ static int seq_table_upload(cfear_ctx* ctx, cfear_odometry* o) {
 // (loud, never silent) and the table follows them
 static int odo_seq_sync(cfear_ctx* ctx, cfear_odometry* o, const char* what) {
   if (!o->d_seq || memcmp(&o->seq_par_seen, &ctx->par, sizeof(cfear_params)) == 0) return CFEAR_OK;
-  if (!o->seq_rows.empty()) CFEAR_TRY(seq_rows_check(ctx, o, o->seq_rows.data(), o->B, what, odo_shapes(o)));
+  if (!o->seq_rows.empty()) CFEAR_TRY(seq_rows_check(ctx, o, o->seq_rows.data(), o->B, what, odo_shapes(o), odo_dets(o)));
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   CFEAR_TRY(odo_join(ctx, o));
   CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
@@ -865,9 +876,11 @@ static int odo_shape_check(cfear_ctx* ctx, const cfear_odometry* o, const char* 
   snprintf(msg, sizeof(msg), "%s: submap_scan_size / k_strongest / filter_type changed after odometry_create, or a parity mode (cfear_tune NN_TIE_RULE / VOXEL_ORDER) was switched under the object", what);
   return cfear_fail(ctx, CFEAR_ERR_INVALID, msg);
 }
-// the CA-CFAR stage of n_scans sweeps (radar_driver.cpp:52-56) into clouds of o->cap_points points each
-static int odo_launch_cfar(cfear_ctx* ctx, cfear_odometry* o, const uint8_t* d_polar, int n_scans, float* d_xyi, int* d_counts, int* d_rows, hipStream_t st) {
-  return cfear_launch_cfar_batch(ctx, d_polar, n_scans, ctx->par.cfar_window_size, ctx->par.cfar_nb_guard_cells, ctx->par.cfar_false_alarm_rate,
+// the CA-CFAR stage of n_steps sweeps of every sequence (radar_driver.cpp:52-56) into clouds of o->cap_points points each, [step][sequence]: the
+// context's detector over one image per sequence, or the sequences' own over the sources they share
+static int odo_launch_cfar(cfear_ctx* ctx, cfear_odometry* o, const uint8_t* d_polar, int n_steps, float* d_xyi, int* d_counts, int* d_rows, hipStream_t st) {
+  if (o->det_grid) return cfear_launch_cfar_grid(ctx, o->det_grid, d_polar, n_steps, ctx->par.cfar_max_distance, d_xyi, o->cap_points, d_counts, d_rows, st);
+  return cfear_launch_cfar_batch(ctx, d_polar, n_steps * o->B, ctx->par.cfar_window_size, ctx->par.cfar_nb_guard_cells, ctx->par.cfar_false_alarm_rate,
                                  ctx->par.cfar_max_distance, d_xyi, o->cap_points, d_counts, d_rows, st);
 }
 
@@ -1610,6 +1623,7 @@ void cfear_odometry_destroy(cfear_ctx* ctx, cfear_odometry* o) {
   for (auto* v : {&o->ev_free[0], &o->ev_free[1], &o->ev_done}) for (hipEvent_t e : *v) if (e) (void)hipEventDestroy(e);
   if (o->sf) (void)hipStreamDestroy(o->sf);
   for (hipStream_t st : o->so) if (st) (void)hipStreamDestroy(st);
+  cfear_cfar_grid_destroy(o->det_grid);
   delete o;  // (and with it the device buffers)
 }
 
@@ -1800,6 +1814,9 @@ int cfear_odometry_step_cloud_device(cfear_ctx* ctx, cfear_odometry* o, const fl
   if (!o->seq_src.empty())
     return cfear_fail(ctx, CFEAR_ERR_UNSUPPORTED, "odometry_step_cloud: the object has a source map (cfear_odometry_set_sequence_sources), which the cloud route does not "
                       "read - it takes one cloud per sequence; clear the map (NULL) first");
+  if (o->det_map)
+    return cfear_fail(ctx, CFEAR_ERR_UNSUPPORTED, "odometry_step_cloud: the object has per-sequence detectors with a source map (cfear_odometry_set_sequence_detectors), "
+                      "which the cloud route does not read - it takes one cloud per sequence; clear them (NULL) first");
   for (size_t q = 0; q < o->seq_rows.size(); q++)
     if (o->seq_rows[q].k_strongest != ctx->par.k_strongest) {
       char msg[256];
@@ -1828,7 +1845,7 @@ int cfear_odometry_step_device(cfear_ctx* ctx, cfear_odometry* o, const uint8_t*
   if (o->filter == CFEAR_FILTER_CACFAR) {  // radar_driver.cpp:52-56, then the cloud route
     int rc = CFEAR_OK;
     if (o->profile && (rc = odo_timed_event(ctx, o, o->filter_events, ctx->stream)) != CFEAR_OK) return rc;
-    rc = odo_launch_cfar(ctx, o, d_polar, o->B, o->d_cloud, o->d_cloud_n, o->d_cfar_rows, ctx->stream);
+    rc = odo_launch_cfar(ctx, o, d_polar, 1, o->d_cloud, o->d_cloud_n, o->d_cfar_rows, ctx->stream);
     if (rc != CFEAR_OK) return rc;
     if (o->profile && (rc = odo_timed_event(ctx, o, o->filter_events, ctx->stream)) != CFEAR_OK) return rc;
     return odo_step_clouds(ctx, o, o->d_cloud, o->cap_points, o->d_cloud_n, true);
@@ -1989,7 +2006,8 @@ static int replay_ensure(cfear_ctx* ctx, cfear_odometry* o, int chunk, bool stag
     }
     o->rp_ready = true;
   }
-  const size_t sweep = (size_t)odo_sources(o) * ctx->A * ctx->R, slots = (size_t)odo_sources(o) * o->cap_points;  // (a source map: CFEAR_FILTER_KSTRONG only)
+  // (a CA-CFAR object's clouds are one per sequence whatever the sweeps they come from)
+  const size_t sweep = (size_t)odo_sources(o) * ctx->A * ctx->R, slots = (size_t)(o->filter == CFEAR_FILTER_CACFAR ? o->B : odo_sources(o)) * o->cap_points;
   if (chunk > o->rp_chunk) {
     CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(o->rp_stream));
     CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
@@ -2003,7 +2021,9 @@ static int replay_ensure(cfear_ctx* ctx, cfear_odometry* o, int chunk, bool stag
         CFEAR_TRY(o->rp_slots[i].ensure(ctx, slots * chunk, "hipMalloc replay slot buffers"));
       }
     }
-    if (o->filter == CFEAR_FILTER_CACFAR) CFEAR_TRY(o->rp_cfar_rows.ensure(ctx, cfear_cfar_scratch_ints(ctx, (size_t)o->B * chunk), "hipMalloc replay cfar rows"));
+    if (o->filter == CFEAR_FILTER_CACFAR)
+      CFEAR_TRY(o->rp_cfar_rows.ensure(ctx, o->det_grid ? cfear_cfar_grid_scratch_ints(ctx, o->det_grid, (size_t)chunk) : cfear_cfar_scratch_ints(ctx, (size_t)o->B * chunk),
+                                       "hipMalloc replay cfar rows"));
     o->rp_chunk = chunk;
   }
   if (staging && chunk > o->rp_polar_chunk) {
@@ -2025,7 +2045,7 @@ static int replay_ensure(cfear_ctx* ctx, cfear_odometry* o, int chunk, bool stag
 static int replay_impl_queue(cfear_ctx* ctx, cfear_odometry* o, const uint8_t* frames, bool on_device, int n_sweeps, cfear_sweep_record* d_records,
                              double* d_cov6) {
   const int nsrc = odo_sources(o);  // input sweeps per step: the sequences, or the sources of a source map
-  const size_t sweep = (size_t)nsrc * ctx->A * ctx->R, slots = (size_t)nsrc * o->cap_points;
+  const size_t sweep = (size_t)nsrc * ctx->A * ctx->R, slots = (size_t)(o->filter == CFEAR_FILTER_CACFAR ? o->B : nsrc) * o->cap_points;
   // chunk: enough sweeps for the filter to run at its streaming rate (>= ~16 k azimuth rows per launch) and for the copy of the
   // next chunk to hide behind the odometry kernels of this one, at most 256 MB per buffer (host route: of staged sweeps; device
   // route: of filter slots - there is no staging)
@@ -2057,7 +2077,7 @@ static int replay_impl_queue(cfear_ctx* ctx, cfear_odometry* o, const uint8_t* f
       CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(o->rp_polar[b], src, sweep * (size_t)cnt, hipMemcpyHostToDevice, o->rp_stream));
       src = o->rp_polar[b];
     }
-    const int frc = cfar ? odo_launch_cfar(ctx, o, src, cnt * o->B, o->rp_cloud[b], o->rp_cloud_n[b], o->rp_cfar_rows, o->rp_stream)  // radar_driver.cpp:52-56
+    const int frc = cfar ? odo_launch_cfar(ctx, o, src, cnt, o->rp_cloud[b], o->rp_cloud_n[b], o->rp_cfar_rows, o->rp_stream)  // radar_driver.cpp:52-56
                          : cfear_launch_kstrongest(ctx, src, cnt * nsrc, o->rp_slots[b], o->rp_stream, false, o->seq_zmin);  // radar_driver.cpp:58, pose-independent
     if (frc != CFEAR_OK) return frc;
     CFEAR_HIP_CHECK(ctx, hipEventRecord(o->rp_filt[b], o->rp_stream));
@@ -2113,10 +2133,12 @@ static int replay_check(cfear_ctx* ctx, cfear_odometry* o, const uint8_t* frames
   CFEAR_TRY(odo_shape_check(ctx, o, "odometry_replay"));
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   CFEAR_TRY(odo_seq_sync(ctx, o, "odometry_replay"));
-  // CA-CFAR reads the images as dwords: every chunk of the replay starts a whole number of sweeps (of B images) after `frames`, so the base and the
-  // sweep size decide the alignment of all of them - refused here, before any chunk has advanced the sequences' state
-  if (o->filter == CFEAR_FILTER_CACFAR && ((reinterpret_cast<uintptr_t>(frames) & 3) != 0 || (n_sweeps > 1 && (((size_t)o->B * ctx->A * ctx->R) & 3) != 0)))
-    return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_replay: filter_type CA-CFAR needs a 4-byte aligned recording and B * A * R a multiple of 4 (the detector reads whole dwords)");
+  // CA-CFAR reads the images as dwords: every chunk of the replay starts a whole number of sweeps (of B images, or of the sources the sequences'
+  // detectors share) after `frames`, so the base and the sweep size decide the alignment of all of them - refused here, before any chunk has
+  // advanced the sequences' state
+  if (o->filter == CFEAR_FILTER_CACFAR && ((reinterpret_cast<uintptr_t>(frames) & 3) != 0 || (n_sweeps > 1 && (((size_t)odo_sources(o) * ctx->A * ctx->R) & 3) != 0)))
+    return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_replay: filter_type CA-CFAR needs a 4-byte aligned recording and B * A * R a multiple of 4 (the detector reads whole "
+                      "dwords; B: the input sweeps per step)");
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   return odo_join(ctx, o);
 }
@@ -2268,7 +2290,7 @@ int cfear_odometry_surface(cfear_ctx* ctx, cfear_odometry* o, double res, int wi
 int cfear_odometry_set_sequence_params(cfear_ctx* ctx, cfear_odometry* o, const cfear_params* rows, int n_rows) {
   if (!ctx || !o || (rows && n_rows != o->B)) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_set_sequence_params: bad argument (n_rows must be the object's n_sequences)");
   CFEAR_TRY(seq_fresh_check(ctx, o, "odometry_set_sequence_params"));
-  if (rows) CFEAR_TRY(seq_rows_check(ctx, o, rows, n_rows, "odometry_set_sequence_params", odo_shapes(o)));
+  if (rows) CFEAR_TRY(seq_rows_check(ctx, o, rows, n_rows, "odometry_set_sequence_params", odo_shapes(o), odo_dets(o)));
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   CFEAR_TRY(odo_join(ctx, o));
   CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
@@ -2284,6 +2306,10 @@ int cfear_odometry_sequence_params(cfear_ctx* ctx, cfear_odometry* o, int sequen
   if (!ctx || !o || !out || sequence < 0 || sequence >= o->B) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_sequence_params: bad argument");
   *out = o->seq_rows.empty() ? ctx->par : o->seq_rows[(size_t)sequence];
   if (!o->seq_shapes.empty()) { out->cost = o->seq_shapes[(size_t)sequence].cost; out->submap_scan_size = o->seq_shapes[(size_t)sequence].submap_scan_size; }
+  if (!o->seq_dets.empty()) {
+    const cfear_seq_detector& d = o->seq_dets[(size_t)sequence];
+    out->cfar_window_size = d.window_size; out->cfar_nb_guard_cells = d.nb_guard_cells; out->cfar_false_alarm_rate = d.false_alarm_rate; out->z_min = d.z_min;
+  }
   return CFEAR_OK;
 }
 
@@ -2351,7 +2377,7 @@ int cfear_odometry_set_sequence_shapes(cfear_ctx* ctx, cfear_odometry* o, const 
     }
   }
   // a table whose rows would then disagree with their shapes (NULL: with the context's values again)
-  if (!o->seq_rows.empty()) CFEAR_TRY(seq_rows_check(ctx, o, o->seq_rows.data(), o->B, "odometry_set_sequence_shapes", shapes));
+  if (!o->seq_rows.empty()) CFEAR_TRY(seq_rows_check(ctx, o, o->seq_rows.data(), o->B, "odometry_set_sequence_shapes", shapes, odo_dets(o)));
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   CFEAR_TRY(odo_join(ctx, o));
   CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
@@ -2367,6 +2393,62 @@ int cfear_odometry_sequence_shape(cfear_ctx* ctx, cfear_odometry* o, int sequenc
   if (!ctx || !o || !out || sequence < 0 || sequence >= o->B) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_sequence_shape: bad argument");
   if (o->seq_shapes.empty()) { out->cost = ctx->par.cost; out->submap_scan_size = ctx->par.submap_scan_size; }
   else *out = o->seq_shapes[(size_t)sequence];
+  return CFEAR_OK;
+}
+
+// ---- per-sequence CA-CFAR detectors over shared sweeps (params/kstrong_vs_cfar/oxford-cfear-3-ca-cfar: window_size x false_alarm_rate) ---------
+int cfear_odometry_set_sequence_detectors(cfear_ctx* ctx, cfear_odometry* o, const cfear_seq_detector* dets, int n_rows, const int32_t* source, int n_sources) {
+  const char* what = "odometry_set_sequence_detectors";
+  if (!ctx || !o) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_set_sequence_detectors: bad argument");
+  if (o->filter != CFEAR_FILTER_CACFAR)
+    return cfear_fail(ctx, CFEAR_ERR_UNSUPPORTED, "odometry_set_sequence_detectors: the object runs the k-strongest filter (filter_type at creation); detectors are for "
+                      "filter_type CA-CFAR objects (per-sequence k_strongest and z_min: cfear_odometry_set_sequence_params, shared sweeps: cfear_odometry_set_sequence_sources)");
+  if (dets && n_rows != o->B) {
+    char msg[200];
+    snprintf(msg, sizeof(msg), "%s: n_rows = %d must be the object's n_sequences = %d", what, n_rows, o->B);
+    return cfear_fail(ctx, CFEAR_ERR_INVALID, msg);
+  }
+  if (dets && source && (n_sources < 1 || n_sources > o->B)) {
+    char msg[200];
+    snprintf(msg, sizeof(msg), "%s: n_sources = %d must be in 1..%d, the object's n_sequences", what, n_sources, o->B);
+    return cfear_fail(ctx, CFEAR_ERR_INVALID, msg);
+  }
+  CFEAR_TRY(seq_fresh_check(ctx, o, what));
+  cfear_cfar_grid* grid = nullptr;
+  if (dets) CFEAR_TRY(cfear_cfar_grid_create(ctx, dets, source, o->B, source ? n_sources : o->B, what, &grid));
+  // a table whose rows would then disagree with their detectors (NULL: with the context's values again)
+  if (!o->seq_rows.empty()) {
+    const int rc = seq_rows_check(ctx, o, o->seq_rows.data(), o->B, what, odo_shapes(o), dets);
+    if (rc != CFEAR_OK) { cfear_cfar_grid_destroy(grid); return rc; }
+  }
+  hipError_t e = hipSetDevice(ctx->device);
+  int rc = e == hipSuccess ? odo_join(ctx, o) : cfear_fail(ctx, CFEAR_ERR_HIP, what, e);
+  if (rc == CFEAR_OK && o->rp_stream && (e = hipStreamSynchronize(o->rp_stream)) != hipSuccess) rc = cfear_fail(ctx, CFEAR_ERR_HIP, what, e);
+  if (rc == CFEAR_OK && (e = hipStreamSynchronize(ctx->stream)) != hipSuccess) rc = cfear_fail(ctx, CFEAR_ERR_HIP, what, e);
+  // the step's row scratch for the new detections first: a failure leaves the object as it was
+  if (rc == CFEAR_OK) rc = o->d_cfar_rows.ensure(ctx, grid ? cfear_cfar_grid_scratch_ints(ctx, grid, 1) : cfear_cfar_scratch_ints(ctx, (size_t)o->B), "hipMalloc cfar rows");
+  if (rc != CFEAR_OK) { cfear_cfar_grid_destroy(grid); return rc; }
+  cfear_cfar_grid_destroy(o->det_grid);
+  o->det_grid = grid;
+  if (dets) o->seq_dets.assign(dets, dets + n_rows); else o->seq_dets.clear();
+  o->det_map = dets && source;
+  o->n_sources = o->det_map ? n_sources : 0;
+  // the staging and chunk buffers are sized per input sweep of a step and per detection: released here, allocated again by the next call that needs them
+  o->d_polar.release();
+  for (int i = 0; i < 2; i++) o->rp_polar[i].release();
+  o->rp_cfar_rows.release();
+  o->rp_chunk = 0; o->rp_polar_chunk = 0; o->rp_used_pending[0] = o->rp_used_pending[1] = false;
+  return CFEAR_OK;
+}
+
+int cfear_odometry_sequence_detector(cfear_ctx* ctx, cfear_odometry* o, int sequence, cfear_seq_detector* out) {
+  if (!ctx || !o || !out || sequence < 0 || sequence >= o->B) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_sequence_detector: bad argument");
+  if (o->seq_dets.empty()) {
+    out->window_size = ctx->par.cfar_window_size; out->nb_guard_cells = ctx->par.cfar_nb_guard_cells;
+    out->false_alarm_rate = ctx->par.cfar_false_alarm_rate; out->z_min = ctx->par.z_min;
+  } else {
+    *out = o->seq_dets[(size_t)sequence];
+  }
   return CFEAR_OK;
 }
 

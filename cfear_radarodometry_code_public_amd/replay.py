@@ -44,6 +44,43 @@ def param_grid(base, **axes):
     return rows
 
 
+# ... of a CA-CFAR base: offline_odometry.cpp:260-265 hands the worker's kstrong loop to nb_guard_cells, its covar_scale loop to window_size
+# and its regularization loop to false_alarm_rate (params/kstrong_vs_cfar/oxford-cfear-3-ca-cfar:28-30), so the detector axes sit in those
+# loops' positions: guard cells, then z_min, then the window, the rate innermost of the three
+CFAR_GRID_ORDER = tuple({"k_strongest": "cfar_nb_guard_cells", "covar_scale": "cfar_window_size", "regularization": "cfar_false_alarm_rate"}.get(k, k)
+                        for k in GRID_ORDER)
+
+
+def cfar_grid(base, **axes):
+    """param_grid for a filter_type CA-CFAR base with the detector's cfar_nb_guard_cells, cfar_window_size and cfar_false_alarm_rate as
+    axes, in the loop positions the reference's worker gives them (utils/worker:61-77 through offline_odometry.cpp:260-265): ...
+    res, cfar_nb_guard_cells, z_min, loss, loss_limit, cfar_window_size, cfar_false_alarm_rate, weight_intensity, weight_opt
+    innermost. k_strongest, covar_scale and regularization are no axes here (their loops carry the detector's values). -> list of
+    capi.Params, job 1 first - what replay_grid runs as the sequences of one object. Pure Python (no device)."""
+    import itertools
+    if int(base.filter_type) != capi.FILTER_CACFAR:
+        raise ValueError("cfar_grid: the base's filter_type is not CA-CFAR (param_grid builds k-strongest grids)")
+    for k in axes:
+        if not hasattr(base, k):
+            raise AttributeError(k)
+        if k in ("k_strongest", "covar_scale", "regularization"):
+            raise ValueError("cfar_grid: %s is no axis of a CA-CFAR grid (the worker's loop of that name carries a detector value)" % k)
+    names = [k for k in CFAR_GRID_ORDER if k in axes] + [k for k in axes if k not in CFAR_GRID_ORDER]
+    rows = []
+    for values in itertools.product(*[list(axes[k]) for k in names]):
+        p = capi.Params.from_buffer_copy(base)
+        for k, v in zip(names, values):
+            setattr(p, k, v)
+        rows.append(p)
+    return rows
+
+
+def grid_detectors(rows):
+    """The capi.SeqDetector of every row of a CA-CFAR grid (its cfar_window_size, cfar_nb_guard_cells, cfar_false_alarm_rate and z_min):
+    what Odometry.set_sequence_detectors takes before the table. Pure Python (no device)."""
+    return [capi.SeqDetector(int(r.cfar_window_size), int(r.cfar_nb_guard_cells), float(r.cfar_false_alarm_rate), float(r.z_min)) for r in rows]
+
+
 def grid_context_params(rows):
     """The parameters of the context a grid's rows run under: a copy of rows[0] with k_strongest the largest of the rows - the filter runs
     with it and the object is sized for it, every row takes its own k strongest out of those (cfear_odometry_set_sequence_params) - and
@@ -110,7 +147,8 @@ def replay_grid(frames, rows, A=None, R=None, gt=None, device=0, piece=256, cont
     agree in the object-wide fields (param_grid of one base does; k_strongest and submap_scan_size may be axes: the context then runs with
     the largest of each, grid_context_params, unless context_params says otherwise; so may cost: rows that differ from the context in cost
     or submap_scan_size run under their own shapes, grid_shapes). The recording is the single source sweep of every sequence: it is
-    copied and filtered once per sweep. options: a capi.FuserOptions for every row or a list of one per row (fuser_grid builds both
+    copied and filtered once per sweep. Rows of filter_type CA-CFAR (cfar_grid) run under their own detectors over that one source
+    (Odometry.set_sequence_detectors): the sweep is staged and its prefix sums built once, every distinct detector decided once. options: a capi.FuserOptions for every row or a list of one per row (fuser_grid builds both
     lists); None: the fuser's defaults. -> dict(poses [n, len(rows), 3], records, drift: per row KITTI drift against gt ([n, 4, 4]
     poses) or None). drift_on: "host" - kitti.drift row by row; "device" - all rows in one cfear_drift_host call against a plan of
     gt[:n] (capi.DriftPlan), each row's dict then also holds the per-length table as kitti.drift_by_length returns it."""
@@ -128,8 +166,12 @@ def replay_grid(frames, rows, A=None, R=None, gt=None, device=0, piece=256, cont
         shapes = grid_shapes(rows, cpar)
         if shapes is not None:
             odo.set_sequence_shapes(shapes)
-        odo.set_sequence_params(rows)
-        odo.set_sequence_sources(np.zeros(len(rows), dtype=np.int32), 1)
+        if int(cpar.filter_type) == capi.FILTER_CACFAR:  # every row its own detector over the one source (cfar_grid), then the table that carries them
+            odo.set_sequence_detectors(grid_detectors(rows), np.zeros(len(rows), dtype=np.int32), 1)
+            odo.set_sequence_params(rows)
+        else:
+            odo.set_sequence_params(rows)
+            odo.set_sequence_sources(np.zeros(len(rows), dtype=np.int32), 1)
         if options is not None:
             opts = options if isinstance(options, capi.FuserOptions) else list(options)
             if not isinstance(opts, capi.FuserOptions) and len(opts) != len(rows):

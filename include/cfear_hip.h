@@ -194,6 +194,24 @@ int cfear_filter_cfar_device(cfear_ctx* ctx, const uint8_t* d_polar, int window_
  * cfear_cloud_upload-style consumers or a caller's own kernels; sizes are known on the device without a host round trip. */
 int cfear_filter_cfar_batch_device(cfear_ctx* ctx, const uint8_t* d_polar, int n_scans, int window_size, int nb_guard_cells,
                                    float false_alarm_rate, double max_distance, float* d_xyi, int capacity, int* d_counts);
+/* One CA-CFAR detector of a grid (launch/oxford/eval/params/kstrong_vs_cfar/oxford-cfear-3-ca-cfar sweeps window_size x
+ * false_alarm_rate, and guard cells and z_min are loops of the worker too): what AzimuthCACFAR takes besides the object-wide range_res,
+ * min_distance and max_distance. */
+typedef struct cfear_seq_detector {
+  int32_t window_size, nb_guard_cells; /* >= 1, >= 0 */
+  float false_alarm_rate;              /* > 0, finite */
+  float z_min;                         /* the static threshold (cfar.cpp:45), finite */
+} cfear_seq_detector;
+/* Several detectors over shared images in one pass: d_polar holds n_sources images back to back, cloud c (of n_clouds) is the detections
+ * of image source[c] under dets[c] (source NULL: cloud c reads image c, n_sources must be n_clouds) and goes to d_xyi + c * capacity * 3,
+ * its true count to d_counts[c] - bit for bit what cfear_filter_cfar_batch_device gives for that image under a context whose z_min is
+ * dets[c].z_min. A source row is staged and its prefix sum of squares built ONCE; every distinct (source, detector) is decided against it
+ * once, however many clouds ask for it. Rows of a multiple of 4 bins up to 8192 with nb_guard_cells + window_size <= 2048 take that shared
+ * kernel; every other shape cfear_filter_cfar_batch_device accepts runs its detectors once per distinct detector instead, same clouds.
+ * CFEAR_ERR_INVALID for a bad detector or source (the message names the cloud and the field). Asynchronous on the context stream (a call
+ * whose dets / source differ from the previous call's waits for the stream first: the table on the device is replaced). */
+int cfear_filter_cfar_grid_device(cfear_ctx* ctx, const uint8_t* d_polar, int n_sources, const cfear_seq_detector* dets, const int32_t* source,
+                                  int n_clouds, double max_distance, float* d_xyi, int capacity, int* d_counts);
 /* Upload an existing cloud: xyi = n x (x, y, intensity) floats. */
 int cfear_cloud_upload(cfear_ctx* ctx, const float* xyi, int n, cfear_cloud** cloud);
 int cfear_cloud_size(cfear_ctx* ctx, const cfear_cloud* cloud, int* n);
@@ -430,7 +448,7 @@ int cfear_odometry_sequence_params(cfear_ctx* ctx, cfear_odometry* odo, int sequ
 /* source[q] in [0, n_sources): the input sweep sequence q reads (1 <= n_sources <= n_sequences). Afterwards cfear_odometry_step_device /
  * _step_host take n_sources sweeps and the replay entry points n_sweeps x n_sources x A x R bytes instead of n_sequences per sweep: a
  * shared sweep is stored, copied and filtered once. NULL: identity (one sweep per sequence). k-strongest objects only: a CA-CFAR object
- * refuses a map, and cfear_odometry_step_cloud_device refuses to run while one is set (both CFEAR_ERR_UNSUPPORTED). A source out of
+ * refuses a map (its sequences share sweeps through cfear_odometry_set_sequence_detectors, whose clouds stay per sequence), and cfear_odometry_step_cloud_device refuses to run while one is set (both CFEAR_ERR_UNSUPPORTED). A source out of
  * range: CFEAR_ERR_INVALID, nothing changed. As the table: only before the first sweep since create / reset; reset keeps it.
  * Synchronises the context stream. */
 int cfear_odometry_set_sequence_sources(cfear_ctx* ctx, cfear_odometry* odo, const int32_t* source, int n_sequences, int n_sources);
@@ -463,6 +481,28 @@ typedef struct cfear_seq_shape {
 int cfear_odometry_set_sequence_shapes(cfear_ctx* ctx, cfear_odometry* odo, const cfear_seq_shape* shapes, int n_rows);
 /* The shape sequence q runs with: shapes[q], or the context's cost and submap_scan_size without shapes. */
 int cfear_odometry_sequence_shape(cfear_ctx* ctx, cfear_odometry* odo, int sequence, cfear_seq_shape* out);
+/* ---- Per-sequence CA-CFAR detectors over shared sweeps: the detector grid of 4_filter_eval (params/kstrong_vs_cfar/oxford-cfear-3-ca-cfar:
+ * window_size x false_alarm_rate, 49 jobs per recording; nb_guard_cells and z_min are loops too) as sequences of one filter_type CA-CFAR
+ * object. dets[q]: the detector of sequence q (n_rows must be the object's n_sequences); source[q] in [0, n_sources): the sweep it reads
+ * (NULL: one sweep per sequence, n_sources is ignored). NULL dets: back to the context's detector and one sweep per sequence. Afterwards
+ * cfear_odometry_step_device / _step_host take n_sources sweeps and the replay entry points n_sweeps x n_sources x A x R bytes (the
+ * dword rule of the replay is on n_sources x A x R then); a shared sweep is stored, copied and staged once, its prefix sums are built once
+ * and every distinct (source, detector) is decided once (cfear_filter_cfar_grid_device); the clouds stay one per sequence, so the feature
+ * and registration kernels and both replay shapes run as before, and sequence q gives bit for bit what the only sequence of a CA-CFAR
+ * object under a context with dets[q] (and the row's other values) gives on the same sweeps. cfar_max_points and cfar_max_distance stay
+ * the context's. Once set, cfear_odometry_set_sequence_params compares row q's cfar_window_size, cfar_nb_guard_cells,
+ * cfar_false_alarm_rate and z_min with dets[q] instead of the context's, and cfear_odometry_sequence_params(q) reports dets[q]'s values;
+ * setting detectors while a table exists whose rows would then disagree is CFEAR_ERR_INVALID. cfear_odometry_step_cloud_device refuses to
+ * run while detectors with a source map are set (CFEAR_ERR_UNSUPPORTED: it takes one cloud per sequence).
+ * CFEAR_ERR_UNSUPPORTED on a k-strongest object. CFEAR_ERR_INVALID (row and field named, nothing changed) for window_size < 1,
+ * nb_guard_cells < 0, a false_alarm_rate that is not finite or <= 0, a z_min that is not finite, a source outside [0, n_sources),
+ * n_sources outside 1 .. n_sequences, n_rows other than n_sequences, and on an object that has processed a sweep since
+ * cfear_odometry_create / cfear_odometry_reset. cfear_odometry_reset keeps the detectors. Composes with shapes, the parameter table, the
+ * fuser options, the cost-sampling covariance, both replay shapes and cfear_odometry_status. Synchronises the context stream. */
+int cfear_odometry_set_sequence_detectors(cfear_ctx* ctx, cfear_odometry* odo, const cfear_seq_detector* dets, int n_rows, const int32_t* source,
+                                          int n_sources);
+/* The detector sequence q runs with: dets[q], or the context's cfar_* values and z_min without a call. */
+int cfear_odometry_sequence_detector(cfear_ctx* ctx, cfear_odometry* odo, int sequence, cfear_seq_detector* out);
 /* ---- The fuser's own switches on the batched routes (OdometryKeyframeFuser::Parameters soft_constraint and use_guess,
  * odometrykeyframefuser.h:94; offline_odometry.cpp:166,273-274; the third loop of the evaluation grid, utils/worker:43), per object or per
  * sequence. They are not in cfear_params (whose layout is fixed); the defaults are what the batched routes did before: 0, 1. */
