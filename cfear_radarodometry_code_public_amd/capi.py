@@ -104,6 +104,25 @@ SWEEP_RECORD_DTYPE = np.dtype([("pose", "f8", 3), ("final_cost", "f8"), ("outer_
 assert SWEEP_RECORD_DTYPE.itemsize == 80
 
 
+# cfear_keyframe_node / cfear_keyframe_cell (include/cfear_hip.h): the keyframe graph of the batched routes (AddToGraph,
+# odometrykeyframefuser.cpp:428-445): a RadarScan node with its odometry constraint to the previous keyframe, and one of its cells
+class KeyframeNode(C.Structure):
+    _fields_ = [("index", C.c_int32), ("sweep", C.c_int32), ("n_cells", C.c_int32), ("prev", C.c_int32), ("pose", C.c_double * 3),
+                ("motion", C.c_double * 3), ("t_be", C.c_double * 3), ("information", C.c_double * 36)]
+
+
+class KeyframeCell(C.Structure):
+    _fields_ = [("mean", C.c_double * 2), ("normal", C.c_double * 2), ("cov", C.c_double * 3), ("scale", C.c_double),
+                ("nsamples", C.c_int32), ("pad_", C.c_int32)]
+
+
+KEYFRAME_NODE_DTYPE = np.dtype([("index", "i4"), ("sweep", "i4"), ("n_cells", "i4"), ("prev", "i4"), ("pose", "f8", 3), ("motion", "f8", 3),
+                                ("t_be", "f8", 3), ("information", "f8", (6, 6))])
+KEYFRAME_CELL_DTYPE = np.dtype([("mean", "f8", 2), ("normal", "f8", 2), ("cov", "f8", 3), ("scale", "f8"), ("nsamples", "i4"), ("pad_", "i4")])
+assert KEYFRAME_NODE_DTYPE.itemsize == C.sizeof(KeyframeNode) == 376 and KEYFRAME_CELL_DTYPE.itemsize == C.sizeof(KeyframeCell) == 72
+KF_NODES, KF_CELLS = 1, 2  # CFEAR_KF_NODES / CFEAR_KF_CELLS
+STATUS_CELLS_LOST, STATUS_POINTS_LOST, STATUS_KEYFRAMES_DROPPED = 1, 2, 4  # the bits of a sequence's word in cfear_odometry_status
+
 
 class Drift(C.Structure):
     """cfear_drift (include/cfear_hip.h): the KITTI drift of one trajectory with its per-length table (100 ... 800 m)"""
@@ -132,6 +151,8 @@ EXPORTS = [
     "cfear_odometry_set_sequence_shapes", "cfear_odometry_sequence_shape",
     "cfear_odometry_set_sequence_detectors", "cfear_odometry_sequence_detector",
     "cfear_odometry_covariances", "cfear_odometry_status", "cfear_odometry_summary", "cfear_odometry_profile", "cfear_odometry_profile_read", "cfear_odometry_profile_read_stages", "cfear_odometry_phase_times", "cfear_time_kstrongest",
+    "cfear_keyframe_constraint", "cfear_odometry_set_keyframe_recording", "cfear_odometry_keyframe_counts", "cfear_odometry_keyframe_nodes",
+    "cfear_odometry_keyframe_cells", "cfear_odometry_keyframe_scans",
     "cfear_drift_segments", "cfear_drift_plan_create", "cfear_drift_plan_release", "cfear_drift_device", "cfear_drift_host",
 ]
 
@@ -232,6 +253,12 @@ def lib():
         "cfear_odometry_profile_read_stages": (C.c_int, [vp, vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int)]),
         "cfear_odometry_phase_times": (C.c_int, [vp, vp, C.c_int, vp]),
         "cfear_time_kstrongest": (C.c_int, [vp, u8p, C.c_int, u32p, C.c_int, C.c_int, C.POINTER(C.c_double)]),
+        "cfear_keyframe_constraint": (C.c_int, [f64p, f64p, f64p, f64p, f64p]),
+        "cfear_odometry_set_keyframe_recording": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int]),
+        "cfear_odometry_keyframe_counts": (C.c_int, [vp, vp, i32p, i32p]),
+        "cfear_odometry_keyframe_nodes": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, C.c_int, C.POINTER(C.c_int)]),
+        "cfear_odometry_keyframe_cells": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, C.c_int, C.POINTER(C.c_int)]),
+        "cfear_odometry_keyframe_scans": (C.c_int, [vp, vp, C.c_int, i32p, C.c_int, C.POINTER(vp)]),
         "cfear_drift_segments": (C.c_int, [f64p, C.c_int, i32p, i32p, i32p, C.c_int, C.POINTER(C.c_int)]),
         "cfear_drift_plan_create": (C.c_int, [vp, f64p, C.c_int, C.POINTER(vp)]),
         "cfear_drift_plan_release": (None, [vp, vp]),
@@ -254,6 +281,20 @@ def surface_dims(res, width, x0=0.0, y0=0.0):
     if rc != 0:
         raise CfearError("cfear_surface_dims failed rc=%d" % rc)
     return p.value, nx.value, ny.value
+
+
+def keyframe_constraint(from_xyt, to_xyt, cov6):
+    """cfear_keyframe_constraint (host only, no device): AddToGraph's odometry constraint (odometrykeyframefuser.cpp:435-440) from the
+    new keyframe's pose, the previous one's and cov_current [6, 6] -> (t_be (x, y, theta), information [6, 6]). Raises CfearError for a
+    non-finite input or a singular covariance."""
+    f = np.ascontiguousarray(from_xyt, dtype=np.float64).reshape(3)
+    t = np.ascontiguousarray(to_xyt, dtype=np.float64).reshape(3)
+    c = np.ascontiguousarray(cov6, dtype=np.float64).reshape(36)
+    tbe, info = np.zeros(3), np.zeros(36)
+    rc = lib().cfear_keyframe_constraint(f.ctypes.data, t.ctypes.data, c.ctypes.data, tbe.ctypes.data, info.ctypes.data)
+    if rc != 0:
+        raise CfearError("cfear_keyframe_constraint failed rc=%d" % rc)
+    return tbe, info.reshape(6, 6)
 
 
 def _gt34(gt):
@@ -963,6 +1004,43 @@ class Odometry:
         c._check(L.cfear_odometry_phase_times(c._h, self._h, -1, buf.ctypes.data), "cfear_odometry_phase_times")
         return buf
 
+    # ---- the keyframe graph (AddToGraph, odometrykeyframefuser.cpp:428-445) ----
+    def record_keyframes(self, what=KF_NODES | KF_CELLS, max_keyframes=1024, max_cells=0):
+        """cfear_odometry_set_keyframe_recording: what = 0 (off), KF_NODES or KF_NODES | KF_CELLS; the capacities are per sequence (nodes;
+        cells summed over its keyframes). Switching on needs an object that has processed no sweep since it was created / reset."""
+        self._ctx._check(self._ctx._L.cfear_odometry_set_keyframe_recording(self._ctx._h, self._h, int(what), int(max_keyframes), int(max_cells)),
+                         "cfear_odometry_set_keyframe_recording")
+
+    def keyframe_counts(self):
+        """-> (recorded [B], dropped [B]) keyframes per sequence"""
+        rec, drop = np.zeros(self.B, dtype=np.int32), np.zeros(self.B, dtype=np.int32)
+        self._ctx._check(self._ctx._L.cfear_odometry_keyframe_counts(self._ctx._h, self._h, rec.ctypes.data, drop.ctypes.data), "cfear_odometry_keyframe_counts")
+        return rec, drop
+
+    def keyframes(self, q):
+        """the recorded nodes of sequence q -> structured array of KEYFRAME_NODE_DTYPE"""
+        n = C.c_int()
+        self._ctx._check(self._ctx._L.cfear_odometry_keyframe_nodes(self._ctx._h, self._h, int(q), 0, None, 0, C.byref(n)), "cfear_odometry_keyframe_nodes")
+        out = np.zeros(max(n.value, 1), dtype=KEYFRAME_NODE_DTYPE)
+        self._ctx._check(self._ctx._L.cfear_odometry_keyframe_nodes(self._ctx._h, self._h, int(q), 0, out.ctypes.data, n.value, C.byref(n)), "cfear_odometry_keyframe_nodes")
+        return out[:n.value]
+
+    def keyframe_cells(self, q, i):
+        """the cells of keyframe i of sequence q, in the scan's order -> structured array of KEYFRAME_CELL_DTYPE"""
+        n = C.c_int()
+        self._ctx._check(self._ctx._L.cfear_odometry_keyframe_cells(self._ctx._h, self._h, int(q), int(i), None, 0, C.byref(n)), "cfear_odometry_keyframe_cells")
+        out = np.zeros(max(n.value, 1), dtype=KEYFRAME_CELL_DTYPE)
+        self._ctx._check(self._ctx._L.cfear_odometry_keyframe_cells(self._ctx._h, self._h, int(q), int(i), out.ctypes.data, n.value, C.byref(n)), "cfear_odometry_keyframe_cells")
+        return out[:n.value]
+
+    def keyframe_scans(self, q, indices):
+        """per-call Scans rebuilt from the recorded keyframes `indices` of sequence q in one launch (cfear_odometry_keyframe_scans): ready for
+        Context.register / get_cost; their downloadable cells carry intensities 0. -> list of Scan"""
+        idx = np.ascontiguousarray(indices, dtype=np.int32).reshape(-1)
+        arr = (C.c_void_p * len(idx))()
+        self._ctx._check(self._ctx._L.cfear_odometry_keyframe_scans(self._ctx._h, self._h, int(q), idx.ctypes.data, len(idx), arr), "cfear_odometry_keyframe_scans")
+        return [Scan(self._ctx, C.c_void_p(h)) for h in arr]
+
     def poses(self):
         out = np.zeros((self.B, 3))
         self._ctx._check(self._ctx._L.cfear_odometry_poses(self._ctx._h, self._h, out.ctypes.data), "cfear_odometry_poses")
@@ -970,7 +1048,8 @@ class Odometry:
 
     def status(self, per_sequence=False):
         """raises CfearError (rc=-6) if a scan of this object was truncated (cfear_odometry_status); per_sequence=True: returns the per-sequence
-        flag words instead of raising (bit 0 cells lost, bit 1 points lost)"""
+        flag words instead of raising (bit 0 = STATUS_CELLS_LOST, bit 1 = STATUS_POINTS_LOST, bit 2 = STATUS_KEYFRAMES_DROPPED: the sequence's keyframe
+        log is full - no error of the odometry, the call does not raise for it)"""
         if per_sequence:
             out = np.zeros(self.B, dtype=np.int32)
             rc = self._ctx._L.cfear_odometry_status(self._ctx._h, self._h, out.ctypes.data)

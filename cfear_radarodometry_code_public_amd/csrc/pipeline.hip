@@ -22,6 +22,7 @@
 #include "cov_sampling_dev.h"
 #include "surface_dev.h"
 #include "seq_groups.h"
+#include "keyframe_dev.h"
 
 namespace {
 
@@ -585,7 +586,21 @@ struct cfear_odometry {
   cfear_cfar_grid* det_grid = nullptr;       // the plan and device tables of seq_dets and their source map
   bool det_map = false;                      // the detectors came with a source map
   long long sweeps = 0;                // sweeps processed since cfear_odometry_create / cfear_odometry_reset
+  // the keyframe graph (cfear_odometry_set_keyframe_recording): while kf_what != 0 the recorder stage of keyframes.hip runs behind every
+  // registration stage and appends the keyframes of the sequences that fused to these
+  int kf_what = 0, kf_max = 0, kf_max_cells = 0;
+  DevBuf<cfear_keyframe_node> d_kf_nodes;  // [B][kf_max]
+  DevBuf<cfear_keyframe_cell> d_kf_cells;  // [B][kf_max_cells] (CFEAR_KF_CELLS)
+  DevBuf<int> d_kf_off;                    // [B][kf_max] a node's first cell in its sequence's cells
+  DevBuf<int> d_kf_counts;                 // [B][4] nodes recorded, keyframes dropped, cells used, 0
+  DevBuf<double> d_kf_tmot;                // [B][6] the recorder's copy of SeqState::Tmot (KfLog::tmot)
 };
+static KfLog odo_kf_log(const cfear_odometry* o) {
+  KfLog L;
+  L.what = o->kf_what; L.max_kf = o->kf_max; L.max_cells = o->kf_max_cells; L.pad_ = 0;
+  L.nodes = o->d_kf_nodes; L.cells = o->d_kf_cells; L.cell_off = o->d_kf_off; L.counts = o->d_kf_counts; L.tmot = o->d_kf_tmot;
+  return L;
+}
 static int odo_sources(const cfear_odometry* o) { return o->n_sources > 0 ? o->n_sources : o->B; }
 // a timing event from the pool, recorded on `st`
 static int odo_grow_pool(cfear_ctx* ctx, cfear_odometry* o) {
@@ -840,11 +855,15 @@ static void launch_register_kernel(const OdoParams& P_in, int count, hipStream_t
 // (the replay's per-sweep covariances): before the next sweep's features kernel may reuse a slot the registration read
 static void launch_register_step(const OdoParams& P, int count, hipStream_t st, cfear_odometry* o) {
   launch_register_kernel(P, count, st, o);
-  if (!P.cs.m && !P.cs.cov_out) return;  // (cs.m: sampling on; cs.ctx alone: the surface recording only)
-  if (CFEAR_COV_SAMPLING_NAIVE || P.rp.nn_tie != 0)  // (cov_sample_general)
-    hipLaunchKernelGGL(cov_sample_kernel<true>, dim3(count), dim3(BLOCK_R), 0, st, P, o->d_scratch_hdr, o->d_cov_work);
-  else
-    hipLaunchKernelGGL(cov_sample_kernel<false>, dim3(count), dim3(BLOCK_R), 0, st, P, o->d_scratch_hdr, o->d_cov_work);
+  if (P.cs.m || P.cs.cov_out) {  // (cs.m: sampling on; cs.ctx alone: the surface recording only)
+    if (CFEAR_COV_SAMPLING_NAIVE || P.rp.nn_tie != 0)  // (cov_sample_general)
+      hipLaunchKernelGGL(cov_sample_kernel<true>, dim3(count), dim3(BLOCK_R), 0, st, P, o->d_scratch_hdr, o->d_cov_work);
+    else
+      hipLaunchKernelGGL(cov_sample_kernel<false>, dim3(count), dim3(BLOCK_R), 0, st, P, o->d_scratch_hdr, o->d_cov_work);
+  }
+  // ... and the keyframe recorder (AddToGraph, :234-248 behind the sampling of :202-208: cov_work holds cov_current): the same sequences on the
+  // same stream, so the sub-batches of the overlap mode need nothing extra
+  if (o->kf_what) cfear_launch_keyframe_record(odo_kf_log(o), P, count, st, o->d_states, o->d_cov_work);
 }
 // the features stage of a sweep: `count` sequences from P.seq0 on, from the filter's slots ...
 static void launch_features_step(const cfear_ctx* ctx, const cfear_odometry* o, const OdoParams& P, const uint32_t* d_slots, int count, hipStream_t st) {
@@ -1627,6 +1646,16 @@ void cfear_odometry_destroy(cfear_ctx* ctx, cfear_odometry* o) {
   delete o;  // (and with it the device buffers)
 }
 
+// an empty keyframe log: no nodes, no drops, and the recorder's copy of Tmot the identity the states start with
+static int odo_kf_clear(cfear_ctx* ctx, cfear_odometry* o) {
+  std::vector<double> tm(6 * (size_t)o->B, 0.0);
+  for (int q = 0; q < o->B; q++) tm[6 * (size_t)q] = tm[6 * (size_t)q + 3] = 1.0;
+  CFEAR_HIP_CHECK(ctx, hipMemsetAsync(o->d_kf_counts, 0, sizeof(int) * 4 * (size_t)o->B, ctx->stream));
+  CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(o->d_kf_tmot, tm.data(), sizeof(double) * tm.size(), hipMemcpyHostToDevice, ctx->stream));
+  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // (tm is read until here)
+  return CFEAR_OK;
+}
+
 int cfear_odometry_reset(cfear_ctx* ctx, cfear_odometry* o) {
   if (!ctx || !o) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_reset: bad argument");
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
@@ -1641,6 +1670,7 @@ int cfear_odometry_reset(cfear_ctx* ctx, cfear_odometry* o) {
   CFEAR_HIP_CHECK(ctx, hipMemsetAsync(o->d_poses_out, 0, sizeof(double) * 3 * (size_t)o->B, ctx->stream));
   CFEAR_HIP_CHECK(ctx, hipMemsetAsync(o->d_cov_work, 0, sizeof(double) * 36 * (size_t)o->B, ctx->stream));
   if (o->d_flags) CFEAR_HIP_CHECK(ctx, hipMemsetAsync(o->d_flags, 0, sizeof(int) * ((size_t)o->B + 1), ctx->stream));
+  if (o->kf_what) CFEAR_TRY(odo_kf_clear(ctx, o));  // (the setting stays, the log starts again at keyframe 0)
   o->order_ready = false;
   o->surf_ready = false;
   o->sweeps = 0;  // (the parameter table, the source map and the fuser options stay)
@@ -2064,7 +2094,8 @@ static int replay_impl_queue(cfear_ctx* ctx, cfear_odometry* o, const uint8_t* f
   OdoParams OP = odo_params(ctx, o);
   if (!o->cov_on) OP.cs.ctx = nullptr;  // the replay routes do not record for cost surfaces
   o->surf_ready = false;
-  const bool persistent = o->B <= ctx->tune_replay_persistent_max && !OP.phase_times && !OP.wg_times;
+  // (the keyframe recorder is a stage behind the registration stage: with recording on the sweeps run as two launches, like the timed ones)
+  const bool persistent = o->B <= ctx->tune_replay_persistent_max && !OP.phase_times && !OP.wg_times && !o->kf_what;
   if (on_device) {  // the sweeps are ready at this point of the context stream: the replay stream (which reads them) starts there
     CFEAR_HIP_CHECK(ctx, hipEventRecord(o->rp_in, ctx->stream));
     CFEAR_HIP_CHECK(ctx, hipStreamWaitEvent(o->rp_stream, o->rp_in, 0));
@@ -2557,6 +2588,169 @@ int cfear_odometry_status(cfear_ctx* ctx, cfear_odometry* o, int32_t* per_sequen
     else memset(per_sequence, 0, sizeof(int) * (size_t)o->B);
   }
   return odo_capacity_check(ctx, o, "odometry_status");
+}
+
+// ---- the keyframe graph (AddToGraph, odometrykeyframefuser.cpp:428-445; keyframes.hip) -----------------------------------------------
+int cfear_odometry_set_keyframe_recording(cfear_ctx* ctx, cfear_odometry* o, int what, int max_keyframes, int max_cells) {
+  if (!ctx || !o) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_set_keyframe_recording: bad argument");
+  if (what != 0 && what != CFEAR_KF_NODES && what != (CFEAR_KF_NODES | CFEAR_KF_CELLS))
+    return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_set_keyframe_recording: what must be 0, CFEAR_KF_NODES or CFEAR_KF_NODES | CFEAR_KF_CELLS");
+  const bool cells = (what & CFEAR_KF_CELLS) != 0;
+  if (what && (max_keyframes < 1 || (cells && max_cells < 1)))
+    return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_set_keyframe_recording: max_keyframes (and with CFEAR_KF_CELLS max_cells) must be at least 1");
+  if (what) CFEAR_TRY(seq_fresh_check(ctx, o, "odometry_set_keyframe_recording"));
+  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  CFEAR_TRY(odo_join(ctx, o));
+  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // no recorder is running: the buffers may go
+  if (o->kf_what && o->d_flags) {  // a full log is the log's condition, not the object's: its status bit goes with the log
+    std::vector<int> f((size_t)o->B + 1);
+    CFEAR_HIP_CHECK(ctx, hipMemcpy(f.data(), o->d_flags, sizeof(int) * f.size(), hipMemcpyDeviceToHost));
+    for (int q = 1; q <= o->B; q++) f[(size_t)q] &= ~4;
+    CFEAR_HIP_CHECK(ctx, hipMemcpy(o->d_flags, f.data(), sizeof(int) * f.size(), hipMemcpyHostToDevice));
+  }
+  o->kf_what = 0;
+  o->d_kf_nodes.release(); o->d_kf_cells.release(); o->d_kf_off.release(); o->d_kf_counts.release(); o->d_kf_tmot.release();
+  if (!what) return CFEAR_OK;
+  const size_t B = (size_t)o->B;
+  const char* msg = "hipMalloc keyframe log";
+  CFEAR_TRY(odo_ensure_flags(ctx, o));  // (a full log is reported in the sequence's status word)
+  CFEAR_TRY(o->d_kf_nodes.ensure(ctx, B * (size_t)max_keyframes, msg));
+  CFEAR_TRY(o->d_kf_off.ensure(ctx, B * (size_t)max_keyframes, msg));
+  CFEAR_TRY(o->d_kf_counts.ensure(ctx, 4 * B, msg));
+  CFEAR_TRY(o->d_kf_tmot.ensure(ctx, 6 * B, msg));
+  if (cells) CFEAR_TRY(o->d_kf_cells.ensure(ctx, B * (size_t)max_cells, msg));
+  o->kf_max = max_keyframes; o->kf_max_cells = cells ? max_cells : 0;
+  CFEAR_TRY(odo_kf_clear(ctx, o));
+  o->kf_what = what;
+  return CFEAR_OK;
+}
+
+// the reading calls' common start: recording on, the context stream drained; `cnt`: the sequence's four counters (sequence < 0: none)
+static int odo_kf_read(cfear_ctx* ctx, cfear_odometry* o, const char* what, int sequence, int cnt[4]) {
+  char msg[160];
+  if (!ctx || !o) { snprintf(msg, sizeof(msg), "%s: bad argument", what); return cfear_fail(ctx, CFEAR_ERR_INVALID, msg); }
+  if (!o->kf_what) { snprintf(msg, sizeof(msg), "%s: keyframe recording is off (cfear_odometry_set_keyframe_recording)", what); return cfear_fail(ctx, CFEAR_ERR_INVALID, msg); }
+  if (cnt && (sequence < 0 || sequence >= o->B)) { snprintf(msg, sizeof(msg), "%s: sequence %d of %d", what, sequence, o->B); return cfear_fail(ctx, CFEAR_ERR_INVALID, msg); }
+  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  CFEAR_TRY(odo_join(ctx, o));
+  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  if (cnt) CFEAR_HIP_CHECK(ctx, hipMemcpy(cnt, o->d_kf_counts + 4 * (size_t)sequence, sizeof(int) * 4, hipMemcpyDeviceToHost));
+  return CFEAR_OK;
+}
+
+int cfear_odometry_keyframe_counts(cfear_ctx* ctx, cfear_odometry* o, int32_t* recorded, int32_t* dropped) {
+  CFEAR_TRY(odo_kf_read(ctx, o, "odometry_keyframe_counts", -1, nullptr));
+  std::vector<int> c(4 * (size_t)o->B);
+  CFEAR_HIP_CHECK(ctx, hipMemcpy(c.data(), o->d_kf_counts, sizeof(int) * c.size(), hipMemcpyDeviceToHost));
+  for (int q = 0; q < o->B; q++) {
+    if (recorded) recorded[q] = c[4 * (size_t)q];
+    if (dropped) dropped[q] = c[4 * (size_t)q + 1];
+  }
+  return CFEAR_OK;
+}
+
+int cfear_odometry_keyframe_nodes(cfear_ctx* ctx, cfear_odometry* o, int sequence, int first, cfear_keyframe_node* nodes, int capacity, int* n) {
+  int cnt[4];
+  CFEAR_TRY(odo_kf_read(ctx, o, "odometry_keyframe_nodes", sequence, cnt));
+  if (first < 0 || capacity < 0 || (capacity > 0 && !nodes)) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_keyframe_nodes: bad argument");
+  if (n) *n = cnt[0];
+  const int m = std::min(capacity, cnt[0] - first);
+  if (m > 0)
+    CFEAR_HIP_CHECK(ctx, hipMemcpy(nodes, o->d_kf_nodes + (size_t)sequence * o->kf_max + first, sizeof(cfear_keyframe_node) * (size_t)m, hipMemcpyDeviceToHost));
+  return CFEAR_OK;
+}
+
+// where the cells of keyframes 0 .. recorded - 1 of a sequence start in its cells, and (entry `recorded`) where they end
+static int odo_kf_offsets(cfear_ctx* ctx, cfear_odometry* o, int sequence, const int cnt[4], std::vector<int>& off) {
+  off.assign((size_t)cnt[0] + 1, 0);
+  if (cnt[0] > 0) CFEAR_HIP_CHECK(ctx, hipMemcpy(off.data(), o->d_kf_off + (size_t)sequence * o->kf_max, sizeof(int) * (size_t)cnt[0], hipMemcpyDeviceToHost));
+  off[(size_t)cnt[0]] = cnt[2];
+  return CFEAR_OK;
+}
+
+int cfear_odometry_keyframe_cells(cfear_ctx* ctx, cfear_odometry* o, int sequence, int index, cfear_keyframe_cell* cells, int capacity, int* n) {
+  int cnt[4];
+  CFEAR_TRY(odo_kf_read(ctx, o, "odometry_keyframe_cells", sequence, cnt));
+  if (!(o->kf_what & CFEAR_KF_CELLS)) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_keyframe_cells: the log was switched on without CFEAR_KF_CELLS");
+  if (index < 0 || index >= cnt[0] || capacity < 0 || (capacity > 0 && !cells)) {
+    char msg[160];
+    snprintf(msg, sizeof(msg), "odometry_keyframe_cells: keyframe %d of sequence %d (%d recorded), capacity %d", index, sequence, cnt[0], capacity);
+    return cfear_fail(ctx, CFEAR_ERR_INVALID, msg);
+  }
+  std::vector<int> off;
+  CFEAR_TRY(odo_kf_offsets(ctx, o, sequence, cnt, off));
+  const int nc = off[(size_t)index + 1] - off[(size_t)index];
+  if (n) *n = nc;
+  const int m = std::min(capacity, nc);
+  if (m > 0)
+    CFEAR_HIP_CHECK(ctx, hipMemcpy(cells, o->d_kf_cells + (size_t)sequence * o->kf_max_cells + off[(size_t)index], sizeof(cfear_keyframe_cell) * (size_t)m, hipMemcpyDeviceToHost));
+  return CFEAR_OK;
+}
+
+int cfear_odometry_keyframe_scans(cfear_ctx* ctx, cfear_odometry* o, int sequence, const int32_t* indices, int m, cfear_scan** scans) {
+  int cnt[4];
+  CFEAR_TRY(odo_kf_read(ctx, o, "odometry_keyframe_scans", sequence, cnt));
+  if (!(o->kf_what & CFEAR_KF_CELLS)) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_keyframe_scans: the log was switched on without CFEAR_KF_CELLS");
+  if (!indices || !scans || m < 1) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_keyframe_scans: bad argument");
+  for (int i = 0; i < m; i++) scans[i] = nullptr;
+  std::vector<int> off;
+  CFEAR_TRY(odo_kf_offsets(ctx, o, sequence, cnt, off));
+  const bool kd = ctx->tune_nn_tie == 2;
+  int nmax = 0;
+  for (int i = 0; i < m; i++) {
+    char msg[160];
+    if (indices[i] < 0 || indices[i] >= cnt[0]) {
+      snprintf(msg, sizeof(msg), "odometry_keyframe_scans: indices[%d] = %d, sequence %d has recorded %d keyframes", i, indices[i], sequence, cnt[0]);
+      return cfear_fail(ctx, CFEAR_ERR_INVALID, msg);
+    }
+    const int nc = off[(size_t)indices[i] + 1] - off[(size_t)indices[i]];
+    if (nc < 1) {
+      snprintf(msg, sizeof(msg), "odometry_keyframe_scans: keyframe %d of sequence %d has no cells (reference: 'error, cloud empty' + exit)", indices[i], sequence);
+      return cfear_fail(ctx, CFEAR_ERR_EMPTY, msg);
+    }
+    nmax = std::max(nmax, nc);
+  }
+  // working memory of the m workgroups (one block of the pool): the job table, the grid cursors and - parity mode - the kd build's stacks
+  const size_t part_doubles = kd ? 7 * (size_t)std::max(nmax, ctx->A * ctx->par.k_strongest) : 0;
+  const size_t jobs_b = align_up(sizeof(KfScanJob) * (size_t)m, 256), vcur_b = align_up(sizeof(int) * (GRID_CAP + 4), 256), part_b = align_up(sizeof(double) * part_doubles, 256);
+  void* work = nullptr;
+  size_t work_bytes = 0;
+  CFEAR_TRY(cfear_pool_alloc(ctx, jobs_b + (vcur_b + part_b) * (size_t)m, &work, &work_bytes));
+  unsigned char* wb = static_cast<unsigned char*>(work);
+  std::vector<KfScanJob> jobs((size_t)m);
+  int rc = CFEAR_OK;
+  for (int i = 0; i < m && rc == CFEAR_OK; i++) {
+    const int nc = off[(size_t)indices[i] + 1] - off[(size_t)indices[i]];
+    cfear_scan* s = new (std::nothrow) cfear_scan();
+    if (!s) { rc = cfear_fail(ctx, CFEAR_ERR_NOMEM, "scan alloc"); break; }
+    s->cap_points = nc; s->with_kd = kd; s->n_cells = nc;
+    void* blk = nullptr;
+    rc = cfear_pool_alloc(ctx, scan_layout(nc, nc, true, kd).total, &blk, &s->bytes);
+    if (rc != CFEAR_OK) { delete s; break; }
+    s->d_block = static_cast<unsigned char*>(blk);
+    scans[i] = s;
+    KfScanJob& J = jobs[(size_t)i];
+    J.hdr = scan_header(s->d_block, nc, nc, true, kd);
+    J.dst = reinterpret_cast<ScanDev*>(s->d_block);
+    J.src = o->d_kf_cells + (size_t)sequence * o->kf_max_cells + off[(size_t)indices[i]];
+    J.n = nc; J.part_doubles = (int)part_doubles;
+    J.vcur = reinterpret_cast<int*>(wb + jobs_b + (vcur_b + part_b) * (size_t)i);
+    J.part = kd ? reinterpret_cast<double*>(wb + jobs_b + (vcur_b + part_b) * (size_t)i + vcur_b) : nullptr;
+  }
+  hipError_t e = hipSuccess;
+  if (rc == CFEAR_OK) {
+    e = hipMemcpyAsync(wb, jobs.data(), sizeof(KfScanJob) * (size_t)m, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) {
+      cfear_launch_keyframe_scans(reinterpret_cast<const KfScanJob*>(wb), m, feature_params(ctx), ctx->stream);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // the job table is read until here
+    if (e != hipSuccess) rc = cfear_fail(ctx, CFEAR_ERR_HIP, "odometry_keyframe_scans", e);
+  }
+  cfear_pool_free(ctx, work, work_bytes);
+  if (rc != CFEAR_OK)
+    for (int i = 0; i < m; i++) { cfear_scan_release(ctx, scans[i]); scans[i] = nullptr; }
+  return rc;
 }
 
 int cfear_odometry_summary(cfear_ctx* ctx, cfear_odometry* o, int sequence, cfear_reg_summary* summary, int* n_cells,

@@ -6,7 +6,10 @@
 //
 // Input: a flat binary file of uint8 sweeps, frames x azimuths x range-bins, rows = azimuth
 // (radar_driver.cpp:92-98). Flags follow offline_odometry.cpp:152-193 where they exist there.
+#include <algorithm>
+#include <charconv>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -22,6 +25,49 @@ using namespace CFEAR_Radarodometry;
 static const char* arg(int argc, char** argv, const char* name, const char* def) {
   for (int i = 1; i + 1 < argc; i++) if (!strcmp(argv[i], name)) return argv[i + 1];
   return def;
+}
+
+// a double as Python's repr writes it (the shortest digits that read back to the same bits; fixed notation for decimal exponents
+// -4 .. 15, scientific otherwise): the g2o text of --store_graph equals what replay.write_g2o writes for the same graph, byte for byte
+static std::string repr_double(double v) {
+  if (std::isnan(v)) return "nan";
+  if (std::isinf(v)) return v < 0 ? "-inf" : "inf";
+  char buf[64];
+  const auto r = std::to_chars(buf, buf + sizeof(buf), v, std::chars_format::scientific);  // d[.ddd]e+XX, shortest round trip
+  std::string t(buf, r.ptr);
+  std::string out;
+  if (t[0] == '-') { out = "-"; t.erase(0, 1); }
+  const size_t e = t.find('e');
+  std::string digits = t.substr(0, e);
+  const int exp10 = atoi(t.c_str() + e + 1);
+  digits.erase(std::remove(digits.begin(), digits.end(), '.'), digits.end());
+  const int nd = (int)digits.size(), decpt = exp10 + 1;
+  if (decpt <= -4 || decpt > 16) {
+    out += digits.substr(0, 1);
+    if (nd > 1) out += "." + digits.substr(1);
+    char ex[16];
+    snprintf(ex, sizeof(ex), "e%c%02d", exp10 < 0 ? '-' : '+', exp10 < 0 ? -exp10 : exp10);
+    return out + ex;
+  }
+  if (decpt <= 0) return out + "0." + std::string((size_t)-decpt, '0') + digits;
+  if (decpt >= nd) return out + digits + std::string((size_t)(decpt - nd), '0') + ".0";
+  return out + digits.substr(0, (size_t)decpt) + "." + digits.substr((size_t)decpt);
+}
+
+// the keyframe graph of sequence 0 as g2o text (replay.write_g2o): VERTEX_SE2 per node, EDGE_SE2 to the previous keyframe with the upper
+// triangle of the information's (x, y, yaw) block
+static void write_g2o(const std::string& path, const std::vector<cfear_keyframe_node>& nodes) {
+  std::ofstream f(path);
+  for (const auto& nd : nodes) f << "VERTEX_SE2 " << nd.index << " " << repr_double(nd.pose[0]) << " " << repr_double(nd.pose[1]) << " " << repr_double(nd.pose[2]) << "\n";
+  static const int ix[3] = {0, 1, 5};
+  for (const auto& nd : nodes) {
+    if (nd.prev < 0) continue;
+    f << "EDGE_SE2 " << nd.index << " " << nd.prev;
+    for (int i = 0; i < 3; i++) f << " " << repr_double(nd.t_be[i]);
+    for (int i = 0; i < 3; i++)
+      for (int j = i; j < 3; j++) f << " " << repr_double(nd.information[6 * ix[i] + ix[j]]);
+    f << "\n";
+  }
 }
 
 int main(int argc, char** argv) {
@@ -41,7 +87,10 @@ int main(int argc, char** argv) {
            "       [--replay 1]   whole recording through cfear_odometry_replay_host (pieces of 256 sweeps in pinned memory, no\n"
            "                      host round trip per sweep) instead of one CallbackOffline + pointcloudCallback per sweep; --covar_sampling and\n"
            "                      --cov_file work there too (cfear_odometry_set_cov_sampling, cfear_odometry_replay_host_cov), and so does\n"
-           "                      --soft_constraint (cfear_odometry_set_fuser_options); Oxford sweeps only\n");
+           "                      --soft_constraint (cfear_odometry_set_fuser_options); Oxford sweeps only\n"
+           "       [--store_graph graph.g2o] with --replay 1: the keyframe graph (AddToGraph, odometrykeyframefuser.cpp:428-445) is recorded on the device\n"
+           "                      (cfear_odometry_set_keyframe_recording, at most --max_keyframes 65536 nodes) and written as g2o text: VERTEX_SE2 per\n"
+           "                      keyframe, EDGE_SE2 to the previous one with the information of the rotated covariance\n");
     return argc < 2;
   }
   const std::string frames = arg(argc, argv, "--frames", "");
@@ -94,6 +143,8 @@ int main(int argc, char** argv) {
     // std::sort order inside a voxel - together what an Ubuntu 18.04 build of the reference does where its sources leave the choice to a library
     dev->check(cfear_tune(dev->ctx(), CFEAR_TUNE_NN_TIE_RULE, atoi(arg(argc, argv, "--nn-tie", "0"))), "cfear_tune");
     if (!atoi(arg(argc, argv, "--replay", "0"))) dev->check(cfear_tune(dev->ctx(), CFEAR_TUNE_VOXEL_ORDER, atoi(arg(argc, argv, "--voxel-order", "0"))), "cfear_tune");
+    if (!atoi(arg(argc, argv, "--replay", "0")) && arg(argc, argv, "--store_graph", "")[0])
+      throw std::runtime_error("--store_graph records the graph of the batched route: it needs --replay 1 (the per-sweep route builds its graph on the host)");
     if (atoi(arg(argc, argv, "--replay", "0"))) {
       if (rad_par.dataset != "oxford")
         throw std::runtime_error("--replay 1 runs the Oxford route; use the per-sweep route for the other datasets");
@@ -123,6 +174,10 @@ int main(int argc, char** argv) {
         fo.soft_constraint = par.soft_constraint ? 1 : 0; fo.use_guess = par.use_guess ? 1 : 0;
         dev->check(cfear_odometry_set_fuser_options(dev->ctx(), odo, &fo, 1), "cfear_odometry_set_fuser_options");
       }
+      const std::string graph_file = arg(argc, argv, "--store_graph", "");
+      if (!graph_file.empty())
+        dev->check(cfear_odometry_set_keyframe_recording(dev->ctx(), odo, CFEAR_KF_NODES, atoi(arg(argc, argv, "--max_keyframes", "65536")), 0),
+                   "cfear_odometry_set_keyframe_recording");
       const int piece = 256;
       const size_t sweep = (size_t)A * R;
       void* pinned = nullptr;
@@ -158,6 +213,15 @@ int main(int argc, char** argv) {
         std::cout << "Frame: " << n << ", avg: " << n / tot << " Hz (device part alone: " << n / t_dev << " Hz)" << std::endl;  // :125
       }
       std::cout << "frames " << n << std::endl;
+      if (!graph_file.empty()) {
+        int nk = 0, dropped = 0;
+        dev->check(cfear_odometry_keyframe_nodes(dev->ctx(), odo, 0, 0, nullptr, 0, &nk), "cfear_odometry_keyframe_nodes");
+        std::vector<cfear_keyframe_node> nodes((size_t)nk);
+        dev->check(cfear_odometry_keyframe_nodes(dev->ctx(), odo, 0, 0, nodes.data(), nk, &nk), "cfear_odometry_keyframe_nodes");
+        dev->check(cfear_odometry_keyframe_counts(dev->ctx(), odo, nullptr, &dropped), "cfear_odometry_keyframe_counts");
+        write_g2o(graph_file, nodes);
+        std::cout << "keyframes " << nk << ", dropped " << dropped << " -> " << graph_file << std::endl;
+      }
       cfear_host_free(dev->ctx(), pinned);
       cfear_odometry_destroy(dev->ctx(), odo);
       return 0;

@@ -142,7 +142,61 @@ def drift_dict(row):
                           "segments": [int(v) for v in row["segments_by_length"]]}}
 
 
-def replay_grid(frames, rows, A=None, R=None, gt=None, device=0, piece=256, context_params=None, options=None, drift_on="host"):
+G2O_INFO = (0, 1, 5)  # rows / columns of the 6x6 information (x, y, z, roll, pitch, yaw) a planar EDGE_SE2 carries: x, y, yaw
+
+
+def write_g2o(path, nodes):
+    """The keyframe graph of one sequence (capi.Odometry.keyframes: KEYFRAME_NODE_DTYPE) as g2o text: `VERTEX_SE2 index x y theta` per
+    node and, for every node with a previous one, `EDGE_SE2 index prev dx dy dtheta i11 i12 i13 i22 i23 i33` - the constraint AddToGraph
+    stores (odometrykeyframefuser.cpp:435-443: from the new keyframe to the previous one) with the upper triangle of the information's
+    (x, y, yaw) block. Floats are written with repr: read_g2o gives back the same bits. Pure Python (no device)."""
+    with open(path, "w") as f:
+        f.write(g2o_text(nodes))
+
+
+def g2o_text(nodes):
+    lines = []
+    for nd in nodes:
+        lines.append("VERTEX_SE2 %d %s" % (int(nd["index"]), " ".join(repr(float(v)) for v in nd["pose"])))
+    for nd in nodes:
+        if int(nd["prev"]) < 0:
+            continue
+        info = np.asarray(nd["information"]).reshape(6, 6)
+        tri = [info[G2O_INFO[i], G2O_INFO[j]] for i in range(3) for j in range(i, 3)]
+        lines.append("EDGE_SE2 %d %d %s" % (int(nd["index"]), int(nd["prev"]), " ".join(repr(float(v)) for v in list(nd["t_be"]) + tri)))
+    return "".join(l + "\n" for l in lines)
+
+
+def read_g2o(path):
+    """write_g2o's text -> nodes (KEYFRAME_NODE_DTYPE) in file order: index, pose, prev (-1 without an edge), t_be and the (x, y, yaw)
+    block of the information, both triangles; what the text does not carry (sweep, n_cells, motion, the other information entries) is 0."""
+    verts, edges = [], {}
+    with open(path) as f:
+        for line in f:
+            w = line.split()
+            if not w:
+                continue
+            if w[0] == "VERTEX_SE2":
+                verts.append((int(w[1]), [float(v) for v in w[2:5]]))
+            elif w[0] == "EDGE_SE2":
+                edges[int(w[1])] = (int(w[2]), [float(v) for v in w[3:12]])
+    nodes = np.zeros(len(verts), dtype=capi.KEYFRAME_NODE_DTYPE)
+    for k, (idx, pose) in enumerate(verts):
+        nodes[k]["index"], nodes[k]["pose"], nodes[k]["prev"] = idx, pose, -1
+        if idx in edges:
+            prev, v = edges[idx]
+            nodes[k]["prev"], nodes[k]["t_be"] = prev, v[:3]
+            tri = iter(v[3:])
+            for i in range(3):
+                for j in range(i, 3):
+                    x = next(tri)
+                    nodes[k]["information"][G2O_INFO[i], G2O_INFO[j]] = x
+                    nodes[k]["information"][G2O_INFO[j], G2O_INFO[i]] = x
+    return nodes
+
+
+def replay_grid(frames, rows, A=None, R=None, gt=None, device=0, piece=256, context_params=None, options=None, drift_on="host", keyframes=None,
+                max_keyframes=None, max_cells=None):
     """One recording under len(rows) parameter sets in one batched odometry object: frames uint8 [n, A, R], rows a list of capi.Params that
     agree in the object-wide fields (param_grid of one base does; k_strongest and submap_scan_size may be axes: the context then runs with
     the largest of each, grid_context_params, unless context_params says otherwise; so may cost: rows that differ from the context in cost
@@ -151,9 +205,16 @@ def replay_grid(frames, rows, A=None, R=None, gt=None, device=0, piece=256, cont
     (Odometry.set_sequence_detectors): the sweep is staged and its prefix sums built once, every distinct detector decided once. options: a capi.FuserOptions for every row or a list of one per row (fuser_grid builds both
     lists); None: the fuser's defaults. -> dict(poses [n, len(rows), 3], records, drift: per row KITTI drift against gt ([n, 4, 4]
     poses) or None). drift_on: "host" - kitti.drift row by row; "device" - all rows in one cfear_drift_host call against a plan of
-    gt[:n] (capi.DriftPlan), each row's dict then also holds the per-length table as kitti.drift_by_length returns it."""
+    gt[:n] (capi.DriftPlan), each row's dict then also holds the per-length table as kitti.drift_by_length returns it.
+    keyframes: None, "nodes" or "cells" - record every row's keyframe graph on the device (Odometry.record_keyframes; max_keyframes per row,
+    default n: every sweep may fuse; max_cells per row, default 256 * n - 18 KB per sweep and row; a scan of the reference's presets has 150-400
+    cells and about every second sweep fuses: size it yourself for a grid of many rows or dense scans, `keyframes_dropped` says when it was too small) and add `keyframes`: a list of
+    per-row node arrays (KEYFRAME_NODE_DTYPE), `keyframes_dropped` [rows] and, with "cells", `keyframe_cells`: per row a list of cell
+    arrays (KEYFRAME_CELL_DTYPE), one per node."""
     if drift_on not in ("host", "device"):
         raise ValueError("replay_grid: drift_on is 'host' or 'device'")
+    if keyframes not in (None, "nodes", "cells"):
+        raise ValueError("replay_grid: keyframes is None, 'nodes' or 'cells'")
     frames = np.ascontiguousarray(frames, dtype=np.uint8)
     n, A, R = frames.shape
     rows = list(rows)
@@ -177,9 +238,17 @@ def replay_grid(frames, rows, A=None, R=None, gt=None, device=0, piece=256, cont
             if not isinstance(opts, capi.FuserOptions) and len(opts) != len(rows):
                 raise ValueError("replay_grid: %d option sets for %d rows" % (len(opts), len(rows)))
             odo.set_fuser_options(opts)
+        if keyframes is not None:
+            odo.record_keyframes(capi.KF_NODES | (capi.KF_CELLS if keyframes == "cells" else 0), max_keyframes if max_keyframes is not None else n,
+                                 max_cells if max_cells is not None else 256 * n)
         recs = [odo.replay_host(frames[t0:t0 + piece, None]) for t0 in range(0, n, piece)]
         rec = np.concatenate(recs, axis=0)
         poses = np.array(rec["pose"])
+        graph = None
+        if keyframes is not None:
+            graph = {"keyframes": [odo.keyframes(q) for q in range(len(rows))], "keyframes_dropped": odo.keyframe_counts()[1]}
+            if keyframes == "cells":
+                graph["keyframe_cells"] = [[odo.keyframe_cells(q, i) for i in range(len(nodes))] for q, nodes in enumerate(graph["keyframes"])]
         scored = None
         if gt is not None and drift_on == "device":
             plan = ctx.drift_plan(np.asarray(gt)[:n])
@@ -196,7 +265,10 @@ def replay_grid(frames, rows, A=None, R=None, gt=None, device=0, piece=256, cont
         drift = [drift_dict(r) for r in scored]
     elif gt is not None:
         drift = [kitti.drift(np.asarray(gt)[:n], kitti.poses_from_xyt(poses[:, q])) for q in range(len(rows))]
-    return {"poses": poses, "records": rec, "drift": drift}
+    out = {"poses": poses, "records": rec, "drift": drift}
+    if graph is not None:
+        out.update(graph)
+    return out
 
 
 def sweeps(args):
@@ -237,6 +309,9 @@ def main(argv=None):
     ap.add_argument("--registered_min_keyframe_dist", type=float, default=1.5)
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--piece", type=int, default=256, help="sweeps handed to one cfear_odometry_replay_host call (pinned staging buffer)")
+    ap.add_argument("--store_graph", default=None, metavar="PATH",
+                    help="record the keyframe graph on the device (offline_odometry --store_graph) and write it to PATH as g2o text (write_g2o)")
+    ap.add_argument("--max_keyframes", type=int, default=65536, help="with --store_graph: nodes the log holds (later keyframes are dropped and reported)")
     ap.add_argument("--trace", action="store_true",
                     help="keep per-sweep poses, Register summaries (outer / inner iteration counts, residuals), keyframe and cell counts in the result")
     args = ap.parse_args(argv)
@@ -283,6 +358,8 @@ def main(argv=None):
                                     compensate=0 if args.disable_compensate else 1, min_keyframe_dist=args.registered_min_keyframe_dist)
             ctx = capi.Context(p, img.shape[0], img.shape[1], device=args.device)
             odo = ctx.odometry(1)
+            if args.store_graph:
+                odo.record_keyframes(capi.KF_NODES, args.max_keyframes, 0)
             buf = ctx.pinned((max(1, args.piece), 1, img.shape[0], img.shape[1]))
         buf[fill, 0] = img
         fill += 1
@@ -308,6 +385,11 @@ def main(argv=None):
         m = min(len(gts), len(est_T))
         kitti.write_kitti(os.path.join(gdir, "gt_00.txt"), gts[:m])
         out["drift"] = kitti.drift(np.array(gts[:m]), est_T[:m])
+    if args.store_graph:
+        nodes = odo.keyframes(0)
+        write_g2o(args.store_graph, nodes)
+        out["keyframes"] = int(len(nodes))
+        out["keyframes_dropped"] = int(odo.keyframe_counts()[1][0])
     print(json.dumps(out))
     if args.trace:
         out["poses"] = np.array(est)

@@ -534,7 +534,9 @@ int cfear_odometry_fuser_options(cfear_ctx* ctx, cfear_odometry* odo, int sequen
  * holds? Synchronises the context stream; returns CFEAR_OK or CFEAR_ERR_CAPACITY (with the message the reading calls give). For callers of the
  * asynchronous cfear_odometry_replay_device, which read their records on the device and never pass through poses / summary / replay_host.
  * per_sequence (optional, n_sequences words): which sequences - bit 0 = a scan of that sequence lost cells, bit 1 = a cloud of it lost points;
- * the others' results are untouched (the condition is sticky until cfear_odometry_reset, like the return code). */
+ * the others' results are untouched (the condition is sticky until cfear_odometry_reset, like the return code). Bit 2 = the sequence's
+ * keyframe log is full (cfear_odometry_set_keyframe_recording): keyframes were dropped, the odometry itself is untouched and the return
+ * code stays CFEAR_OK. Switching the recording off clears the bit; it cannot be set while recording is off. */
 int cfear_odometry_status(cfear_ctx* ctx, cfear_odometry* odo, int32_t* per_sequence);
 /* Last Register() summary / cell count / keyframe count of one sequence (debug + parity tests). */
 int cfear_odometry_summary(cfear_ctx* ctx, cfear_odometry* odo, int sequence, cfear_reg_summary* summary,
@@ -577,6 +579,64 @@ int cfear_odometry_replay_device_cov(cfear_ctx* ctx, cfear_odometry* odo, const 
 /* Page-locked host memory for the sweeps of a replay (hipHostMalloc / hipHostFree). */
 int cfear_host_alloc(cfear_ctx* ctx, size_t bytes, void** out);
 void cfear_host_free(cfear_ctx* ctx, void* p);
+
+/* ---- The keyframe graph of the batched routes: what OdometryKeyframeFuser keeps per KEYFRAME. processFrame ends a fused sweep with
+ * scan_ = RadarScan(Tcurrent, TprevMot, cloud_peaks, cloud, Pcurrent, t) and AddToGraph(keyframes_, scan_, cov_current)
+ * (odometrykeyframefuser.cpp:171-176, 234-248, 428-445): a node (RadarScan, types.h:93-143) with its oriented surface points and one
+ * odometry Constraint3d to the previous keyframe (types.h:155-190) whose information matrix is the inverse of the covariance rotated
+ * into the new keyframe's frame; offline_odometry --store_graph hands the result to the SLAM system downstream. With recording on, a
+ * stage of its own behind the registration stage (and the cost sampling) appends the node - and the scan's cells - of every sequence
+ * that fused to that sequence's log on the device: no host round trip per sweep, no change to any other kernel. cloud_nopeaks_ /
+ * cloud_peaks_ are not recorded (the k-strongest routes never write the compensated cloud), nor Tgt / the stamp (`sweep` stands in). */
+typedef struct cfear_keyframe_node {
+  int32_t index;          /* RadarScan::idx_: 0, 1, 2 ... per sequence since cfear_odometry_create / cfear_odometry_reset */
+  int32_t sweep;          /* the sweep of the sequence that fused (0-based since create / reset): the stamp's stand-in */
+  int32_t n_cells;        /* oriented surface points of the scan (the sweep record's n_cells) */
+  int32_t prev;           /* id_end of the odometry constraint: index - 1, or -1 for the first keyframe */
+  double pose[3];         /* T (x, y, theta): the sweep record's pose, bit for bit */
+  double motion[3];       /* motion_ = TprevMot, what the sweep was compensated with; (0, 0, 0) for the first keyframe (:172) */
+  double t_be[3];         /* Constraint3d::t_be = T^-1 * T_prev as (x, y, theta) (:436); zeros when prev < 0 */
+  double information[36]; /* Constraint3d::information, row-major over (x, y, z, roll, pitch, yaw) (:437-440); zeros when prev < 0. Where the sweep's
+                           * cov_current cannot be inverted (singular or non-finite) the entries are inf / NaN, as Eigen's inverse() leaves them in the
+                           * reference: the node is recorded all the same (cfear_keyframe_constraint on the host refuses the same input) */
+} cfear_keyframe_node;    /* 376 bytes */
+/* One oriented surface point of a recorded keyframe: exactly what the registration reads of a cell (and what cfear_scan_from_cells
+ * reads of a cfear_cell) - a scan rebuilt from these is the scan the fuser registered against. */
+typedef struct cfear_keyframe_cell {
+  double mean[2], normal[2], cov[3], scale;
+  int32_t nsamples, pad_;
+} cfear_keyframe_cell;    /* 72 bytes */
+#define CFEAR_KF_NODES 1
+#define CFEAR_KF_CELLS 2
+/* The rule of AddToGraph :435-440, host only (no context, no device; the recorder runs the same function): from = the new keyframe's
+ * pose, to = the previous one's, cov6 = cov_current of the sweep that fused -> t_be = Tfrom^-1 * Tto as (x, y, theta) and information =
+ * C^-1 with C = cov6 whose leading 3x3 block is turned by the rotation of Tfrom^-1 (only that block: the (0,5) / (5,0) terms stay, as in
+ * the reference). CFEAR_ERR_INVALID for a null pointer, a non-finite input or a singular C. */
+int cfear_keyframe_constraint(const double from_xyt[3], const double to_xyt[3], const double cov6[36], double t_be_xyt[3], double information[36]);
+/* what: 0 = off (releases the log; allowed at any time), CFEAR_KF_NODES, or CFEAR_KF_NODES | CFEAR_KF_CELLS. Capacities per sequence:
+ * max_keyframes nodes, max_cells cells summed over its keyframes (ignored without CFEAR_KF_CELLS). Switching on: only on an object that
+ * has processed no sweep since cfear_odometry_create / cfear_odometry_reset (CFEAR_ERR_INVALID otherwise); cfear_odometry_reset empties
+ * the log and keeps the setting. While on, every route of the object records (cfear_odometry_step_*, both replay routes - which then
+ * run two launches per sweep, not the persistent kernel -, per-sequence parameters / sources / shapes / detectors / fuser options,
+ * cost sampling, ODOMETRY_OVERLAP). A keyframe that does not fit - its node or its cells - is dropped with every later keyframe of
+ * that sequence (what is recorded is a gap-free prefix), counted in `dropped`, and sets bit 2 of that sequence's word in
+ * cfear_odometry_status; it is not an error of the reading calls. Synchronises the context stream. */
+int cfear_odometry_set_keyframe_recording(cfear_ctx* ctx, cfear_odometry* odo, int what, int max_keyframes, int max_cells);
+/* Per sequence (n_sequences words each, either may be NULL): keyframes in the log, keyframes dropped. Synchronises the context stream,
+ * like cfear_odometry_poses (so do the three calls below). CFEAR_ERR_INVALID while recording is off. */
+int cfear_odometry_keyframe_counts(cfear_ctx* ctx, cfear_odometry* odo, int32_t* recorded, int32_t* dropped);
+/* Nodes first, first + 1 ... of one sequence: at most `capacity` are written; *n = the nodes the sequence has recorded in all. */
+int cfear_odometry_keyframe_nodes(cfear_ctx* ctx, cfear_odometry* odo, int sequence, int first, cfear_keyframe_node* nodes, int capacity, int* n);
+/* The cells of keyframe `index` of one sequence, in the scan's order: at most `capacity` are written; *n = the node's n_cells.
+ * CFEAR_ERR_INVALID for an index outside the recorded prefix or a log without CFEAR_KF_CELLS. */
+int cfear_odometry_keyframe_cells(cfear_ctx* ctx, cfear_odometry* odo, int sequence, int index, cfear_keyframe_cell* cells, int capacity, int* n);
+/* m per-call scans rebuilt from recorded keyframes of one sequence, device to device in one launch (a workgroup per scan): float means,
+ * the registration views, the search grid and - under cfear_tune NN_TIE_RULE = 2 - the kd-tree, ready for cfear_register /
+ * cfear_get_cost. Their cfear_cell records (cfear_scan_download_cells) carry the recorded fields bit for bit, valid = 1, orth =
+ * (-normal_y, normal_x), lambda_min / lambda_max = the closed-form eigenvalues of cov, and BOTH INTENSITIES 0 (the log does not keep
+ * them). Memory from the context's pool; release each with cfear_scan_release. CFEAR_ERR_INVALID for an index outside the recorded
+ * prefix or a log without CFEAR_KF_CELLS, CFEAR_ERR_EMPTY for a keyframe without cells; nothing is created then. Synchronous. */
+int cfear_odometry_keyframe_scans(cfear_ctx* ctx, cfear_odometry* odo, int sequence, const int32_t* indices, int m, cfear_scan** scans);
 
 /* ---- KITTI drift of a batch's trajectories on the device: the metric of include/cfear_hip/kitti_metric.hpp (kitti_drift,
  * kitti_drift_by_length; what the reference's evaluation worker computes per job, launch/oxford/eval/utils/worker:94-98) for every
