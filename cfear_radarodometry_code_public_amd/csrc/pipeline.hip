@@ -10,6 +10,9 @@
 //                          unit so that the serial Levenberg-Marquardt controllers of different sequences overlap):
 //                          association, robust normal equations, LM, outer loop, keyframe logic
 // Per-call entry points (clouds, scans, Register, GetCost, cost-sampling covariance) use the same device code.
+// The object itself (struct cfear_odometry) is odometry_obj.h's; its per-sequence configuration - the setters and getters of rows, source
+// map, shapes, detectors and fuser options, the device table (seq_table_upload) and odo_seq_sync's re-check - lives in odometry_seq.hip
+// over seq_config.h. This file reads the configuration through o->cfg (effective(), sources(), other_cost()) and never writes it.
 #include <math.h>
 #include <cmath>
 #include <stdlib.h>
@@ -17,11 +20,8 @@
 #include <algorithm>
 #include <new>
 
-#include "common.h"
-#include "odometry_step_dev.h"
+#include "odometry_obj.h"
 #include "cov_sampling_dev.h"
-#include "surface_dev.h"
-#include "seq_groups.h"
 #include "keyframe_dev.h"
 
 namespace {
@@ -486,122 +486,12 @@ static int check_tie_rule_scans(cfear_ctx* ctx, cfear_scan* const* scans, int n,
     }
   return CFEAR_OK;
 }
-struct cfear_odometry {
-  int B = 0, nslots = 0, cap_points = 0, cap_cells = 0, pair_cap = 0;
-  DevBuf<int> d_order; DevBuf<unsigned> d_work;  // registration workgroups longest first (cfear_tune REGISTRATION_ORDER): see order_kernel
-  bool order_ready = false;  // d_work holds the keys of a registration launch
-  bool with_kd = false;  // the scans carry FLANN kd-tree arrays (cfear_tune NN_TIE_RULE = 2 at creation)
-  int large_kernel = 0, n_cus = 256;  // cfear_tune LARGE_SUBMAP_KERNEL at creation; compute units of the device
-  DevBuf<int> d_flags;  // bit 0: a scan had more cells than cap_cells, bit 1: a cloud had more points than cap_points (only allocated when either can happen)
-  DevBuf<unsigned char> d_scans;       // B * nslots flat scan blocks
-  size_t scan_stride = 0;              // bytes between consecutive scan slots of d_scans
-  DevBuf<unsigned char> d_scratch;     // B scratch blocks
-  DevBuf<BlockScratch> d_scratch_hdr;
-  DevBuf<SeqState> d_states;
-  DevBuf<double> d_cov_work;
-  DevBuf<cfear_reg_summary> d_summaries;
-  DevBuf<double> d_poses_out;
-  DevBuf<uint32_t> d_slots[2];  // filter output, double-buffered: the filter runs one sweep ahead
-  DevBuf<uint8_t> d_polar;  // staging for step_host
-  // filter_type CA-CFAR (radar_driver.cpp:52-56): the filter's output is a cloud per sequence instead of A * k slots
-  int filter = CFEAR_FILTER_KSTRONG;
-  DevBuf<float> d_cloud;         // [B][cap_points][3]
-  DevBuf<int> d_cloud_n;         // [B] detections per sequence (may exceed cap_points: the cloud keeps the first cap_points)
-  DevBuf<int> d_cfar_rows;       // row counts / row bases / hit masks of one sweep (cfear_cfar_scratch_ints)
-  DevBuf<float> rp_cloud[2];     // replay: clouds of a chunk of sweeps, double-buffered like rp_slots
-  DevBuf<int> rp_cloud_n[2];
-  DevBuf<int> rp_cfar_rows;      // ... of a chunk (the replay stream runs one filter at a time)
-  // cfear_odometry_replay_host: chunks of sweeps are copied and filtered on a stream of their own (rp_stream), two chunks
-  // in flight (staging + slots double-buffered), while the context stream runs features -> registration sweep after sweep
-  hipStream_t rp_stream = nullptr;
-  DevBuf<uint8_t> rp_polar[2];
-  DevBuf<uint32_t> rp_slots[2];
-  hipEvent_t rp_filt[2] = {nullptr, nullptr}, rp_used[2] = {nullptr, nullptr};  // chunk filtered / chunk consumed by the odometry kernels
-  hipEvent_t rp_in = nullptr;  // device-resident frames ready on the context stream
-  bool rp_used_pending[2] = {false, false};
-  bool rp_ready = false;       // stream + events exist
-  int rp_chunk = 0;            // sweeps per chunk the slot buffers are sized for
-  int rp_polar_chunk = 0;      // ... and the staging buffers (allocated on the first replay from host memory only)
-  DevBuf<cfear_sweep_record> d_records;
-  DevBuf<long long> d_phase_times;  // optional [B][32] (cfear_odometry_phase_times)
-  int phase_detail = 1;
-  bool wg_only = false;  // the table only receives the workgroups' start / end clocks, from the production kernels
-  // The filter of a sweep needs nothing but its input, and it is bound by HBM while features / registration are chains
-  // of short dependent phases. With overlap on it runs on a stream of its own (sf) into the slot buffer of its parity;
-  // features / registration follow on a second stream (so) once their slot buffer is written (ev_filt) and release it
-  // when features has consumed it (ev_free). The host issues step t+1 while so still works on step t, so filter(t+1)
-  // can start on compute units that the last rounds of registration(t) leave idle. The context stream joins in the
-  // reading calls (odo_join). With overlap off (the default, see DESIGN.md: the three kernels want the same registers and
-  // LDS of a compute unit, so running them side by side stretches all of them) they run in turn on the context stream.
-  int overlap = 0;  // 0: the three kernels in turn on the context stream; n >= 1: filter stream + n odometry streams (below)
-  long long step_no = 0;
-  // overlap = n: the filter runs on a LOW-priority stream of its own (sf) into the slot buffer of its parity, one sweep ahead;
-  // the sequences are cut into n contiguous ranges whose features / registration kernels run on n HIGH-priority streams
-  // (so[i]). Different ranges are at different points of their features -> registration chain, so the ragged last round of one
-  // kernel is filled with workgroups of another (a features workgroup and a registration workgroup fit a compute unit
-  // together), and the filter takes what is left.
-  hipStream_t sf = nullptr;
-  std::vector<hipStream_t> so;
-  hipEvent_t ev_in = nullptr, ev_copied = nullptr;
-  hipEvent_t ev_filt[2] = {nullptr, nullptr};
-  std::vector<hipEvent_t> ev_free[2], ev_done;  // per odometry stream
-  bool filt_pending[2] = {false, false};  // ev_filt / ev_free have been recorded at least once
-  // profiling: timing events taken from a pool that is created up front (and grown in blocks)
-  bool profile = false;
-  std::vector<hipEvent_t> pool;
-  size_t pool_used = 0;
-  std::vector<hipEvent_t> filter_events;  // 2 per profiled filter launch (borrowed from the pool)
-  std::vector<hipEvent_t> stage_events;   // 3 per profiled step: before features, between, after registration
-  // estimate_cov_by_sampling (cfear_odometry_set_cov_sampling): the sampling stage runs after every registration while cov_on
-  bool cov_on = false;
-  int cov_m = 0;                          // samples per sweep (samples_per_axis^3)
-  double cov_scaler = 4.0;
-  DevBuf<CovSampleCtx> d_cov_ctx;         // [B] what each registration used (register_step_body)
-  DevBuf<double> d_cov_design;            // [10][m] pseudo-inverse of the sample design, then [m][3] sample offsets
-  DevBuf<double> d_cov_costs;             // [B][m] sampled costs of the last sweep
-  DevBuf<double> d_cov_seq;               // cfear_odometry_replay_host_cov: cov_current of every sweep ([n][B][36])
-  // cost surfaces (cfear_odometry_set_surface_recording / cfear_odometry_surface): the registration records what it used in d_cov_ctx
-  // (as for the sampling stage, which does not run unless cov_on)
-  bool surf_on = false;
-  bool surf_ready = false;  // d_cov_ctx holds the last step's registrations (a step ran with recording since the last reset / replay)
-  DevBuf<SurfHdr> d_surf_hdr;        // [B]
-  DevBuf<double> d_surf_coords;      // [B][2][pixels]
-  DevBuf<int> d_surf_nxy;            // [B][2]
-  // per-sequence parameters / shared input sweeps (cfear_odometry_set_sequence_params / _set_sequence_sources)
-  std::vector<cfear_params> seq_rows;  // [B] the caller's table; empty: every sequence runs with the context's parameters
-  std::vector<int32_t> seq_src;        // [B] the sweep each sequence reads; empty: sweep q for sequence q
-  int n_sources = 0;                   // sweeps per step with a source map (0: B)
-  std::vector<cfear_fuser_options> fuser_opts;  // [B] cfear_odometry_set_fuser_options; empty: the defaults (no prior, constant-velocity guess)
-  DevBuf<SeqParams> d_seq;             // [B] what the kernels read (OdoParams::seq); exists while any of the above does
-  cfear_params seq_par_seen;           // the context's parameters d_seq was built and the rows were checked against
-  int seq_zmin = -1;                   // the filter's threshold: the smallest z_min of the rows (-1: the context's)
-  // per-sequence cost and submap size (cfear_odometry_set_sequence_shapes): the registration stage runs as one launch per group
-  std::vector<cfear_seq_shape> seq_shapes;  // [B]; empty: every sequence runs with the context's cost and submap_scan_size
-  cfear_seq_groups groups;             // the launch groups of seq_shapes (seq_groups.h), built with the device table
-  DevBuf<int> d_group_list;            // [B] groups.list: what OdoParams::order points into until a sweep's work keys exist
-  DevBuf<int> d_seq_group;             // [B] groups.group (order_groups_kernel)
-  // per-sequence CA-CFAR detectors over shared sweeps (cfear_odometry_set_sequence_detectors): the filter stage runs cfear_launch_cfar_grid. The
-  // clouds stay one per sequence, so seq_src stays empty (SeqParams::source is the k-strongest routes'); n_sources is the grid's with a source map
-  std::vector<cfear_seq_detector> seq_dets;  // [B]; empty: every sequence runs the context's detector
-  cfear_cfar_grid* det_grid = nullptr;       // the plan and device tables of seq_dets and their source map
-  bool det_map = false;                      // the detectors came with a source map
-  long long sweeps = 0;                // sweeps processed since cfear_odometry_create / cfear_odometry_reset
-  // the keyframe graph (cfear_odometry_set_keyframe_recording): while kf_what != 0 the recorder stage of keyframes.hip runs behind every
-  // registration stage and appends the keyframes of the sequences that fused to these
-  int kf_what = 0, kf_max = 0, kf_max_cells = 0;
-  DevBuf<cfear_keyframe_node> d_kf_nodes;  // [B][kf_max]
-  DevBuf<cfear_keyframe_cell> d_kf_cells;  // [B][kf_max_cells] (CFEAR_KF_CELLS)
-  DevBuf<int> d_kf_off;                    // [B][kf_max] a node's first cell in its sequence's cells
-  DevBuf<int> d_kf_counts;                 // [B][4] nodes recorded, keyframes dropped, cells used, 0
-  DevBuf<double> d_kf_tmot;                // [B][6] the recorder's copy of SeqState::Tmot (KfLog::tmot)
-};
 static KfLog odo_kf_log(const cfear_odometry* o) {
   KfLog L;
   L.what = o->kf_what; L.max_kf = o->kf_max; L.max_cells = o->kf_max_cells; L.pad_ = 0;
   L.nodes = o->d_kf_nodes; L.cells = o->d_kf_cells; L.cell_off = o->d_kf_off; L.counts = o->d_kf_counts; L.tmot = o->d_kf_tmot;
   return L;
 }
-static int odo_sources(const cfear_odometry* o) { return o->n_sources > 0 ? o->n_sources : o->B; }
 // a timing event from the pool, recorded on `st`
 static int odo_grow_pool(cfear_ctx* ctx, cfear_odometry* o) {
   for (int i = 0; i < 1024; i++) {
@@ -619,16 +509,6 @@ static int odo_timed_event(cfear_ctx* ctx, cfear_odometry* o, std::vector<hipEve
   return CFEAR_OK;
 }
 static int odo_capacity_check(cfear_ctx* ctx, cfear_odometry* o, const char* what);
-// make everything the internal streams have been given so far visible to the context stream
-static int odo_join(cfear_ctx* ctx, cfear_odometry* o) {
-  if (o->overlap && o->step_no > 0) {
-    for (size_t i = 0; i < o->so.size(); i++) {  // an odometry stream waits for every filter it consumes: joining them joins sf
-      CFEAR_HIP_CHECK(ctx, hipEventRecord(o->ev_done[i], o->so[i]));
-      CFEAR_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream, o->ev_done[i], 0));
-    }
-  }
-  return CFEAR_OK;
-}
 
 // has the object the shape the context's parameters ask for? (k_strongest / submap_scan_size / the filter cannot change under an object)
 static int odo_shape_check(cfear_ctx* ctx, const cfear_odometry* o, const char* what);
@@ -657,133 +537,6 @@ static OdoParams odo_params(const cfear_ctx* ctx, const cfear_odometry* o) {
   return OP;
 }
 
-// ---- per-sequence parameters (the grids of utils/worker:26-99 as sequences of one object) ------------------------------------------
-static SeqParams seq_row_of(const cfear_params& p, int source, int cost, int submap) {
-  SeqParams r;
-  memset(&r, 0, sizeof(r));
-  r.loss_limit = p.loss_limit; r.covar_scale = p.covar_scale; r.regularization = p.regularization;
-  r.min_keyframe_dist = p.min_keyframe_dist; r.min_keyframe_rot_deg = p.min_keyframe_rot_deg;
-  r.radius = (float)p.res; r.weight_intensity = p.weight_intensity; r.loss = p.loss; r.weight_opt = p.weight_opt;
-  r.max_outer = p.max_itr_association; r.min_itr = p.min_itr; r.max_inner = p.max_solver_iterations;
-  r.compensate = p.compensate; r.use_keyframe = p.use_keyframe;
-  r.z_min = (int)(uint8_t)(int)p.z_min;  // as the filter takes it (radar_filters.cpp:198, :212)
-  r.source = source;
-  r.k = p.k_strongest;
-  r.shape = seq_shape_pack(cost, submap);
-  return r;
-}
-// may the rows be the sequences of `o` under the context's parameters? The fields that size memory or select a kernel are the object's
-// shapes: [n] the cost / submap_scan_size row q must carry (cfear_odometry_set_sequence_shapes), null: the context's
-// dets: [n] the detector row q must carry on a CA-CFAR object (cfear_odometry_set_sequence_detectors), null: the context's
-static const cfear_seq_shape* odo_shapes(const cfear_odometry* o) { return o->seq_shapes.empty() ? nullptr : o->seq_shapes.data(); }
-static const cfear_seq_detector* odo_dets(const cfear_odometry* o) { return o->seq_dets.empty() ? nullptr : o->seq_dets.data(); }
-static int seq_rows_check(cfear_ctx* ctx, const cfear_odometry* o, const cfear_params* rows, int n, const char* what, const cfear_seq_shape* shapes,
-                          const cfear_seq_detector* dets) {
-  const cfear_params& c = ctx->par;
-  for (int q = 0; q < n; q++) {
-    const cfear_params& r = rows[q];
-    const int want_window = dets ? dets[q].window_size : c.cfar_window_size, want_guard = dets ? dets[q].nb_guard_cells : c.cfar_nb_guard_cells;
-    const float want_rate = dets ? dets[q].false_alarm_rate : c.cfar_false_alarm_rate, want_z = dets ? dets[q].z_min : c.z_min;
-    const int want_cost = shapes ? shapes[q].cost : c.cost, want_submap = shapes ? shapes[q].submap_scan_size : c.submap_scan_size;
-    // k_strongest: any k up to the context's K. The filter runs with K and the object is sized for it; a sequence reads the last k of the
-    // returns the filter kept of every bearing (cloud_step_block)
-    if (r.k_strongest < 1 || r.k_strongest > c.k_strongest) {
-      char msg[256];
-      snprintf(msg, sizeof(msg), "%s: row %d: k_strongest = %d must be in 1..%d, the context's k_strongest (the filter runs with it and the object's memory is sized "
-               "for it)", what, q, r.k_strongest, c.k_strongest);
-      return cfear_fail(ctx, CFEAR_ERR_INVALID, msg);
-    }
-    const char* f = nullptr;
-    if (o->filter == CFEAR_FILTER_CACFAR && r.k_strongest != c.k_strongest) f = "k_strongest (the CA-CFAR detector has no k)";
-    else if (r.cost != want_cost) f = shapes ? "cost (the sequence's shape says otherwise: cfear_odometry_set_sequence_shapes)" : "cost";
-    else if (r.submap_scan_size != want_submap) f = shapes ? "submap_scan_size (the sequence's shape says otherwise: cfear_odometry_set_sequence_shapes)" : "submap_scan_size";
-    else if (r.filter_type != c.filter_type) f = "filter_type";
-    else if (r.range_res != c.range_res) f = "range_res";
-    else if (r.min_distance != c.min_distance) f = "min_distance";
-    else if (r.downsample_factor != c.downsample_factor) f = "downsample_factor";
-    else if (r.radar_ccw != c.radar_ccw) f = "radar_ccw";
-    else if (r.assoc_radius != c.assoc_radius) f = "assoc_radius";
-    else if (r.cfar_window_size != want_window) f = dets ? "cfar_window_size (the sequence's detector says otherwise: cfear_odometry_set_sequence_detectors)" : "cfar_window_size";
-    else if (r.cfar_nb_guard_cells != want_guard) f = dets ? "cfar_nb_guard_cells (the sequence's detector says otherwise: cfear_odometry_set_sequence_detectors)" : "cfar_nb_guard_cells";
-    else if (r.cfar_false_alarm_rate != want_rate) f = dets ? "cfar_false_alarm_rate (the sequence's detector says otherwise: cfear_odometry_set_sequence_detectors)" : "cfar_false_alarm_rate";
-    else if (r.cfar_max_points != c.cfar_max_points) f = "cfar_max_points";
-    else if (r.cfar_max_distance != c.cfar_max_distance) f = "cfar_max_distance";
-    else if (o->filter == CFEAR_FILTER_CACFAR && r.z_min != want_z)
-      f = dets ? "z_min (the sequence's detector says otherwise: cfear_odometry_set_sequence_detectors)" : "z_min (the CA-CFAR detector's static threshold)";
-    if (f) {
-      char msg[640];
-      snprintf(msg, sizeof(msg), "%s: row %d differs from the context's parameters in %s, which sizes memory or selects a kernel for the whole object "
-               "(cost and submap_scan_size per sequence: cfear_odometry_set_sequence_shapes; per-sequence: z_min, k_strongest (<= the context's), res, weight_intensity, loss, loss_limit, weight_opt, covar_scale, regularization, compensate, "
-               "the keyframe rule, the iteration limits)", what, q, f);
-      return cfear_fail(ctx, CFEAR_ERR_INVALID, msg);
-    }
-    const char* bad = nullptr;  // the values cfear_set_params would refuse
-    if (!(r.res > 0.05) || !std::isfinite(r.res)) bad = "res must be finite and > 0.05";
-    else if (r.loss < 0 || r.loss > 5) bad = "unknown loss";
-    else if (r.max_itr_association < 1 || r.max_itr_association > CFEAR_MAX_OUTER) bad = "max_itr_association must be in 1..64";
-    else if (r.max_solver_iterations < 1) bad = "max_solver_iterations must be >= 1";
-    else if (r.min_itr < 0) bad = "min_itr must be >= 0";
-    else if (!std::isfinite(r.z_min) || !std::isfinite(r.loss_limit)) bad = "z_min and loss_limit must be finite";
-    if (bad) {
-      char msg[160];
-      snprintf(msg, sizeof(msg), "%s: row %d: %s", what, q, bad);
-      return cfear_fail(ctx, CFEAR_ERR_INVALID, msg);
-    }
-  }
-  return CFEAR_OK;
-}
-// (re)builds the device table from the rows (or the context's parameters), the source map and the fuser options; frees it when none is set. The context
-// stream and the object's streams are idle when this is called.
-static int seq_table_upload(cfear_ctx* ctx, cfear_odometry* o) {
-  if (o->seq_shapes.empty()) { o->groups = cfear_seq_groups(); o->d_group_list.release(); o->d_seq_group.release(); }
-  if (o->seq_rows.empty() && o->seq_src.empty() && o->fuser_opts.empty() && o->seq_shapes.empty()) {
-    o->d_seq.release(); o->seq_zmin = -1;
-    return CFEAR_OK;
-  }
-  if (!o->seq_shapes.empty()) {  // the launch groups of the registration stage and their static list (launch_register_kernel)
-    std::vector<int> cost((size_t)o->B), sub((size_t)o->B);
-    for (int q = 0; q < o->B; q++) { cost[q] = o->seq_shapes[q].cost; sub[q] = o->seq_shapes[q].submap_scan_size; }
-    cfear_seq_groups G;
-    if (!cfear_seq_groups_build(cost.data(), sub.data(), o->B, CFEAR_STEP_SMALL_SCANS, G))
-      return cfear_fail(ctx, CFEAR_ERR_INVALID, "sequence shapes: a cost or submap_scan_size that is none");  // (refused by the caller before: never reached)
-    CFEAR_TRY(o->d_group_list.ensure(ctx, (size_t)o->B, "hipMalloc sequence group list"));
-    CFEAR_TRY(o->d_seq_group.ensure(ctx, (size_t)o->B, "hipMalloc sequence group list"));
-    CFEAR_HIP_CHECK(ctx, hipMemcpy(o->d_group_list, G.list.data(), sizeof(int) * (size_t)o->B, hipMemcpyHostToDevice));
-    CFEAR_HIP_CHECK(ctx, hipMemcpy(o->d_seq_group, G.group.data(), sizeof(int) * (size_t)o->B, hipMemcpyHostToDevice));
-    o->groups = G;
-    o->order_ready = false;  // (no sweep since create / reset: nothing was recorded)
-  }
-  std::vector<SeqParams> t((size_t)o->B);
-  int zmin = 255;
-  for (int q = 0; q < o->B; q++) {
-    t[q] = seq_row_of(o->seq_rows.empty() ? ctx->par : o->seq_rows[q], o->seq_src.empty() ? q : o->seq_src[q],
-                      o->seq_shapes.empty() ? ctx->par.cost : o->seq_shapes[q].cost, o->seq_shapes.empty() ? ctx->par.submap_scan_size : o->seq_shapes[q].submap_scan_size);
-    zmin = std::min(zmin, t[q].z_min);
-    if (!o->fuser_opts.empty()) t[q].fuser = (o->fuser_opts[q].soft_constraint ? SEQ_FUSER_SOFT : 0) | (o->fuser_opts[q].use_guess ? 0 : SEQ_FUSER_NO_GUESS);
-  }
-  CFEAR_TRY(o->d_seq.ensure(ctx, t.size(), "hipMalloc sequence parameter table"));
-  CFEAR_HIP_CHECK(ctx, hipMemcpy(o->d_seq, t.data(), sizeof(SeqParams) * t.size(), hipMemcpyHostToDevice));
-  o->seq_zmin = o->seq_rows.empty() ? -1 : zmin;
-  o->seq_par_seen = ctx->par;
-  return CFEAR_OK;
-}
-// before a step / replay / surface call: cfear_set_params since the table was built? The rows are checked against the new parameters
-// (loud, never silent) and the table follows them
-static int odo_seq_sync(cfear_ctx* ctx, cfear_odometry* o, const char* what) {
-  if (!o->d_seq || memcmp(&o->seq_par_seen, &ctx->par, sizeof(cfear_params)) == 0) return CFEAR_OK;
-  if (!o->seq_rows.empty()) CFEAR_TRY(seq_rows_check(ctx, o, o->seq_rows.data(), o->B, what, odo_shapes(o), odo_dets(o)));
-  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  CFEAR_TRY(odo_join(ctx, o));
-  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  return seq_table_upload(ctx, o);
-}
-static int seq_fresh_check(cfear_ctx* ctx, const cfear_odometry* o, const char* what) {
-  if (o->sweeps == 0) return CFEAR_OK;
-  char msg[256];
-  snprintf(msg, sizeof(msg), "%s: the object has processed %lld sweeps since cfear_odometry_create / cfear_odometry_reset - keyframes built under other parameters or "
-           "from other sweeps are not a state the reference can be in; call cfear_odometry_reset first", what, o->sweeps);
-  return cfear_fail(ctx, CFEAR_ERR_INVALID, msg);
-}
 // the registration step kernel of a sweep. register_step.hip holds the production instantiations (one per cost metric, registrations of
 // up to CFEAR_STEP_SMALL_SCANS scans: a bigger LDS match array); a larger submap runs the instantiation of this file (any cost, 64 scans)
 // the registration kernel of `count` sequences that are not small (8 .. 63 keyframes), see launch_register_kernel. n_large / max_submap: what
@@ -820,7 +573,7 @@ static void launch_register_groups(const OdoParams& P_in, hipStream_t st, cfear_
   }
 }
 static void launch_register_kernel(const OdoParams& P_in, int count, hipStream_t st, cfear_odometry* o) {
-  const bool shaped = !o->seq_shapes.empty();
+  const bool shaped = !o->cfg.shapes.empty();
   if (shaped && o->groups.n_launches > 1) { launch_register_groups(P_in, st, o); return; }
   OdoParams P = P_in;
   if (o->d_order && count == o->B && P.seq0 == 0) {  // (whole-batch launches only: the sub-batches of the overlap mode keep their ranges)
@@ -898,7 +651,7 @@ static int odo_shape_check(cfear_ctx* ctx, const cfear_odometry* o, const char* 
 // the CA-CFAR stage of n_steps sweeps of every sequence (radar_driver.cpp:52-56) into clouds of o->cap_points points each, [step][sequence]: the
 // context's detector over one image per sequence, or the sequences' own over the sources they share
 static int odo_launch_cfar(cfear_ctx* ctx, cfear_odometry* o, const uint8_t* d_polar, int n_steps, float* d_xyi, int* d_counts, int* d_rows, hipStream_t st) {
-  if (o->det_grid) return cfear_launch_cfar_grid(ctx, o->det_grid, d_polar, n_steps, ctx->par.cfar_max_distance, d_xyi, o->cap_points, d_counts, d_rows, st);
+  if (o->det_grid) return cfear_launch_cfar_grid(ctx, o->det_grid.get(), d_polar, n_steps, ctx->par.cfar_max_distance, d_xyi, o->cap_points, d_counts, d_rows, st);
   return cfear_launch_cfar_batch(ctx, d_polar, n_steps * o->B, ctx->par.cfar_window_size, ctx->par.cfar_nb_guard_cells, ctx->par.cfar_false_alarm_rate,
                                  ctx->par.cfar_max_distance, d_xyi, o->cap_points, d_counts, d_rows, st);
 }
@@ -1642,8 +1395,7 @@ void cfear_odometry_destroy(cfear_ctx* ctx, cfear_odometry* o) {
   for (auto* v : {&o->ev_free[0], &o->ev_free[1], &o->ev_done}) for (hipEvent_t e : *v) if (e) (void)hipEventDestroy(e);
   if (o->sf) (void)hipStreamDestroy(o->sf);
   for (hipStream_t st : o->so) if (st) (void)hipStreamDestroy(st);
-  cfear_cfar_grid_destroy(o->det_grid);
-  delete o;  // (and with it the device buffers)
+  delete o;  // (and with it the device buffers and the detectors' grid)
 }
 
 // an empty keyframe log: no nodes, no drops, and the recorder's copy of Tmot the identity the states start with
@@ -1841,17 +1593,17 @@ static int odo_step_clouds(cfear_ctx* ctx, cfear_odometry* o, const float* d_xyi
 int cfear_odometry_step_cloud_device(cfear_ctx* ctx, cfear_odometry* o, const float* d_xyi, int capacity, const int* d_counts) {
   if (!ctx || !o || !d_xyi || !d_counts || capacity <= 0) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_step_cloud: bad argument");
   CFEAR_TRY(odo_shape_check(ctx, o, "odometry_step_cloud"));
-  if (!o->seq_src.empty())
+  if (!o->cfg.src.empty())
     return cfear_fail(ctx, CFEAR_ERR_UNSUPPORTED, "odometry_step_cloud: the object has a source map (cfear_odometry_set_sequence_sources), which the cloud route does not "
                       "read - it takes one cloud per sequence; clear the map (NULL) first");
-  if (o->det_map)
+  if (o->cfg.dets_mapped)
     return cfear_fail(ctx, CFEAR_ERR_UNSUPPORTED, "odometry_step_cloud: the object has per-sequence detectors with a source map (cfear_odometry_set_sequence_detectors), "
                       "which the cloud route does not read - it takes one cloud per sequence; clear them (NULL) first");
-  for (size_t q = 0; q < o->seq_rows.size(); q++)
-    if (o->seq_rows[q].k_strongest != ctx->par.k_strongest) {
+  for (size_t q = 0; q < o->cfg.rows.size(); q++)
+    if (o->cfg.rows[q].k_strongest != ctx->par.k_strongest) {
       char msg[256];
       snprintf(msg, sizeof(msg), "odometry_step_cloud: row %d of the object's table has k_strongest = %d, the context %d - a cloud has no slots to take the k strongest "
-               "of; the cloud route runs with rows of the context's k_strongest only", (int)q, o->seq_rows[q].k_strongest, ctx->par.k_strongest);
+               "of; the cloud route runs with rows of the context's k_strongest only", (int)q, o->cfg.rows[q].k_strongest, ctx->par.k_strongest);
       return cfear_fail(ctx, CFEAR_ERR_UNSUPPORTED, msg);
     }
   CFEAR_TRY(odo_seq_sync(ctx, o, "odometry_step_cloud"));
@@ -2052,7 +1804,7 @@ static int replay_ensure(cfear_ctx* ctx, cfear_odometry* o, int chunk, bool stag
       }
     }
     if (o->filter == CFEAR_FILTER_CACFAR)
-      CFEAR_TRY(o->rp_cfar_rows.ensure(ctx, o->det_grid ? cfear_cfar_grid_scratch_ints(ctx, o->det_grid, (size_t)chunk) : cfear_cfar_scratch_ints(ctx, (size_t)o->B * chunk),
+      CFEAR_TRY(o->rp_cfar_rows.ensure(ctx, o->det_grid ? cfear_cfar_grid_scratch_ints(ctx, o->det_grid.get(), (size_t)chunk) : cfear_cfar_scratch_ints(ctx, (size_t)o->B * chunk),
                                        "hipMalloc replay cfar rows"));
     o->rp_chunk = chunk;
   }
@@ -2258,14 +2010,13 @@ int cfear_odometry_surface(cfear_ctx* ctx, cfear_odometry* o, double res, int wi
     if (rc == CFEAR_ERR_INVALID) return cfear_fail(ctx, rc, "odometry_surface: res must be finite and > 0, width >= 0");
     if (rc != CFEAR_OK) return cfear_fail(ctx, rc, "odometry_surface: more than CFEAR_SURFACE_MAX_SIDE pixels per side");
   }
-  for (size_t q = 1; q < o->seq_shapes.size(); q++)
-    if (o->seq_shapes[q].cost != o->seq_shapes[0].cost) {
-      char msg[320];
-      snprintf(msg, sizeof(msg), "odometry_surface: the sequences' shapes differ in cost (sequence 0: %d, sequence %d: %d; cfear_odometry_set_sequence_shapes) - the "
-               "evaluation is one launch per cost metric over all problems; surfaces run under shapes of one cost (any submap_scan_size)",
-               (int)o->seq_shapes[0].cost, (int)q, (int)o->seq_shapes[q].cost);
-      return cfear_fail(ctx, CFEAR_ERR_UNSUPPORTED, msg);
-    }
+  if (const int q = o->cfg.other_cost()) {
+    char msg[320];
+    snprintf(msg, sizeof(msg), "odometry_surface: the sequences' shapes differ in cost (sequence 0: %d, sequence %d: %d; cfear_odometry_set_sequence_shapes) - the "
+             "evaluation is one launch per cost metric over all problems; surfaces run under shapes of one cost (any submap_scan_size)",
+             (int)o->cfg.shapes[0].cost, q, (int)o->cfg.shapes[(size_t)q].cost);
+    return cfear_fail(ctx, CFEAR_ERR_UNSUPPORTED, msg);
+  }
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   CFEAR_TRY(odo_seq_sync(ctx, o, "odometry_surface"));
   CFEAR_TRY(odo_join(ctx, o));
@@ -2310,217 +2061,11 @@ int cfear_odometry_surface(cfear_ctx* ctx, cfear_odometry* o, double res, int wi
   }
   if (!CFEAR_SURFACE_NAIVE || !o->surf_ready) {
     RegParams eval_rp = OP.rp;
-    if (!o->seq_shapes.empty()) eval_rp.cost = o->seq_shapes[0].cost;  // (one cost: checked above)
+    eval_rp.cost = o->cfg.effective(0, ctx->par).par.cost;  // (one cost: checked above)
     launch_surface_eval(eval_rp, B, o->d_surf_hdr, o->d_surf_coords, o->d_surf_nxy, pixels, d_surface, ctx->stream);
     CFEAR_HIP_CHECK(ctx, hipGetLastError());
   }
   return cap_rc;
-}
-
-// ---- per-sequence parameters and shared input sweeps (odometrykeyframefuser.h:72-114; utils/worker:26-99) -----------------------------
-int cfear_odometry_set_sequence_params(cfear_ctx* ctx, cfear_odometry* o, const cfear_params* rows, int n_rows) {
-  if (!ctx || !o || (rows && n_rows != o->B)) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_set_sequence_params: bad argument (n_rows must be the object's n_sequences)");
-  CFEAR_TRY(seq_fresh_check(ctx, o, "odometry_set_sequence_params"));
-  if (rows) CFEAR_TRY(seq_rows_check(ctx, o, rows, n_rows, "odometry_set_sequence_params", odo_shapes(o), odo_dets(o)));
-  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  CFEAR_TRY(odo_join(ctx, o));
-  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  std::vector<cfear_params> keep;
-  if (rows) keep.assign(rows, rows + n_rows);
-  o->seq_rows.swap(keep);
-  const int rc = seq_table_upload(ctx, o);
-  if (rc != CFEAR_OK) { o->seq_rows.swap(keep); (void)seq_table_upload(ctx, o); }  // (the previous table)
-  return rc;
-}
-
-int cfear_odometry_sequence_params(cfear_ctx* ctx, cfear_odometry* o, int sequence, cfear_params* out) {
-  if (!ctx || !o || !out || sequence < 0 || sequence >= o->B) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_sequence_params: bad argument");
-  *out = o->seq_rows.empty() ? ctx->par : o->seq_rows[(size_t)sequence];
-  if (!o->seq_shapes.empty()) { out->cost = o->seq_shapes[(size_t)sequence].cost; out->submap_scan_size = o->seq_shapes[(size_t)sequence].submap_scan_size; }
-  if (!o->seq_dets.empty()) {
-    const cfear_seq_detector& d = o->seq_dets[(size_t)sequence];
-    out->cfar_window_size = d.window_size; out->cfar_nb_guard_cells = d.nb_guard_cells; out->cfar_false_alarm_rate = d.false_alarm_rate; out->z_min = d.z_min;
-  }
-  return CFEAR_OK;
-}
-
-int cfear_odometry_set_sequence_sources(cfear_ctx* ctx, cfear_odometry* o, const int32_t* source, int n_sequences, int n_sources) {
-  if (!ctx || !o || (source && (n_sequences != o->B || n_sources < 1 || n_sources > o->B)))
-    return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_set_sequence_sources: bad argument (n_sequences must be the object's, 1 <= n_sources <= n_sequences)");
-  CFEAR_TRY(seq_fresh_check(ctx, o, "odometry_set_sequence_sources"));
-  if (source) {
-    if (o->filter == CFEAR_FILTER_CACFAR)
-      return cfear_fail(ctx, CFEAR_ERR_UNSUPPORTED, "odometry_set_sequence_sources: filter_type CA-CFAR objects take one sweep per sequence (the detector's clouds are "
-                        "per sequence); source maps are for k-strongest objects");
-    for (int q = 0; q < n_sequences; q++)
-      if (source[q] < 0 || source[q] >= n_sources) {
-        char msg[160];
-        snprintf(msg, sizeof(msg), "odometry_set_sequence_sources: source[%d] = %d is outside [0, %d)", q, (int)source[q], n_sources);
-        return cfear_fail(ctx, CFEAR_ERR_INVALID, msg);
-      }
-  }
-  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  CFEAR_TRY(odo_join(ctx, o));
-  if (o->rp_stream) CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(o->rp_stream));
-  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  std::vector<int32_t> keep;
-  int keep_n = source ? n_sources : 0;
-  if (source) keep.assign(source, source + n_sequences);
-  o->seq_src.swap(keep); std::swap(o->n_sources, keep_n);
-  const int rc = seq_table_upload(ctx, o);
-  if (rc != CFEAR_OK) { o->seq_src.swap(keep); std::swap(o->n_sources, keep_n); (void)seq_table_upload(ctx, o); return rc; }
-  // both parities of the filter-ahead slot buffers hold one slot block per input sweep (nothing is in flight: the streams were joined above)
-  {
-    DevBuf<uint32_t> ns[2];  // the new pair first: a failure leaves the object with the old one (and the old map)
-    const size_t n = (size_t)odo_sources(o) * o->cap_points;
-    const char* what = "hipMalloc filter slot buffers for the source map";
-    if (ns[0].ensure(ctx, n, what) != CFEAR_OK || ns[1].ensure(ctx, n, what) != CFEAR_OK) {
-      o->seq_src.swap(keep); std::swap(o->n_sources, keep_n); (void)seq_table_upload(ctx, o);
-      return cfear_fail(ctx, CFEAR_ERR_NOMEM, what);
-    }
-    for (int i = 0; i < 2; i++) { o->d_slots[i] = std::move(ns[i]); o->filt_pending[i] = false; }
-  }
-  // the staging and chunk buffers are sized per input sweep of a step: released here, allocated again (for the sources) by the next call that needs them
-  o->d_polar.release();
-  for (int i = 0; i < 2; i++) { o->rp_polar[i].release(); o->rp_slots[i].release(); }
-  o->rp_chunk = 0; o->rp_polar_chunk = 0; o->rp_used_pending[0] = o->rp_used_pending[1] = false;
-  return CFEAR_OK;
-}
-
-// ---- per-sequence cost metric and submap size (utils/worker:49-52) --------------------------------------------------------------------
-int cfear_odometry_set_sequence_shapes(cfear_ctx* ctx, cfear_odometry* o, const cfear_seq_shape* shapes, int n_rows) {
-  if (!ctx || !o || (shapes && n_rows != o->B)) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_set_sequence_shapes: bad argument (n_rows must be the object's n_sequences)");
-  if (shapes && o->overlap)
-    return cfear_fail(ctx, CFEAR_ERR_UNSUPPORTED, "odometry_set_sequence_shapes: the object runs its sequences as index ranges on overlap streams (cfear_tune "
-                      "ODOMETRY_OVERLAP at creation); shapes run as one registration launch per group of sequences and are for objects without them");
-  CFEAR_TRY(seq_fresh_check(ctx, o, "odometry_set_sequence_shapes"));
-  const int S = o->nslots - 1;  // the submap_scan_size the object is sized for
-  for (int q = 0; shapes && q < n_rows; q++) {
-    char msg[256];
-    if (shapes[q].cost != CFEAR_COST_P2P && shapes[q].cost != CFEAR_COST_P2L && shapes[q].cost != CFEAR_COST_P2D) {
-      snprintf(msg, sizeof(msg), "odometry_set_sequence_shapes: row %d: cost = %d is no cost metric (CFEAR_COST_P2P / _P2L / _P2D)", q, (int)shapes[q].cost);
-      return cfear_fail(ctx, CFEAR_ERR_INVALID, msg);
-    }
-    if (shapes[q].submap_scan_size < 1 || shapes[q].submap_scan_size > S) {
-      snprintf(msg, sizeof(msg), "odometry_set_sequence_shapes: row %d: submap_scan_size = %d must be in 1..%d, the submap_scan_size the object was created "
-               "with (its scan slots and scratch are sized for it)", q, (int)shapes[q].submap_scan_size, S);
-      return cfear_fail(ctx, CFEAR_ERR_INVALID, msg);
-    }
-  }
-  // a table whose rows would then disagree with their shapes (NULL: with the context's values again)
-  if (!o->seq_rows.empty()) CFEAR_TRY(seq_rows_check(ctx, o, o->seq_rows.data(), o->B, "odometry_set_sequence_shapes", shapes, odo_dets(o)));
-  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  CFEAR_TRY(odo_join(ctx, o));
-  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  std::vector<cfear_seq_shape> keep;
-  if (shapes) keep.assign(shapes, shapes + n_rows);
-  o->seq_shapes.swap(keep);
-  const int rc = seq_table_upload(ctx, o);
-  if (rc != CFEAR_OK) { const std::string err = ctx->err; o->seq_shapes.swap(keep); (void)seq_table_upload(ctx, o); ctx->err = err; }  // (the previous shapes)
-  return rc;
-}
-
-int cfear_odometry_sequence_shape(cfear_ctx* ctx, cfear_odometry* o, int sequence, cfear_seq_shape* out) {
-  if (!ctx || !o || !out || sequence < 0 || sequence >= o->B) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_sequence_shape: bad argument");
-  if (o->seq_shapes.empty()) { out->cost = ctx->par.cost; out->submap_scan_size = ctx->par.submap_scan_size; }
-  else *out = o->seq_shapes[(size_t)sequence];
-  return CFEAR_OK;
-}
-
-// ---- per-sequence CA-CFAR detectors over shared sweeps (params/kstrong_vs_cfar/oxford-cfear-3-ca-cfar: window_size x false_alarm_rate) ---------
-int cfear_odometry_set_sequence_detectors(cfear_ctx* ctx, cfear_odometry* o, const cfear_seq_detector* dets, int n_rows, const int32_t* source, int n_sources) {
-  const char* what = "odometry_set_sequence_detectors";
-  if (!ctx || !o) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_set_sequence_detectors: bad argument");
-  if (o->filter != CFEAR_FILTER_CACFAR)
-    return cfear_fail(ctx, CFEAR_ERR_UNSUPPORTED, "odometry_set_sequence_detectors: the object runs the k-strongest filter (filter_type at creation); detectors are for "
-                      "filter_type CA-CFAR objects (per-sequence k_strongest and z_min: cfear_odometry_set_sequence_params, shared sweeps: cfear_odometry_set_sequence_sources)");
-  if (dets && n_rows != o->B) {
-    char msg[200];
-    snprintf(msg, sizeof(msg), "%s: n_rows = %d must be the object's n_sequences = %d", what, n_rows, o->B);
-    return cfear_fail(ctx, CFEAR_ERR_INVALID, msg);
-  }
-  if (dets && source && (n_sources < 1 || n_sources > o->B)) {
-    char msg[200];
-    snprintf(msg, sizeof(msg), "%s: n_sources = %d must be in 1..%d, the object's n_sequences", what, n_sources, o->B);
-    return cfear_fail(ctx, CFEAR_ERR_INVALID, msg);
-  }
-  CFEAR_TRY(seq_fresh_check(ctx, o, what));
-  cfear_cfar_grid* grid = nullptr;
-  if (dets) CFEAR_TRY(cfear_cfar_grid_create(ctx, dets, source, o->B, source ? n_sources : o->B, what, &grid));
-  // a table whose rows would then disagree with their detectors (NULL: with the context's values again)
-  if (!o->seq_rows.empty()) {
-    const int rc = seq_rows_check(ctx, o, o->seq_rows.data(), o->B, what, odo_shapes(o), dets);
-    if (rc != CFEAR_OK) { cfear_cfar_grid_destroy(grid); return rc; }
-  }
-  hipError_t e = hipSetDevice(ctx->device);
-  int rc = e == hipSuccess ? odo_join(ctx, o) : cfear_fail(ctx, CFEAR_ERR_HIP, what, e);
-  if (rc == CFEAR_OK && o->rp_stream && (e = hipStreamSynchronize(o->rp_stream)) != hipSuccess) rc = cfear_fail(ctx, CFEAR_ERR_HIP, what, e);
-  if (rc == CFEAR_OK && (e = hipStreamSynchronize(ctx->stream)) != hipSuccess) rc = cfear_fail(ctx, CFEAR_ERR_HIP, what, e);
-  // the step's row scratch for the new detections first: a failure leaves the object as it was
-  if (rc == CFEAR_OK) rc = o->d_cfar_rows.ensure(ctx, grid ? cfear_cfar_grid_scratch_ints(ctx, grid, 1) : cfear_cfar_scratch_ints(ctx, (size_t)o->B), "hipMalloc cfar rows");
-  if (rc != CFEAR_OK) { cfear_cfar_grid_destroy(grid); return rc; }
-  cfear_cfar_grid_destroy(o->det_grid);
-  o->det_grid = grid;
-  if (dets) o->seq_dets.assign(dets, dets + n_rows); else o->seq_dets.clear();
-  o->det_map = dets && source;
-  o->n_sources = o->det_map ? n_sources : 0;
-  // the staging and chunk buffers are sized per input sweep of a step and per detection: released here, allocated again by the next call that needs them
-  o->d_polar.release();
-  for (int i = 0; i < 2; i++) o->rp_polar[i].release();
-  o->rp_cfar_rows.release();
-  o->rp_chunk = 0; o->rp_polar_chunk = 0; o->rp_used_pending[0] = o->rp_used_pending[1] = false;
-  return CFEAR_OK;
-}
-
-int cfear_odometry_sequence_detector(cfear_ctx* ctx, cfear_odometry* o, int sequence, cfear_seq_detector* out) {
-  if (!ctx || !o || !out || sequence < 0 || sequence >= o->B) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_sequence_detector: bad argument");
-  if (o->seq_dets.empty()) {
-    out->window_size = ctx->par.cfar_window_size; out->nb_guard_cells = ctx->par.cfar_nb_guard_cells;
-    out->false_alarm_rate = ctx->par.cfar_false_alarm_rate; out->z_min = ctx->par.z_min;
-  } else {
-    *out = o->seq_dets[(size_t)sequence];
-  }
-  return CFEAR_OK;
-}
-
-// ---- the fuser's own switches (odometrykeyframefuser.h:94; odometrykeyframefuser.cpp:165-168, :186) per sequence ------------------------
-int cfear_odometry_set_fuser_options(cfear_ctx* ctx, cfear_odometry* o, const cfear_fuser_options* rows, int n_rows) {
-  if (!ctx || !o) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_set_fuser_options: bad argument");
-  if (rows && n_rows != 1 && n_rows != o->B) {
-    char msg[200];
-    snprintf(msg, sizeof(msg), "odometry_set_fuser_options: n_rows = %d (1: every sequence, or the object's n_sequences = %d: row q for sequence q)", n_rows, o->B);
-    return cfear_fail(ctx, CFEAR_ERR_INVALID, msg);
-  }
-  CFEAR_TRY(seq_fresh_check(ctx, o, "odometry_set_fuser_options"));
-  bool defaults = true;
-  for (int q = 0; rows && q < n_rows; q++) {
-    const char* f = nullptr;
-    int v = 0;
-    if (rows[q].soft_constraint != 0 && rows[q].soft_constraint != 1) { f = "soft_constraint"; v = rows[q].soft_constraint; }
-    else if (rows[q].use_guess != 0 && rows[q].use_guess != 1) { f = "use_guess"; v = rows[q].use_guess; }
-    if (f) {
-      char msg[200];
-      snprintf(msg, sizeof(msg), "odometry_set_fuser_options: row %d: %s = %d (must be 0 or 1)", q, f, v);
-      return cfear_fail(ctx, CFEAR_ERR_INVALID, msg);
-    }
-    if (rows[q].soft_constraint != 0 || rows[q].use_guess != 1) defaults = false;
-  }
-  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  CFEAR_TRY(odo_join(ctx, o));
-  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  std::vector<cfear_fuser_options> keep;  // (all rows at the defaults: no options, the object as it was before the call)
-  if (!defaults) for (int q = 0; q < o->B; q++) keep.push_back(rows[n_rows == 1 ? 0 : q]);
-  o->fuser_opts.swap(keep);
-  const int rc = seq_table_upload(ctx, o);
-  if (rc != CFEAR_OK) { o->fuser_opts.swap(keep); (void)seq_table_upload(ctx, o); }  // (the previous setting)
-  return rc;
-}
-
-int cfear_odometry_fuser_options(cfear_ctx* ctx, cfear_odometry* o, int sequence, cfear_fuser_options* out) {
-  if (!ctx || !o || !out || sequence < 0 || sequence >= o->B) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_fuser_options: bad argument");
-  if (o->fuser_opts.empty()) cfear_default_fuser_options(out);
-  else *out = o->fuser_opts[(size_t)sequence];
-  return CFEAR_OK;
 }
 
 int cfear_odometry_cov_samples(cfear_ctx* ctx, cfear_odometry* o, int sequence, double* costs, int* sampled) {
@@ -2598,7 +2143,7 @@ int cfear_odometry_set_keyframe_recording(cfear_ctx* ctx, cfear_odometry* o, int
   const bool cells = (what & CFEAR_KF_CELLS) != 0;
   if (what && (max_keyframes < 1 || (cells && max_cells < 1)))
     return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_set_keyframe_recording: max_keyframes (and with CFEAR_KF_CELLS max_cells) must be at least 1");
-  if (what) CFEAR_TRY(seq_fresh_check(ctx, o, "odometry_set_keyframe_recording"));
+  if (what) CFEAR_SEQ_TRY(ctx, cfear_seq_fresh_check(odo_seq_object(ctx, o), "odometry_set_keyframe_recording", msg));
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   CFEAR_TRY(odo_join(ctx, o));
   CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // no recorder is running: the buffers may go

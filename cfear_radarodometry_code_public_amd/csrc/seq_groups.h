@@ -1,5 +1,6 @@
 // seq_groups.h -- the registration launch groups of a batched odometry object with per-sequence shapes (cfear_odometry_set_sequence_shapes):
-// host arithmetic only, shared by pipeline.hip (launch_register_kernel) and host/seq_groups_check (tests/test_seq_shape_cpu.py).
+// host arithmetic only, shared by seq_config.h (cfear_seq_config::groups, built by odometry_seq.hip's seq_table_upload), pipeline.hip
+// (launch_register_kernel, which launches by them) and host/seq_groups_check (tests/test_seq_shape_cpu.py).
 //
 // A sequence's group is (cost, small or not small). The batched registration kernels exist once per cost metric (the evaluation inline), and
 // register_step.hip's are compiled for at most `small_scans` scans: their per-scan LDS arrays hold that many, so a registration of more
