@@ -135,10 +135,19 @@ DRIFT_DTYPE = np.dtype([("translation_percent", "f8"), ("rotation_deg_per_100m",
                         ("rotation_deg_per_100m_by_length", "f8", 8), ("segments", "i4"), ("segments_by_length", "i4", 8), ("reserved", "i4")])
 assert DRIFT_DTYPE.itemsize == C.sizeof(Drift) == 184
 
+class CfarPlan(C.Structure):
+    """cfear_cfar_plan (include/cfear_hip.h): the launch plan of the CA-CFAR detector"""
+    _fields_ = [("kernel", C.c_int32), ("TB", C.c_int32), ("NW", C.c_int32), ("RS", C.c_int32), ("full", C.c_int32), ("sh", C.c_int32), ("kopen", C.c_int32),
+                ("rmin", C.c_int32), ("rmax", C.c_int32), ("cr", C.c_int32 * 4), ("cq", C.c_int32 * 4), ("padl", C.c_int32), ("fill", C.c_int32),
+                ("lds_bytes", C.c_int32), ("per_cu", C.c_int32), ("workgroups", C.c_int32)]
+
+
+CFAR_KERNELS = ("owner", "fast16", "fast32", "general")  # CFEAR_CFAR_KERNEL_*
+
 EXPORTS = [
     "cfear_version", "cfear_default_params", "cfear_create", "cfear_destroy", "cfear_last_error",
     "cfear_set_params", "cfear_synchronize", "cfear_tune", "cfear_kstrongest_launch_shape", "cfear_kstrongest_device", "cfear_kstrongest_host",
-    "cfear_rotate_polar", "cfear_rotate_polar_device", "cfear_filter_polar", "cfear_filter_polar_device", "cfear_filter_cfar", "cfear_filter_cfar_device", "cfear_filter_cfar_batch_device", "cfear_filter_cfar_grid_device", "cfear_cloud_upload", "cfear_cloud_size",
+    "cfear_rotate_polar", "cfear_rotate_polar_device", "cfear_filter_polar", "cfear_filter_polar_device", "cfear_filter_cfar", "cfear_filter_cfar_device", "cfear_filter_cfar_batch_device", "cfear_filter_cfar_grid_device", "cfear_cfar_launch_plan", "cfear_cloud_upload", "cfear_cloud_size",
     "cfear_cloud_download", "cfear_clouds_download", "cfear_cloud_release", "cfear_compensate", "cfear_compensate_pair", "cfear_scan_create",
     "cfear_scan_from_cells", "cfear_scan_release", "cfear_scan_size", "cfear_scan_download_cells", "cfear_scan_closest",
     "cfear_register", "cfear_register_soft", "cfear_register_time_continuous", "cfear_get_cost", "cfear_cov_by_sampling", "cfear_odometry_create", "cfear_odometry_destroy", "cfear_odometry_reset",
@@ -196,6 +205,7 @@ def lib():
         "cfear_filter_cfar_device": (C.c_int, [vp, u8p, C.c_int, C.c_int, C.c_float, C.c_double, C.POINTER(vp)]),
         "cfear_filter_cfar_batch_device": (C.c_int, [vp, u8p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_double, f32p, C.c_int, i32p]),
         "cfear_filter_cfar_grid_device": (C.c_int, [vp, u8p, C.c_int, vp, i32p, C.c_int, C.c_double, f32p, C.c_int, i32p]),
+        "cfear_cfar_launch_plan": (C.c_int, [vp, C.c_int, C.c_int, C.c_float, C.c_int, C.POINTER(CfarPlan)]),
         "cfear_cloud_upload": (C.c_int, [vp, f32p, C.c_int, C.POINTER(vp)]),
         "cfear_cloud_size": (C.c_int, [vp, vp, C.POINTER(C.c_int)]),
         "cfear_cloud_download": (C.c_int, [vp, vp, f32p, C.c_int, C.POINTER(C.c_int)]),
@@ -470,6 +480,16 @@ class Context:
             rc = self._L.cfear_filter_cfar_device(self._h, _addr(polar), *args)
         self._check(rc, "cfear_filter_cfar")
         return Cloud(self, c)
+
+    def cfar_launch_plan(self, window_size=10, nb_guard_cells=20, false_alarm_rate=0.01, n_scans=1):
+        """cfear_cfar_launch_plan: the detector launch for n_scans images of this context as a dict - kernel (a CFAR_KERNELS name), TB, NW, RS, full, sh,
+        kopen, rmin, rmax, cr, cq, padl, fill, lds_bytes, per_cu, workgroups (csrc/cfar_shape.h; host/cfar_shape_check prints the same without a GPU)"""
+        p = CfarPlan()
+        self._check(self._L.cfear_cfar_launch_plan(self._h, int(window_size), int(nb_guard_cells), C.c_float(false_alarm_rate), int(n_scans), C.byref(p)),
+                    "cfear_cfar_launch_plan")
+        d = {f: getattr(p, f) for f, _ in CfarPlan._fields_}
+        d.update(kernel=CFAR_KERNELS[p.kernel], cr=tuple(p.cr), cq=tuple(p.cq))
+        return d
 
     def filter_cfar_grid(self, d_polar, n_sources, dets, source, d_xyi, capacity, d_counts, max_distance=400.0):
         """Several CA-CFAR detectors over shared device-resident images in one pass (cfear_filter_cfar_grid_device): cloud c is the

@@ -28,12 +28,13 @@
 
 #include "blockops.h"
 #include "cfar_grid.h"
+#include "cfar_shape.h"
 #include "common.h"
 
 namespace {
 using namespace cfear_dev;
 
-constexpr int CFAR_BLOCK = 256;
+constexpr int CFAR_BLOCK = CFEAR_CFAR_BLOCK;
 constexpr int CFAR_MAX_R = 16384;  // range bins per azimuth the LDS row / prefix arrays hold
 
 struct CfarParams {
@@ -407,7 +408,10 @@ __global__ __launch_bounds__(CFAR_BLOCK) void cfar_detect_grid_kernel(const uint
 //     - not a bit per bin: the second kernel (cfar_emit_recs_kernel) never touches the image or a mask. A segment with more hits than its slot
 //     holds (CFAR_SEG_CAP) writes its threads' hit masks instead and the emit kernel walks those (rare: a row of clutter).
 // The workgroups are persistent (a row per trip, the next row's loads in flight during the current row's decisions).
-constexpr int CFAR_SEG_CAP = 64;  // records per (row, wave) segment
+// What shapes the array is the launch's (cfar_shape.h; cfear_cfar_launch_plan reads it back): tests/test_cfar_layout_gpu.py holds the kernel against
+// the oracle at the edges of that plan - rows that nearly fill the workgroup, every neighbour-copy count, every integer scale, the widest arrays,
+// the candidate and record limits, the trips of the persistent workgroups - and tests/test_cfar_shape_cpu.py pins the plan itself.
+constexpr int CFAR_SEG_CAP = CFEAR_CFAR_SEG_CAP;  // records per (row, wave) segment
 constexpr int CFAR_SEG_MASKS = 1 << 30;  // flag on a segment's count: its hits are in the threads' masks, not in records
 
 // thread's ND dwords of a row. CLAMPED: the caller hands a pointer inside the row for every thread (threads past the row's end one that they
@@ -590,10 +594,20 @@ __global__ __launch_bounds__(64 * NW, NW == 2 ? 3 : 1) void cfar_detect_owner_ke
     }
     if (last_col_thread >= NT - 1) {  // (uniform; a row that nearly fills the workgroup) what no thread is there to write, right of the last thread's column: the row total
       const int c0 = padl + NT - 1, ncol = RS - 1 - c0;  // whole columns c0 + 1 .., and the rows above TB of column c0 itself (thread NT's first values)
+      // One writer per word and barrier interval: thread t writes rows 0 .. TB - 1 of its own column, the rows from TB up of column t - 1 and the rows below 0
+      // of column t + 1. Thread NT - 1 is there and writes whenever this loop runs (NT - 1 <= last_col_thread), so the rows below 0 of column c0 + 1 are ITS:
+      // they hold P'[TB NT + rho], rho < 0 - the row total only from bin R on, and with TB (NT - 1) < R < TB NT the thread's last bytes lie in between.
+      // The loop used to write the total there as well, and a window bound read from those cells saw whichever store came last
+      // (tests/test_cfar_layout_gpu.py: rows that nearly fill the workgroup). It takes the rest: rows from 0 up of column c0 + 1 (thread NT's own and
+      // thread NT + 1's copies, all of bins >= R), the whole columns to the right, and thread NT's copies in column c0.
       const uint32_t tot_s = (uint32_t)tot << sh;
       for (int k = tid; k < nrows * ncol + P.rmax; k += NT) {
-        if (k < nrows * ncol) lp[(k / ncol) * RS + c0 + 1 + k % ncol] = tot_s;
-        else lp0[(TB + k - nrows * ncol) * RS + c0] = tot_s;
+        if (k < nrows * ncol) {
+          const int pr = k / ncol, pc = k % ncol;  // physical row (0 = row rmin), column c0 + 1 + pc
+          if (pc != 0 || pr >= -P.rmin) lp[pr * RS + c0 + 1 + pc] = tot_s;
+        } else {
+          lp0[(TB + k - nrows * ncol) * RS + c0] = tot_s;
+        }
       }
     }
 #pragma unroll
@@ -917,8 +931,7 @@ int cfar_params(cfear_ctx* ctx, int window_size, int nb_guard_cells, float false
   // float members of radarDriver::Parameters bound to const double& (radar_driver.cpp:54)
   P.range_res = (double)ctx->par.range_res;
   const double static_threshold = (double)ctx->par.z_min, min_distance = (double)ctx->par.min_distance;
-  const double N = (double)(window_size * 2);  // CFARFilter::getCAScalingFactor
-  P.scaling = N * (pow((double)false_alarm_rate, -1. / N) - 1.);
+  P.scaling = cfear_cfar_scaling(window_size, false_alarm_rate);
   P.kf = (float)(P.scaling * 0.5 / (double)window_size);
   P.ilo = P.R; P.ihi = -1;
   for (int i = 0; i < P.R; i++) {
@@ -930,78 +943,38 @@ int cfar_params(cfear_ctx* ctx, int window_size, int nb_guard_cells, float false
   P.mask_words = 2 * ((P.R + 63) / 64);
   P.ipt = (P.R + CFAR_BLOCK - 1) / CFAR_BLOCK;
   P.ipt |= 1;
-  // owner-layout detector: the scale of the integer test (sh < 0: not usable - the old kernels run)
-  P.sh = -1; P.kopen = 0;
   { static const int stop = getenv("CFEAR_CFAR_STOP") ? atoi(getenv("CFEAR_CFAR_STOP")) : 0; P.stop = stop; }
-  {
-    const double smax = 2.0 * (double)window_size * 65025.0, kf = P.scaling * 0.5 / (double)window_size;
-    for (int sh = 12; sh >= 0 && P.sh < 0; sh--) {
-      if (smax * (double)(1 << sh) >= 2147483648.0) continue;
-      const double k = ceil((1.0 + 4e-6) * (double)(1 << sh) / kf);
-      if (k >= 64.0 && k <= 33025.0) { P.sh = sh; P.kopen = (int)k; }  // I^2 kopen < 2^31; at least six bits of the threshold
-    }
-  }
+  cfear_cfar_int_scale(window_size, P.scaling, &P.sh, &P.kopen);  // owner-layout detector: the scale of the integer test (sh < 0: not usable - the old kernels run)
   *out = P;
   return CFEAR_OK;
 }
 
-// ---- which instantiation of the owner-layout detector a row length takes (threads x bins per thread just above R) ----
-struct CfarOwnerShape { int TB, NW; };
-
+// ---- which instantiation of the owner-layout detector a row length takes: cfar_shape.h (the arithmetic of this whole section) ----
 const CfarOwnerShape* cfar_owner_shape(int R, int reach /* guard + window, or 0: the shape with the largest scratch for this row length */) {
-  static const CfarOwnerShape shapes[4] = {{28, 2}, {20, 3}, {16, 4}, {32, 4}};
   static const int forced = getenv("CFEAR_CFAR_SHAPE") ? atoi(getenv("CFEAR_CFAR_SHAPE")) : 0;  // bins per thread (tools/gpu_time_cfar.py: A/B of the shapes)
-  // Measured at 3360 bins (profiles/r06_cfar_shapes.txt): two waves x 28 bins per thread is the fastest shape while the windows are short; with long
-  // windows (the reference's sweep goes to 500 bins) the bins a row end clips are hundreds, the integer test is loose for them, and a wave of 1792
-  // bins collects more than the 64 candidates one pass decides - four waves x 16 bins then.
-  const CfarOwnerShape* best = nullptr;
-  for (const CfarOwnerShape& s : shapes) {
-    if (R >= 64 * s.NW * s.TB) continue;
-    if (forced ? s.TB == forced : false) return &s;
-    if (reach > 128 && s.NW < 4) continue;
-    if (reach == 0 ? (!best || s.NW > best->NW) : (!best || s.NW * s.TB < best->NW * best->TB)) best = &s;
-  }
-  return best;
+  return cfear_cfar_owner_shape(R, reach, forced);
 }
-size_t cfar_owner_ints_per_row(const CfarOwnerShape& s) { return (size_t)s.NW * (2 + CFAR_SEG_CAP) + 64 * (size_t)s.NW; }
 int cfar_device_cus(int device) {
   static int cus[64] = {0};
   if (device < 0 || device >= 64) return 256;
   if (!cus[device]) { int n = 0; cus[device] = (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && n > 0) ? n : 256; }
   return cus[device];
 }
-size_t cfar_owner_lds_bytes(int nrows, int NW, int RS) { return sizeof(uint32_t) * ((size_t)nrows * RS + 64 * NW + (size_t)NW * CFAR_SEG_CAP + 16); }
-// (row, column) offsets of the four window bounds for TB bins per thread: r in (-TB, TB), the combination with the fewest rows
 void cfar_owner_offsets(CfarParams* P, int TB) {
-  const int off[4] = {-P->guard - P->window, -P->guard, P->guard, P->guard + P->window};
-  int best = 1 << 30;
-  for (int m = 0; m < 16; m++) {
-    int r[4], lo = 0, hi = 0;
-    for (int c = 0; c < 4; c++) {
-      r[c] = ((off[c] % TB) + TB) % TB;
-      if (((m >> c) & 1) && r[c] > 0) r[c] -= TB;
-      lo = r[c] < lo ? r[c] : lo; hi = r[c] > hi ? r[c] : hi;
-    }
-    if (hi - lo < best) {
-      best = hi - lo; P->rmin = lo; P->rmax = hi;
-      for (int c = 0; c < 4; c++) { P->cr[c] = r[c]; P->cq[c] = (off[c] - r[c]) / TB; }
-    }
-  }
+  const CfarOwnerOffsets O = cfear_cfar_owner_offsets(P->guard, P->window, TB);
+  P->rmin = O.rmin; P->rmax = O.rmax;
+  for (int c = 0; c < 4; c++) { P->cr[c] = O.cr[c]; P->cq[c] = O.cq[c]; }
 }
 template <int TB, int NW, int RS, bool FULL>
 int cfar_launch_owner_tf(cfear_ctx* ctx, const CfarParams& P0, int padl, const uint8_t* d_polar, size_t rows, int* seg_count, uint32_t* recs, uint32_t* hmask, hipStream_t stream) {
   constexpr int NT = 64 * NW;
   CfarParams P = P0;
   cfar_owner_offsets(&P, TB);
-  const size_t lds = cfar_owner_lds_bytes(TB + P.rmax - P.rmin, NW, RS);
+  const size_t lds = cfear_cfar_owner_lds_bytes(TB + P.rmax - P.rmin, NW, RS);
   if (lds > 64 * 1024)
     CFEAR_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(cfar_detect_owner_kernel<TB, NW, RS, FULL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  int per_cu = (int)((160 * 1024) / (lds + 512));  // persistent workgroups: what a compute unit's LDS holds, up to 32 waves
-  if (per_cu * NW > 32) per_cu = 32 / NW;
-  if (per_cu < 1) per_cu = 1;
-  { static const int force = getenv("CFEAR_CFAR_PER_CU") ? atoi(getenv("CFEAR_CFAR_PER_CU")) : 0; if (force > 0 && force < per_cu) per_cu = force; }  // (profiling: fewer resident workgroups)
-  size_t grid = (size_t)cfar_device_cus(ctx->device) * per_cu;
-  if (grid > rows) grid = rows;
+  static const int force = getenv("CFEAR_CFAR_PER_CU") ? atoi(getenv("CFEAR_CFAR_PER_CU")) : 0;  // (profiling: fewer resident workgroups)
+  const size_t grid = cfear_cfar_owner_grid(cfar_device_cus(ctx->device), cfear_cfar_owner_per_cu(lds, NW, force), rows);  // persistent workgroups
   hipLaunchKernelGGL((cfar_detect_owner_kernel<TB, NW, RS, FULL>), dim3((unsigned)grid), dim3(NT), lds, stream, d_polar, P, (int)rows, padl, seg_count, recs, hmask);
   return CFEAR_OK;
 }
@@ -1010,34 +983,21 @@ int cfar_launch_owner_t(cfear_ctx* ctx, const CfarParams& P, int padl, const uin
   return P.R % TB == 0 ? cfar_launch_owner_tf<TB, NW, RS, true>(ctx, P, padl, d_polar, rows, seg_count, recs, hmask, stream)
                        : cfar_launch_owner_tf<TB, NW, RS, false>(ctx, P, padl, d_polar, rows, seg_count, recs, hmask, stream);
 }
-// columns of the transposed prefix array this configuration needs: one per thread that holds bins (and the one that holds bin R), and on either
-// side the window's reach in threads + 1; rounded up to a multiple of 64
-int cfar_owner_columns(const CfarParams& P, const CfarOwnerShape& s, int* padl) {
-  const int pad = (P.guard + P.window + s.TB - 1) / s.TB + 1, data = P.R / s.TB + 1;
-  const int rs = (data + 2 * pad + 63) / 64 * 64;
-  *padl = (rs - data) / 2;
-  return rs;
-}
 // true when the owner-layout detector takes this configuration (dword rows and base, a usable integer scale, an instantiation for its columns)
 bool cfar_owner_usable(const CfarParams& P, const uint8_t* d_polar, const CfarOwnerShape** shape) {
   static const bool off = getenv("CFEAR_CFAR_OLD_KERNELS") != nullptr;  // tools/gpu_time_cfar.py: A/B timing against the round-5 kernels
-  if (off || (P.R & 3) != 0 || (reinterpret_cast<uintptr_t>(d_polar) & 3) != 0 || P.sh < 0 || P.iv_min > 255) return false;
-  const CfarOwnerShape* s = cfar_owner_shape(P.R, P.guard + P.window);
-  if (!s) return false;
-  int padl;
-  if (cfar_owner_columns(P, *s, &padl) > 64 * s->NW + 128) return false;
-  *shape = s;
-  return true;
+  static const int forced = getenv("CFEAR_CFAR_SHAPE") ? atoi(getenv("CFEAR_CFAR_SHAPE")) : 0;
+  return !off && cfear_cfar_owner_usable(P.R, P.guard, P.window, P.sh, (reinterpret_cast<uintptr_t>(d_polar) & 3) == 0, P.iv_min <= 255, forced, shape);
 }
 int cfar_launch_owner(cfear_ctx* ctx, const CfarParams& P, const CfarOwnerShape& s, const uint8_t* d_polar, size_t rows, int* seg_count, uint32_t* recs,
                       uint32_t* hmask, hipStream_t stream) {
   int padl;
-  const int rs = cfar_owner_columns(P, s, &padl);
+  const int RS = cfear_cfar_owner_rs(cfear_cfar_owner_columns(P.R, P.guard, P.window, s.TB, &padl), s.NW, &padl);
 #define CFAR_OWNER_CASE(TB_, NW_) \
   if (s.TB == TB_ && s.NW == NW_) { \
-    if (rs <= 64 * NW_) return cfar_launch_owner_t<TB_, NW_, 64 * NW_>(ctx, P, padl + (64 * NW_ - rs) / 2, d_polar, rows, seg_count, recs, hmask, stream); \
-    if (rs <= 64 * NW_ + 64) return cfar_launch_owner_t<TB_, NW_, 64 * NW_ + 64>(ctx, P, padl + (64 * NW_ + 64 - rs) / 2, d_polar, rows, seg_count, recs, hmask, stream); \
-    return cfar_launch_owner_t<TB_, NW_, 64 * NW_ + 128>(ctx, P, padl + (64 * NW_ + 128 - rs) / 2, d_polar, rows, seg_count, recs, hmask, stream); \
+    if (RS == 64 * NW_) return cfar_launch_owner_t<TB_, NW_, 64 * NW_>(ctx, P, padl, d_polar, rows, seg_count, recs, hmask, stream); \
+    if (RS == 64 * NW_ + 64) return cfar_launch_owner_t<TB_, NW_, 64 * NW_ + 64>(ctx, P, padl, d_polar, rows, seg_count, recs, hmask, stream); \
+    if (RS == 64 * NW_ + 128) return cfar_launch_owner_t<TB_, NW_, 64 * NW_ + 128>(ctx, P, padl, d_polar, rows, seg_count, recs, hmask, stream); \
   }
   CFAR_OWNER_CASE(28, 2)
   CFAR_OWNER_CASE(20, 3)
@@ -1062,11 +1022,11 @@ int cfar_launch_owner_path(cfear_ctx* ctx, const CfarParams& P, const CfarOwnerS
   CFEAR_HIP_CHECK(ctx, hipGetLastError());
   return CFEAR_OK;
 }
-size_t cfar_lds_bytes(const CfarParams& P) { return sizeof(uint32_t) * (size_t)(P.R + 1) + (size_t)((P.R + 3 + 7) & ~3); }
+size_t cfar_lds_bytes(const CfarParams& P) { return cfear_cfar_general_lds_bytes(P.R); }
 template <int TB>
 int cfar_launch_fast(cfear_ctx* ctx, const CfarParams& P, const uint8_t* d_polar, size_t rows, int* d_count, uint32_t* d_mask, hipStream_t stream) {
-  const int pad = (P.guard + P.window + 3) & ~3;
-  const size_t lds = sizeof(uint32_t) * ((size_t)pad + CFAR_BLOCK * TB + pad + 4);  // the padded prefix array
+  const int pad = (int)cfear_cfar_fast_pad(P.guard, P.window);
+  const size_t lds = cfear_cfar_fast_lds_bytes(P.guard, P.window, TB);  // the padded prefix array
   if (lds > 64 * 1024)
     CFEAR_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(cfar_detect_fast_kernel<TB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL((cfar_detect_fast_kernel<TB>), dim3((unsigned)rows), dim3(CFAR_BLOCK), lds, stream, d_polar, P, pad, d_count, d_mask);
@@ -1075,10 +1035,9 @@ int cfar_launch_fast(cfear_ctx* ctx, const CfarParams& P, const uint8_t* d_polar
 int cfar_launch_detect(cfear_ctx* ctx, const CfarParams& P, const uint8_t* d_polar, size_t rows, int* d_count, uint32_t* d_mask, hipStream_t stream) {
   // the lean kernel when the rows are dword-aligned, fit 256 threads x 16 (32) bins, and the window is not enormous (its pads live in LDS)
   static const bool general_only = getenv("CFEAR_CFAR_GENERAL_KERNEL") != nullptr;  // tools/gpu_time_cfar.py: A/B timing of the two detectors
-  if ((P.R & 3) == 0 && (reinterpret_cast<uintptr_t>(d_polar) & 3) == 0 && P.guard + P.window <= 2048 && P.iv_min <= 255 && !general_only) {
-    if (P.R <= CFAR_BLOCK * 16) return cfar_launch_fast<16>(ctx, P, d_polar, rows, d_count, d_mask, stream);
-    if (P.R <= CFAR_BLOCK * 32) return cfar_launch_fast<32>(ctx, P, d_polar, rows, d_count, d_mask, stream);
-  }
+  const int kernel = general_only ? CFEAR_CFAR_KERNEL_GENERAL : cfear_cfar_round5_kernel(P.R, P.guard, P.window, (reinterpret_cast<uintptr_t>(d_polar) & 3) == 0, P.iv_min <= 255);
+  if (kernel == CFEAR_CFAR_KERNEL_FAST16) return cfar_launch_fast<16>(ctx, P, d_polar, rows, d_count, d_mask, stream);
+  if (kernel == CFEAR_CFAR_KERNEL_FAST32) return cfar_launch_fast<32>(ctx, P, d_polar, rows, d_count, d_mask, stream);
   const size_t lds = cfar_lds_bytes(P);
   if (lds > 64 * 1024)
     CFEAR_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(cfar_detect_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -1143,7 +1102,7 @@ int cfar_run(cfear_ctx* ctx, const uint8_t* d_polar, int window_size, int nb_gua
 __attribute__((visibility("hidden"))) size_t cfear_cfar_scratch_ints(const cfear_ctx* ctx, size_t n_scans) {
   size_t per_row = 2 + 2 * (size_t)((ctx->R + 63) / 64);  // mask-based kernels
   const CfarOwnerShape* s = cfar_owner_shape(ctx->R, 0);  // owner-layout detector: segment counts, bases, record slots, overflow masks (its widest shape)
-  if (s && cfar_owner_ints_per_row(*s) > per_row) per_row = cfar_owner_ints_per_row(*s);
+  if (s && cfear_cfar_owner_ints_per_row(*s) > per_row) per_row = cfear_cfar_owner_ints_per_row(*s);
   return n_scans * (size_t)ctx->A * per_row;
 }
 // the batched filter on `stream` with the caller's row scratch (cfear_cfar_scratch_ints): detect pass (the only one that reads the
@@ -1307,6 +1266,15 @@ __attribute__((visibility("hidden"))) int cfear_launch_cfar_grid(cfear_ctx* ctx,
 }
 
 extern "C" {
+
+int cfear_cfar_launch_plan(cfear_ctx* ctx, int window_size, int nb_guard_cells, float false_alarm_rate, int n_scans, cfear_cfar_plan* plan) {
+  if (!ctx) return CFEAR_ERR_INVALID;
+  if (!plan || n_scans <= 0) return cfear_fail(ctx, CFEAR_ERR_INVALID, "cfar_launch_plan: bad argument");
+  CfarParams P;
+  CFEAR_TRY(cfar_params(ctx, window_size, nb_guard_cells, false_alarm_rate, 400.0, &P));  // (the range gate is no part of the plan)
+  *plan = cfear_cfar_plan_of(P.R, P.window, P.guard, false_alarm_rate, P.iv_min <= 255, cfar_device_cus(ctx->device), (size_t)n_scans * P.A);
+  return CFEAR_OK;
+}
 
 int cfear_filter_cfar_grid_device(cfear_ctx* ctx, const uint8_t* d_polar, int n_sources, const cfear_seq_detector* dets, const int32_t* source, int n_clouds,
                                   double max_distance, float* d_xyi, int capacity, int* d_counts) {

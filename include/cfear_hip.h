@@ -194,6 +194,26 @@ int cfear_filter_cfar_device(cfear_ctx* ctx, const uint8_t* d_polar, int window_
  * cfear_cloud_upload-style consumers or a caller's own kernels; sizes are known on the device without a host round trip. */
 int cfear_filter_cfar_batch_device(cfear_ctx* ctx, const uint8_t* d_polar, int n_scans, int window_size, int nb_guard_cells,
                                    float false_alarm_rate, double max_distance, float* d_xyi, int capacity, int* d_counts);
+/* The launch plan of the CA-CFAR detector for n_scans images of this context (4-byte-aligned image base; the launcher calls the same arithmetic,
+ * csrc/cfar_shape.h; no GPU work). kernel: which detector takes the configuration - the owner-layout detector, or a round-5 kernel (rows that
+ * are no whole dwords, no usable integer scale, more columns than the widest instantiation holds). For the owner-layout detector: TB bins per
+ * thread x NW waves ({28,2} below 3584 bins, {20,3} below 3840, {16,4} below 4096, {32,4} below 8192; four waves whenever nb_guard_cells +
+ * window_size > 128), RS columns of the transposed prefix array, full = the row is a whole number of threads' segments, sh / kopen the scale of
+ * the integer test, window bound c of bin TB t + e at row e + cr[c], column padl + t + cq[c] of rows rmin .. TB + rmax - 1 (guard 10 / window 40
+ * at 3360 bins: {28,2}, cr = 6, -10, 10, -6, 48 rows), fill = the row nearly fills the workgroup and a loop writes the columns right of the last
+ * thread's, lds_bytes, per_cu persistent workgroups per compute unit, workgroups launched. The owner fields are 0 for a round-5 kernel, whose
+ * workgroups are one per row. (The profiling overrides the launcher reads from the environment - CFEAR_CFAR_SHAPE, _PER_CU, _OLD_KERNELS,
+ * _GENERAL_KERNEL - are not part of the plan.) */
+enum { CFEAR_CFAR_KERNEL_OWNER = 0, CFEAR_CFAR_KERNEL_FAST16 = 1, CFEAR_CFAR_KERNEL_FAST32 = 2, CFEAR_CFAR_KERNEL_GENERAL = 3 };
+typedef struct cfear_cfar_plan {
+  int32_t kernel;
+  int32_t TB, NW, RS, full;
+  int32_t sh, kopen;
+  int32_t rmin, rmax, cr[4], cq[4];
+  int32_t padl, fill;
+  int32_t lds_bytes, per_cu, workgroups;
+} cfear_cfar_plan;
+int cfear_cfar_launch_plan(cfear_ctx* ctx, int window_size, int nb_guard_cells, float false_alarm_rate, int n_scans, cfear_cfar_plan* plan);
 /* One CA-CFAR detector of a grid (launch/oxford/eval/params/kstrong_vs_cfar/oxford-cfear-3-ca-cfar sweeps window_size x
  * false_alarm_rate, and guard cells and z_min are loops of the worker too): what AzimuthCACFAR takes besides the object-wide range_res,
  * min_distance and max_distance. */
