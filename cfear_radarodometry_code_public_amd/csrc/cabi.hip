@@ -83,10 +83,10 @@ int cfear_create(cfear_ctx** out, int device, void* stream, const cfear_params* 
   if (stream) {
     ctx->stream = reinterpret_cast<hipStream_t>(stream);
   } else {
-    if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) { delete ctx; return CFEAR_ERR_HIP; }
-    ctx->own_stream = true;
+    if (ctx->own_stream.create(hipStreamNonBlocking) != hipSuccess) { delete ctx; return CFEAR_ERR_HIP; }
+    ctx->stream = ctx->own_stream;
   }
-  if (hipEventCreate(&ctx->ev0) != hipSuccess || hipEventCreate(&ctx->ev1) != hipSuccess) { cfear_destroy(ctx); return CFEAR_ERR_HIP; }
+  if (ctx->ev0.create(hipEventDefault) != hipSuccess || ctx->ev1.create(hipEventDefault) != hipSuccess) { cfear_destroy(ctx); return CFEAR_ERR_HIP; }
   // theta = (double(bearing + 1) / nb_azimuths) * 2 * M_PI (radar_filters.cpp:317), cos/sin by host libm
   std::vector<double> trig(2 * (size_t)A);
   for (int b = 0; b < A; b++) {
@@ -106,14 +106,8 @@ void cfear_destroy(cfear_ctx* ctx) {
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   for (auto& b : ctx->pool) (void)hipFree(b.second);
   for (auto& b : ctx->hpool) (void)hipHostFree(b.second);
-  if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
-  if (ctx->h_img) (void)hipHostFree(ctx->h_img);
-  if (ctx->ev_img) (void)hipEventDestroy(ctx->ev_img);
-  if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
-  if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
   cfear_cfar_grid_destroy(ctx->cfar_grid);
-  if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
-  delete ctx;  // (and with it the device buffers it owns)
+  delete ctx;  // (and with it what it owns: pinned staging, events, its own stream, device buffers - in that order)
 }
 
 const char* cfear_last_error(const cfear_ctx* ctx) { return ctx ? ctx->err.c_str() : "null context"; }
@@ -210,13 +204,9 @@ void cfear_hpool_free(cfear_ctx* ctx, void* p, size_t bytes) {
   ctx->hpool.emplace_back(bytes, p);
 }
 int cfear_ensure_hstage(cfear_ctx* ctx, size_t bytes) {
-  if (bytes <= ctx->h_stage_bytes) return CFEAR_OK;
-  if (ctx->h_stage) { CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream)); (void)hipHostFree(ctx->h_stage); }
-  ctx->h_stage = nullptr; ctx->h_stage_bytes = 0;
-  const size_t want = (bytes + 65535) & ~(size_t)65535;
-  if (hipHostMalloc(reinterpret_cast<void**>(&ctx->h_stage), want, hipHostMallocDefault) != hipSuccess) return cfear_fail(ctx, CFEAR_ERR_NOMEM, "hipHostMalloc staging");
-  ctx->h_stage_bytes = want;
-  return CFEAR_OK;
+  if (bytes <= ctx->h_stage.size()) return CFEAR_OK;
+  if (ctx->h_stage) CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  return ctx->h_stage.ensure(ctx, (bytes + 65535) & ~(size_t)65535, "hipHostMalloc staging");
 }
 
 // One polar image (or a few) from host memory to the device on the context stream. Pinned memory (cfear_host_alloc) goes by DMA directly.
@@ -234,13 +224,8 @@ int cfear_upload_image(cfear_ctx* ctx, void* d_dst, const void* h_src, size_t by
     return CFEAR_OK;
   }
   if (ctx->ev_img_pending) { CFEAR_HIP_CHECK(ctx, hipEventSynchronize(ctx->ev_img)); ctx->ev_img_pending = false; }  // the previous image has left the staging
-  if (bytes > ctx->h_img_bytes) {
-    if (ctx->h_img) (void)hipHostFree(ctx->h_img);
-    ctx->h_img = nullptr; ctx->h_img_bytes = 0;
-    if (hipHostMalloc(reinterpret_cast<void**>(&ctx->h_img), bytes, hipHostMallocDefault) != hipSuccess) return cfear_fail(ctx, CFEAR_ERR_NOMEM, "hipHostMalloc image staging");
-    ctx->h_img_bytes = bytes;
-  }
-  if (!ctx->ev_img) CFEAR_HIP_CHECK(ctx, hipEventCreateWithFlags(&ctx->ev_img, hipEventDisableTiming));
+  CFEAR_TRY(ctx->h_img.ensure(ctx, bytes, "hipHostMalloc image staging"));
+  CFEAR_TRY(ctx->ev_img.ensure(ctx, hipEventDisableTiming, "hipEventCreateWithFlags(&ctx->ev_img, hipEventDisableTiming)"));
   for (size_t off = 0; off < bytes; off += PIECE) {
     const size_t nb = bytes - off < PIECE ? bytes - off : PIECE;
     memcpy(ctx->h_img + off, static_cast<const unsigned char*>(h_src) + off, nb);

@@ -51,10 +51,103 @@ class DevBuf {
   size_t n_ = 0;
 };
 
+// The owners of the other three things the runtime hands out, of DevBuf's shape: move-only, converting to the raw handle, gone with their
+// owner. As with DevBuf, WHEN one may go is the caller's to know: the work that uses it is drained first.
+// An event, created with the caller's flags (hipEventDefault: a timing event).
+class Event {
+ public:
+  Event() = default;
+  Event(Event&& b) noexcept : e_(b.e_) { b.e_ = nullptr; }
+  Event& operator=(Event&& b) noexcept {
+    if (this != &b) { release(); e_ = b.e_; b.e_ = nullptr; }
+    return *this;
+  }
+  ~Event() { release(); }
+  operator hipEvent_t() const { return e_; }
+  void release() {
+    if (e_) (void)hipEventDestroy(e_);
+    e_ = nullptr;
+  }
+  hipError_t create(unsigned flags) {
+    release();
+    const hipError_t e = flags == hipEventDefault ? hipEventCreate(&e_) : hipEventCreateWithFlags(&e_, flags);
+    if (e != hipSuccess) e_ = nullptr;
+    return e;
+  }
+  // created on first use; a failure leaves it empty and is reported as `what` with the runtime's text
+  int ensure(cfear_ctx* ctx, unsigned flags, const char* what) {
+    if (e_) return CFEAR_OK;
+    const hipError_t e = create(flags);
+    return e == hipSuccess ? CFEAR_OK : cfear_fail(ctx, CFEAR_ERR_HIP, what, e);
+  }
+
+ private:
+  hipEvent_t e_ = nullptr;
+};
+
+// A stream, made in one of the three ways this library makes them. It knows nothing of cfear_ctx::aux_streams: who creates a stream the
+// context is to wait for adds it there, and takes it out again before the owner goes.
+class Stream {
+ public:
+  Stream() = default;
+  Stream(Stream&& b) noexcept : s_(b.s_) { b.s_ = nullptr; }
+  Stream& operator=(Stream&& b) noexcept {
+    if (this != &b) { release(); s_ = b.s_; b.s_ = nullptr; }
+    return *this;
+  }
+  ~Stream() { release(); }
+  operator hipStream_t() const { return s_; }
+  void release() {
+    if (s_) (void)hipStreamDestroy(s_);
+    s_ = nullptr;
+  }
+  hipError_t create(unsigned flags) { release(); return made(hipStreamCreateWithFlags(&s_, flags)); }
+  hipError_t create_with_priority(unsigned flags, int priority) { release(); return made(hipStreamCreateWithPriority(&s_, flags, priority)); }
+  hipError_t create_with_cu_mask(const std::vector<uint32_t>& mask) { release(); return made(hipExtStreamCreateWithCUMask(&s_, (uint32_t)mask.size(), mask.data())); }
+
+ private:
+  hipError_t made(hipError_t e) {
+    if (e != hipSuccess) s_ = nullptr;
+    return e;
+  }
+  hipStream_t s_ = nullptr;
+};
+
+// DevBuf's twin for pinned host memory (hipHostMalloc): ensure() grows and never shrinks, the old contents are gone, and the caller has
+// drained what may still read or write the old block.
+template <typename T>
+class PinnedBuf {
+ public:
+  PinnedBuf() = default;
+  PinnedBuf(PinnedBuf&& b) noexcept : p_(b.p_), n_(b.n_) { b.p_ = nullptr; b.n_ = 0; }
+  PinnedBuf& operator=(PinnedBuf&& b) noexcept {
+    if (this != &b) { release(); p_ = b.p_; n_ = b.n_; b.p_ = nullptr; b.n_ = 0; }
+    return *this;
+  }
+  ~PinnedBuf() { release(); }
+  operator T*() const { return p_; }
+  size_t size() const { return n_; }
+  void release() {
+    if (p_) (void)hipHostFree(p_);
+    p_ = nullptr; n_ = 0;
+  }
+  int ensure(cfear_ctx* ctx, size_t count, const char* what) {
+    if (count <= n_) return CFEAR_OK;
+    release();
+    if (hipHostMalloc(reinterpret_cast<void**>(&p_), sizeof(T) * count, hipHostMallocDefault) != hipSuccess) { p_ = nullptr; return cfear_fail(ctx, CFEAR_ERR_NOMEM, what); }
+    n_ = count;
+    return CFEAR_OK;
+  }
+
+ private:
+  T* p_ = nullptr;
+  size_t n_ = 0;
+};
+
+// Members are destroyed last first: the pinned blocks and the events, then the context's own stream, then the device buffers above them.
 struct cfear_ctx {
   int device = 0;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
+  hipStream_t stream = nullptr;  // the caller's, or own_stream (below)
   cfear_params par;
   int A = 0, R = 0;
   std::string err;
@@ -64,7 +157,6 @@ struct cfear_ctx {
   // staging for the host entry points (these and the three below grow and never shrink)
   DevBuf<uint8_t> d_polar;
   DevBuf<uint32_t> d_slots;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
   DevBuf<unsigned char> d_scratch;  // scratch for the per-call feature / registration kernels
   DevBuf<int> d_cfar_rows;          // row counts / bases of cfear_filter_cfar_batch_device
   struct cfear_cfar_grid* cfar_grid = nullptr;  // the plan and tables of the last cfear_filter_cfar_grid_device call (kept while the next call's dets / source equal them)
@@ -91,13 +183,13 @@ struct cfear_ctx {
   std::vector<std::pair<size_t, void*>> pool;
   size_t pool_bytes = 0;
   std::vector<std::pair<size_t, void*>> hpool;  // ... and the pinned host blocks of the clouds' mirrors
+  Stream own_stream;  // the stream of a context that was given none (a caller's stream is never destroyed)
+  Event ev0, ev1;     // cfear_time_kstrongest (timing events)
   // pinned host staging of the per-call entry points: downloads that complete with ONE synchronisation, registration arguments in one copy
-  unsigned char* h_stage = nullptr;
-  size_t h_stage_bytes = 0;
+  PinnedBuf<unsigned char> h_stage;
   // pinned staging of one polar image for callers that hand over pageable memory (cfear_upload_image), and the event after its last copy
-  unsigned char* h_img = nullptr;
-  size_t h_img_bytes = 0;
-  hipEvent_t ev_img = nullptr;
+  PinnedBuf<unsigned char> h_img;
+  Event ev_img;
   bool ev_img_pending = false;
 };
 

@@ -1,5 +1,7 @@
-// odometry_obj.h -- the batched odometry object (cfear_odometry) and the few helpers that more than one translation unit needs: pipeline.hip
-// (creation, the step, replay and reading routes) and odometry_seq.hip (the per-sequence configuration: setters, getters, the device table).
+// odometry_obj.h -- the batched odometry object (cfear_odometry) and the few helpers that more than one translation unit needs:
+// pipeline.hip (the kernels, the launch layer that names them, the scan and scratch layouts, the reading, surface, cov-sampling and
+// keyframe routes), odometry_run.hip (the object's life: creation, reset, destruction, the steps, the profile, the replay) and
+// odometry_seq.hip (the per-sequence configuration: setters, getters, the device table). The latter two hold no kernel.
 #pragma once
 #include <memory>
 
@@ -10,6 +12,33 @@
 
 struct cfear_cfar_grid_delete { void operator()(cfear_cfar_grid* g) const { cfear_cfar_grid_destroy(g); } };
 typedef std::unique_ptr<cfear_cfar_grid, cfear_cfar_grid_delete> cfear_cfar_grid_ptr;
+
+// The timing events of a profiled object: created in blocks of 1024 outside any timed region (cfear_odometry_profile; a run that outlasts
+// them grows the pool where it stands), handed out in order, all of them free again after reset().
+struct EventPool {
+  std::vector<Event> events;
+  size_t used = 0;
+  int grow(cfear_ctx* ctx) {
+    for (int i = 0; i < 1024; i++) {
+      Event e;
+      CFEAR_TRY(e.ensure(ctx, hipEventDefault, "hipEventCreate(&e)"));
+      events.push_back(std::move(e));
+    }
+    return CFEAR_OK;
+  }
+  // the next event, appended to `list` and recorded on `st`
+  int take(cfear_ctx* ctx, hipStream_t st, std::vector<hipEvent_t>& list) {
+    if (used == events.size()) CFEAR_TRY(grow(ctx));
+    hipEvent_t e = events[used++];
+    list.push_back(e);
+    CFEAR_HIP_CHECK(ctx, hipEventRecord(e, st));
+    return CFEAR_OK;
+  }
+  void reset() { used = 0; }
+};
+
+// Members are destroyed last first, and the order below is chosen for that: the events (the last block), then the streams, then the
+// device buffers and the detectors' grid. cfear_odometry_destroy drains the streams and takes them out of the context's list first.
 
 struct cfear_odometry {
   int B = 0, nslots = 0, cap_points = 0, cap_cells = 0, pair_cap = 0;
@@ -38,13 +67,9 @@ struct cfear_odometry {
   DevBuf<int> rp_cfar_rows;      // ... of a chunk (the replay stream runs one filter at a time)
   // cfear_odometry_replay_host: chunks of sweeps are copied and filtered on a stream of their own (rp_stream), two chunks
   // in flight (staging + slots double-buffered), while the context stream runs features -> registration sweep after sweep
-  hipStream_t rp_stream = nullptr;
   DevBuf<uint8_t> rp_polar[2];
   DevBuf<uint32_t> rp_slots[2];
-  hipEvent_t rp_filt[2] = {nullptr, nullptr}, rp_used[2] = {nullptr, nullptr};  // chunk filtered / chunk consumed by the odometry kernels
-  hipEvent_t rp_in = nullptr;  // device-resident frames ready on the context stream
   bool rp_used_pending[2] = {false, false};
-  bool rp_ready = false;       // stream + events exist
   int rp_chunk = 0;            // sweeps per chunk the slot buffers are sized for
   int rp_polar_chunk = 0;      // ... and the staging buffers (allocated on the first replay from host memory only)
   DevBuf<cfear_sweep_record> d_records;
@@ -65,17 +90,10 @@ struct cfear_odometry {
   // (so[i]). Different ranges are at different points of their features -> registration chain, so the ragged last round of one
   // kernel is filled with workgroups of another (a features workgroup and a registration workgroup fit a compute unit
   // together), and the filter takes what is left.
-  hipStream_t sf = nullptr;
-  std::vector<hipStream_t> so;
-  hipEvent_t ev_in = nullptr, ev_copied = nullptr;
-  hipEvent_t ev_filt[2] = {nullptr, nullptr};
-  std::vector<hipEvent_t> ev_free[2], ev_done;  // per odometry stream
   bool filt_pending[2] = {false, false};  // ev_filt / ev_free have been recorded at least once
   // profiling: timing events taken from a pool that is created up front (and grown in blocks)
   bool profile = false;
-  std::vector<hipEvent_t> pool;
-  size_t pool_used = 0;
-  std::vector<hipEvent_t> filter_events;  // 2 per profiled filter launch (borrowed from the pool)
+  std::vector<hipEvent_t> filter_events;  // 2 per profiled filter launch (borrowed from the pool, `timers` below)
   std::vector<hipEvent_t> stage_events;   // 3 per profiled step: before features, between, after registration
   // estimate_cov_by_sampling (cfear_odometry_set_cov_sampling): the sampling stage runs after every registration while cov_on
   bool cov_on = false;
@@ -113,6 +131,24 @@ struct cfear_odometry {
   DevBuf<int> d_kf_off;                    // [B][kf_max] a node's first cell in its sequence's cells
   DevBuf<int> d_kf_counts;                 // [B][4] nodes recorded, keyframes dropped, cells used, 0
   DevBuf<double> d_kf_tmot;                // [B][6] the recorder's copy of SeqState::Tmot (KfLog::tmot)
+  // ---- streams (destroyed before everything above) ----
+  Stream sf;               // overlap: the filter's
+  std::vector<Stream> so;  // ... and the odometry streams
+  Stream rp_stream;        // the replay's copies and filters; made by the first replay (replay_ensure), with its events
+  std::vector<hipStream_t> streams() const {  // those that exist: what the context is told to wait for, and what is drained before the object goes
+    std::vector<hipStream_t> all;
+    if (sf) all.push_back(sf);
+    for (const Stream& st : so) all.push_back(st);
+    if (rp_stream) all.push_back(rp_stream);
+    return all;
+  }
+  // ---- events (destroyed first) ----
+  Event ev_in, ev_copied;
+  Event ev_filt[2];
+  std::vector<Event> ev_free[2], ev_done;  // per odometry stream
+  Event rp_filt[2], rp_used[2];  // chunk filtered / chunk consumed by the odometry kernels
+  Event rp_in;                   // device-resident frames ready on the context stream
+  EventPool timers;              // what filter_events / stage_events borrow from
 };
 // make everything the internal streams have been given so far visible to the context stream
 static int odo_join(cfear_ctx* ctx, cfear_odometry* o) {
@@ -140,6 +176,34 @@ static cfear_seq_object odo_seq_object(const cfear_ctx* ctx, const cfear_odometr
     const int _rc = (expr);                                                \
     if (_rc != CFEAR_OK) return cfear_fail((ctx), _rc, msg.c_str());       \
   } while (0)
+// ---- pipeline.hip: what odometry_run.hip calls of the launch layer ----
+// the kernel parameters of one odometry step of `o` under the context's current settings
+__attribute__((visibility("hidden"))) OdoParams odo_params(const cfear_ctx* ctx, const cfear_odometry* o);
+// Where a sweep's points come from: the filter's slots, or clouds of `cap` points each with their counts
+struct SweepPoints {
+  const uint32_t* slots = nullptr;
+  const float* xyi = nullptr; int cap = 0; const int* counts = nullptr;
+  static SweepPoints of_slots(const uint32_t* d_slots) { SweepPoints S; S.slots = d_slots; return S; }
+  static SweepPoints of_clouds(const float* d_xyi, int cap, const int* d_counts) { SweepPoints S; S.xyi = d_xyi; S.cap = cap; S.counts = d_counts; return S; }
+};
+// one sweep of `count` sequences from P.seq0 on, enqueued on `st`: features, then registration with the stages behind it. timed: three
+// events of the profile around the two (stage_events); consumed: recorded once features has read the points (null: nothing is)
+__attribute__((visibility("hidden"))) int odo_launch_sweep(cfear_ctx* ctx, cfear_odometry* o, const OdoParams& P, const SweepPoints& src, int count, hipStream_t st,
+                                                           bool timed, hipEvent_t consumed = nullptr);
+// the CA-CFAR stage of n_steps sweeps of every sequence into clouds of o->cap_points points each, [step][sequence]
+__attribute__((visibility("hidden"))) int odo_launch_cfar(cfear_ctx* ctx, cfear_odometry* o, const uint8_t* d_polar, int n_steps, float* d_xyi, int* d_counts, int* d_rows,
+                                                          hipStream_t st);
+// has the object the shape the context's parameters ask for? (k_strongest / submap_scan_size / the filter cannot change under an object)
+__attribute__((visibility("hidden"))) int odo_shape_check(cfear_ctx* ctx, const cfear_odometry* o, const char* what);
+// after a synchronising read: an overflow of cells or points since the last one is reported, loudly, as `what`
+__attribute__((visibility("hidden"))) int odo_capacity_check(cfear_ctx* ctx, cfear_odometry* o, const char* what);
+// the scan and scratch layouts of an object whose capacities are set: bytes of one scan slot and of one sequence's scratch block ...
+__attribute__((visibility("hidden"))) void odo_block_bytes(const cfear_odometry* o, size_t* scan_bytes, size_t* scratch_bytes);
+// ... and the headers of all of them, built on the host and uploaded ("odometry state upload")
+__attribute__((visibility("hidden"))) int odo_upload_headers(cfear_ctx* ctx, cfear_odometry* o, size_t scratch_bytes);
+// ---- odometry_run.hip: what the keyframe route of pipeline.hip calls ----
+__attribute__((visibility("hidden"))) int odo_ensure_flags(cfear_ctx* ctx, cfear_odometry* o);
+__attribute__((visibility("hidden"))) int odo_kf_clear(cfear_ctx* ctx, cfear_odometry* o);
 // odometry_seq.hip: cfear_set_params since the device table was built - the rows are checked against the new parameters and the table follows them
 __attribute__((visibility("hidden"))) int odo_seq_resync(cfear_ctx* ctx, cfear_odometry* o, const char* what);
 // before a step / replay / surface call: cfear_set_params since the table was built? The rows are checked against the new parameters

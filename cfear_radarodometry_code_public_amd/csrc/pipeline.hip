@@ -10,7 +10,8 @@
 //                          unit so that the serial Levenberg-Marquardt controllers of different sequences overlap):
 //                          association, robust normal equations, LM, outer loop, keyframe logic
 // Per-call entry points (clouds, scans, Register, GetCost, cost-sampling covariance) use the same device code.
-// The object itself (struct cfear_odometry) is odometry_obj.h's; its per-sequence configuration - the setters and getters of rows, source
+// The object itself (struct cfear_odometry) is odometry_obj.h's; its life - creation, reset, destruction, the step entry points, the profile
+// and the replay - is odometry_run.hip's, over the launch layer of this file (odo_params, odo_launch_sweep, odo_launch_cfar); its per-sequence configuration - the setters and getters of rows, source
 // map, shapes, detectors and fuser options, the device table (seq_table_upload) and odo_seq_sync's re-check - lives in odometry_seq.hip
 // over seq_config.h. This file reads the configuration through o->cfg (effective(), sources(), other_cost()) and never writes it.
 #include <math.h>
@@ -21,6 +22,7 @@
 #include <new>
 
 #include "odometry_obj.h"
+#include "odometry_plan.h"
 #include "cov_sampling_dev.h"
 #include "keyframe_dev.h"
 
@@ -492,29 +494,8 @@ static KfLog odo_kf_log(const cfear_odometry* o) {
   L.nodes = o->d_kf_nodes; L.cells = o->d_kf_cells; L.cell_off = o->d_kf_off; L.counts = o->d_kf_counts; L.tmot = o->d_kf_tmot;
   return L;
 }
-// a timing event from the pool, recorded on `st`
-static int odo_grow_pool(cfear_ctx* ctx, cfear_odometry* o) {
-  for (int i = 0; i < 1024; i++) {
-    hipEvent_t e = nullptr;
-    CFEAR_HIP_CHECK(ctx, hipEventCreate(&e));
-    o->pool.push_back(e);
-  }
-  return CFEAR_OK;
-}
-static int odo_timed_event(cfear_ctx* ctx, cfear_odometry* o, std::vector<hipEvent_t>& list, hipStream_t st) {
-  if (o->pool_used == o->pool.size()) CFEAR_TRY(odo_grow_pool(ctx, o));
-  hipEvent_t e = o->pool[o->pool_used++];
-  list.push_back(e);
-  CFEAR_HIP_CHECK(ctx, hipEventRecord(e, st));
-  return CFEAR_OK;
-}
-static int odo_capacity_check(cfear_ctx* ctx, cfear_odometry* o, const char* what);
-
-// has the object the shape the context's parameters ask for? (k_strongest / submap_scan_size / the filter cannot change under an object)
-static int odo_shape_check(cfear_ctx* ctx, const cfear_odometry* o, const char* what);
-
 // the kernel parameters of one odometry step of `o` under the context's current settings
-static OdoParams odo_params(const cfear_ctx* ctx, const cfear_odometry* o) {
+OdoParams odo_params(const cfear_ctx* ctx, const cfear_odometry* o) {
   OdoParams OP;
   OP.fp = feature_params(ctx); OP.rp = reg_params(ctx);
   OP.A = ctx->A; OP.k = ctx->par.k_strongest; OP.compensate = ctx->par.compensate; OP.ccw = ctx->par.radar_ccw;
@@ -618,42 +599,80 @@ static void launch_register_step(const OdoParams& P, int count, hipStream_t st, 
   // same stream, so the sub-batches of the overlap mode need nothing extra
   if (o->kf_what) cfear_launch_keyframe_record(odo_kf_log(o), P, count, st, o->d_states, o->d_cov_work);
 }
-// the features stage of a sweep: `count` sequences from P.seq0 on, from the filter's slots ...
-static void launch_features_step(const cfear_ctx* ctx, const cfear_odometry* o, const OdoParams& P, const uint32_t* d_slots, int count, hipStream_t st) {
-  if (P.phase_times)
-    hipLaunchKernelGGL(features_step_kernel<true>, dim3(count), dim3(BLOCK_F), 0, st, d_slots, ctx->d_trig, P, o->d_states, nullptr, o->d_scratch_hdr);
+// one sweep of `count` sequences from P.seq0 on (odometry_obj.h): the features stage from the filter's slots or from clouds on the device, then the
+// registration stage and what runs behind it
+int odo_launch_sweep(cfear_ctx* ctx, cfear_odometry* o, const OdoParams& P, const SweepPoints& src, int count, hipStream_t st, bool timed, hipEvent_t consumed) {
+  if (timed) CFEAR_TRY(o->timers.take(ctx, st, o->stage_events));
+  if (!src.slots)
+    hipLaunchKernelGGL(features_cloud_step_kernel, dim3(count), dim3(BLOCK_F), 0, st, src.xyi, src.cap, src.counts, P, o->d_states, o->d_scratch_hdr);
+  else if (P.phase_times)
+    hipLaunchKernelGGL(features_step_kernel<true>, dim3(count), dim3(BLOCK_F), 0, st, src.slots, ctx->d_trig, P, o->d_states, nullptr, o->d_scratch_hdr);
   else
-    hipLaunchKernelGGL(features_step_kernel<false>, dim3(count), dim3(BLOCK_F), 0, st, d_slots, ctx->d_trig, P, o->d_states, nullptr, o->d_scratch_hdr);
+    hipLaunchKernelGGL(features_step_kernel<false>, dim3(count), dim3(BLOCK_F), 0, st, src.slots, ctx->d_trig, P, o->d_states, nullptr, o->d_scratch_hdr);
+  if (consumed) {  // (the overlap mode's ev_free: the slot buffer may be filtered into again)
+    const hipError_t e = hipEventRecord(consumed, st);
+    if (e != hipSuccess) return cfear_fail(ctx, CFEAR_ERR_HIP, "hipEventRecord(o->ev_free[buf][i], so)", e);
+  }
+  if (timed) CFEAR_TRY(o->timers.take(ctx, st, o->stage_events));
+  launch_register_step(P, count, st, o);
+  if (timed) CFEAR_TRY(o->timers.take(ctx, st, o->stage_events));
+  return CFEAR_OK;
 }
-// ... or from clouds on the device
-static void launch_features_cloud_step(const cfear_odometry* o, const OdoParams& P, const float* d_xyi, int cap, const int* d_counts, int count, hipStream_t st) {
-  hipLaunchKernelGGL(features_cloud_step_kernel, dim3(count), dim3(BLOCK_F), 0, st, d_xyi, cap, d_counts, P, o->d_states, o->d_scratch_hdr);
-}
-// features -> registration of one sweep of every sequence on `st` (the replay's non-persistent route)
-static void odo_launch_sweep(const cfear_ctx* ctx, cfear_odometry* o, const OdoParams& P, const uint32_t* d_slots, int seq_count, hipStream_t st) {
-  launch_features_step(ctx, o, P, d_slots, seq_count, st);
-  launch_register_step(P, seq_count, st, o);
-}
-static void odo_launch_sweep_cloud(cfear_odometry* o, const OdoParams& P, const float* d_xyi, int cap, const int* d_counts, int seq_count, hipStream_t st) {
-  launch_features_cloud_step(o, P, d_xyi, cap, d_counts, seq_count, st);
-  launch_register_step(P, seq_count, st, o);
-}
-static int odo_cfar_points(const cfear_ctx* ctx) { return ctx->par.cfar_max_points > 0 ? ctx->par.cfar_max_points : 32768; }
-static int odo_shape_check(cfear_ctx* ctx, const cfear_odometry* o, const char* what) {
+int odo_shape_check(cfear_ctx* ctx, const cfear_odometry* o, const char* what) {
   bool ok = o->nslots == ctx->par.submap_scan_size + 1 && o->filter == ctx->par.filter_type;
-  if ((ctx->tune_nn_tie == 2 && !o->with_kd) || (ctx->tune_nn_tie != 0 && o->pair_cap < 8192)) ok = false;  // the tie rule was switched after the object was created
+  if ((ctx->tune_nn_tie == 2 && !o->with_kd) || (ctx->tune_nn_tie != 0 && o->pair_cap < 8192 /* cfear_odo_capacities */)) ok = false;  // the tie rule was switched after the object was created
   if (ctx->tune_voxel_order != 0) ok = false;  // per-call scans only (cfear_odometry_create refuses it too)
-  if (ok && o->cap_points == (o->filter == CFEAR_FILTER_CACFAR ? odo_cfar_points(ctx) : ctx->A * ctx->par.k_strongest)) return CFEAR_OK;
+  if (ok && o->cap_points == cfear_odo_cap_points(o->filter == CFEAR_FILTER_CACFAR, ctx->A, ctx->par.k_strongest, ctx->par.cfar_max_points)) return CFEAR_OK;
   char msg[320];
   snprintf(msg, sizeof(msg), "%s: submap_scan_size / k_strongest / filter_type changed after odometry_create, or a parity mode (cfear_tune NN_TIE_RULE / VOXEL_ORDER) was switched under the object", what);
   return cfear_fail(ctx, CFEAR_ERR_INVALID, msg);
 }
 // the CA-CFAR stage of n_steps sweeps of every sequence (radar_driver.cpp:52-56) into clouds of o->cap_points points each, [step][sequence]: the
 // context's detector over one image per sequence, or the sequences' own over the sources they share
-static int odo_launch_cfar(cfear_ctx* ctx, cfear_odometry* o, const uint8_t* d_polar, int n_steps, float* d_xyi, int* d_counts, int* d_rows, hipStream_t st) {
+int odo_launch_cfar(cfear_ctx* ctx, cfear_odometry* o, const uint8_t* d_polar, int n_steps, float* d_xyi, int* d_counts, int* d_rows, hipStream_t st) {
   if (o->det_grid) return cfear_launch_cfar_grid(ctx, o->det_grid.get(), d_polar, n_steps, ctx->par.cfar_max_distance, d_xyi, o->cap_points, d_counts, d_rows, st);
   return cfear_launch_cfar_batch(ctx, d_polar, n_steps * o->B, ctx->par.cfar_window_size, ctx->par.cfar_nb_guard_cells, ctx->par.cfar_false_alarm_rate,
                                  ctx->par.cfar_max_distance, d_xyi, o->cap_points, d_counts, d_rows, st);
+}
+// after a synchronisation of the context stream: has any scan of this object overflowed its cell capacity (CFEAR_TUNE_MAX_CELLS)?
+int odo_capacity_check(cfear_ctx* ctx, cfear_odometry* o, const char* what) {
+  if (!o->d_flags) return CFEAR_OK;  // sized for every filtered point: cannot happen
+  int f = 0;
+  CFEAR_HIP_CHECK(ctx, hipMemcpy(&f, o->d_flags, sizeof(int), hipMemcpyDeviceToHost));
+  if (f & 2) {
+    char msg[320];
+    snprintf(msg, sizeof(msg), "%s: a sweep's cloud had more points than the %d this object is sized for (cfear_params.cfar_max_points with filter_type CA-CFAR; the "
+             "capacity argument of cfear_odometry_step_cloud_device): the first %d in (azimuth, range) order were kept, the results of that sequence are those "
+             "of a truncated cloud", what, o->cap_points, o->cap_points);
+    return cfear_fail(ctx, CFEAR_ERR_CAPACITY, msg);
+  }
+  if (f & 1) {
+    char msg[400];
+    snprintf(msg, sizeof(msg), "%s: a scan produced more than %d oriented surface points (%s): its first %d were kept, the results of that sequence are those of a "
+             "truncated scan", what, o->cap_cells, ctx->tune_max_cells > 0 ? "cfear_tune CFEAR_TUNE_MAX_CELLS of this object" :
+             "the default of objects with more than 7 keyframes: min(points per scan, 4096); raise it with cfear_tune CFEAR_TUNE_MAX_CELLS before cfear_odometry_create", o->cap_cells);
+    return cfear_fail(ctx, CFEAR_ERR_CAPACITY, msg);
+  }
+  return CFEAR_OK;
+}
+// the scan and scratch layouts of an object (odometry_obj.h): the bytes of one scan slot and of one sequence's scratch block ...
+void odo_block_bytes(const cfear_odometry* o, size_t* scan_bytes, size_t* scratch_bytes) {
+  *scan_bytes = scan_layout(o->cap_points, o->cap_cells, false, o->with_kd).total;
+  *scratch_bytes = scratch_layout(o->cap_points, o->pair_cap).total;
+}
+// ... and their headers into d_scans (o->scan_stride apart) and d_scratch_hdr
+int odo_upload_headers(cfear_ctx* ctx, cfear_odometry* o, size_t scratch_bytes) {
+  const int B = o->B;
+  std::vector<BlockScratch> hdrs((size_t)B);
+  std::vector<ScanDev> scan_hdrs((size_t)B * o->nslots);  // all headers built on the host, uploaded with one strided copy
+  for (int q = 0; q < B; q++) {
+    for (int j = 0; j < o->nslots; j++)
+      scan_hdrs[(size_t)q * o->nslots + j] = scan_header(o->d_scans + o->scan_stride * ((size_t)q * o->nslots + j), o->cap_points, o->cap_cells, false, o->with_kd);
+    hdrs[q] = scratch_header(o->d_scratch + scratch_bytes * (size_t)q, o->cap_points, o->pair_cap);
+  }
+  bool ok = hipMemcpy2D(o->d_scans, o->scan_stride, scan_hdrs.data(), sizeof(ScanDev), sizeof(ScanDev), scan_hdrs.size(), hipMemcpyHostToDevice) == hipSuccess;
+  ok = ok && hipMemcpy(o->d_scratch_hdr, hdrs.data(), sizeof(BlockScratch) * hdrs.size(), hipMemcpyHostToDevice) == hipSuccess;
+  return ok ? CFEAR_OK : cfear_fail(ctx, CFEAR_ERR_HIP, "odometry state upload");
 }
 
 // What a per-call problem (Register / GetCost / GetSurface) keeps on the device behind the working arrays of the context scratch
@@ -1052,7 +1071,7 @@ static int register_impl(cfear_ctx* ctx, cfear_scan* const* scans, int n, double
   // arguments and results travel through pinned staging laid out like the device tail: one copy each way and one synchronisation per
   // registration (round 6; it was three small pageable copies in, three out)
   CFEAR_TRY(cfear_ensure_hstage(ctx, sizeof(CallTail)));
-  CallTail* h = reinterpret_cast<CallTail*>(ctx->h_stage);
+  CallTail* h = reinterpret_cast<CallTail*>(static_cast<unsigned char*>(ctx->h_stage));
   const size_t in_bytes = offsetof(CallTail, sum);
   memset(h, 0, in_bytes);
   memcpy(h->ptrs, pb.ptrs, sizeof(void*) * n);
@@ -1372,587 +1391,10 @@ int cfear_cov_by_sampling(cfear_ctx* ctx, cfear_scan* const* scans, int n, const
   return CFEAR_OK;
 }
 
-// ---- batched odometry --------------------------------------------------------------------------
-void cfear_odometry_destroy(cfear_ctx* ctx, cfear_odometry* o) {
-  if (!o) return;
-  if (ctx) {
-    (void)hipSetDevice(ctx->device);
-    std::vector<hipStream_t> all = o->so;  // the object's streams: drained, then no longer the context's to wait for
-    all.push_back(o->sf);
-    all.push_back(o->rp_stream);
-    for (hipStream_t st : all) {
-      if (!st) continue;
-      (void)hipStreamSynchronize(st);
-      const auto it = std::find(ctx->aux_streams.begin(), ctx->aux_streams.end(), st);
-      if (it != ctx->aux_streams.end()) ctx->aux_streams.erase(it);
-    }
-    (void)hipStreamSynchronize(ctx->stream);
-  }
-  for (hipEvent_t e : {o->rp_filt[0], o->rp_filt[1], o->rp_used[0], o->rp_used[1], o->rp_in}) if (e) (void)hipEventDestroy(e);
-  if (o->rp_stream) (void)hipStreamDestroy(o->rp_stream);
-  for (hipEvent_t e : o->pool) (void)hipEventDestroy(e);
-  for (hipEvent_t e : {o->ev_in, o->ev_copied, o->ev_filt[0], o->ev_filt[1]}) if (e) (void)hipEventDestroy(e);
-  for (auto* v : {&o->ev_free[0], &o->ev_free[1], &o->ev_done}) for (hipEvent_t e : *v) if (e) (void)hipEventDestroy(e);
-  if (o->sf) (void)hipStreamDestroy(o->sf);
-  for (hipStream_t st : o->so) if (st) (void)hipStreamDestroy(st);
-  delete o;  // (and with it the device buffers and the detectors' grid)
-}
-
-// an empty keyframe log: no nodes, no drops, and the recorder's copy of Tmot the identity the states start with
-static int odo_kf_clear(cfear_ctx* ctx, cfear_odometry* o) {
-  std::vector<double> tm(6 * (size_t)o->B, 0.0);
-  for (int q = 0; q < o->B; q++) tm[6 * (size_t)q] = tm[6 * (size_t)q + 3] = 1.0;
-  CFEAR_HIP_CHECK(ctx, hipMemsetAsync(o->d_kf_counts, 0, sizeof(int) * 4 * (size_t)o->B, ctx->stream));
-  CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(o->d_kf_tmot, tm.data(), sizeof(double) * tm.size(), hipMemcpyHostToDevice, ctx->stream));
-  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // (tm is read until here)
-  return CFEAR_OK;
-}
-
-int cfear_odometry_reset(cfear_ctx* ctx, cfear_odometry* o) {
-  if (!ctx || !o) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_reset: bad argument");
-  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  CFEAR_TRY(odo_join(ctx, o));
-  std::vector<SeqState> st((size_t)o->B);
-  for (auto& s : st) {
-    memset(&s, 0, sizeof(s));
-    s.T_prev.l0 = s.T_prev.l3 = 1; s.Tmot.l0 = s.Tmot.l3 = 1; s.Tcurrent.l0 = s.Tcurrent.l3 = 1;  // odometrykeyframefuser.cpp:34-38
-  }
-  CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(o->d_states, st.data(), sizeof(SeqState) * st.size(), hipMemcpyHostToDevice, ctx->stream));
-  CFEAR_HIP_CHECK(ctx, hipMemsetAsync(o->d_summaries, 0, sizeof(cfear_reg_summary) * (size_t)o->B, ctx->stream));
-  CFEAR_HIP_CHECK(ctx, hipMemsetAsync(o->d_poses_out, 0, sizeof(double) * 3 * (size_t)o->B, ctx->stream));
-  CFEAR_HIP_CHECK(ctx, hipMemsetAsync(o->d_cov_work, 0, sizeof(double) * 36 * (size_t)o->B, ctx->stream));
-  if (o->d_flags) CFEAR_HIP_CHECK(ctx, hipMemsetAsync(o->d_flags, 0, sizeof(int) * ((size_t)o->B + 1), ctx->stream));
-  if (o->kf_what) CFEAR_TRY(odo_kf_clear(ctx, o));  // (the setting stays, the log starts again at keyframe 0)
-  o->order_ready = false;
-  o->surf_ready = false;
-  o->sweeps = 0;  // (the parameter table, the source map and the fuser options stay)
-  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  return CFEAR_OK;
-}
-
-// the overflow flags of `o`, all clear: created with the object when a scan can overflow its cells or the filter's clouds their points, by
-// cfear_odometry_step_cloud_device otherwise (the caller's clouds may) when it is first used
-static int odo_ensure_flags(cfear_ctx* ctx, cfear_odometry* o) {
-  if (o->d_flags) return CFEAR_OK;
-  CFEAR_TRY(o->d_flags.ensure(ctx, (size_t)o->B + 1, "hipMalloc odometry state"));
-  CFEAR_HIP_CHECK(ctx, hipMemsetAsync(o->d_flags, 0, sizeof(int) * o->d_flags.size(), ctx->stream));
-  return CFEAR_OK;
-}
-// ... and the [B] records of the registrations (cost sampling and surface recording share them), all 'nothing recorded'. The streams are idle.
+// ---- batched odometry: the object's life is odometry_run.hip's; here the routes that read it or run kernels of their own ----------
+// the [B] records of the registrations (cost sampling and surface recording share them), all 'nothing recorded'. The streams are idle.
 static int odo_ensure_cov_ctx(cfear_ctx* ctx, cfear_odometry* o, const char* what) {
   return o->d_cov_ctx.ensure(ctx, (size_t)o->B, what, true);
-}
-// the device memory every object has, sized by the fields cfear_odometry_create has set (scratch_bytes: of one sequence's scratch block)
-static int odo_alloc_state(cfear_ctx* ctx, cfear_odometry* o, size_t scratch_bytes) {
-  const size_t B = (size_t)o->B;
-  const char* what = "hipMalloc odometry state";
-  CFEAR_TRY(o->d_scans.ensure(ctx, o->scan_stride * B * o->nslots, what));
-  CFEAR_TRY(o->d_scratch.ensure(ctx, scratch_bytes * B, what, true));  // dense voxel tables start all-zero
-  CFEAR_TRY(o->d_scratch_hdr.ensure(ctx, B, what));
-  CFEAR_TRY(o->d_states.ensure(ctx, B, what));
-  CFEAR_TRY(o->d_cov_work.ensure(ctx, 36 * B, what));
-  CFEAR_TRY(o->d_summaries.ensure(ctx, B, what));
-  CFEAR_TRY(o->d_poses_out.ensure(ctx, 3 * B, what));
-  if (o->filter == CFEAR_FILTER_CACFAR) {
-    CFEAR_TRY(o->d_cloud.ensure(ctx, 3 * B * o->cap_points, what));
-    CFEAR_TRY(o->d_cloud_n.ensure(ctx, B, what));
-    CFEAR_TRY(o->d_cfar_rows.ensure(ctx, cfear_cfar_scratch_ints(ctx, B), what));
-  } else {
-    for (auto& slots : o->d_slots) CFEAR_TRY(slots.ensure(ctx, B * o->cap_points, what));
-  }
-  if (o->cap_cells < o->cap_points || o->filter == CFEAR_FILTER_CACFAR) CFEAR_TRY(odo_ensure_flags(ctx, o));
-  if (ctx->tune_reg_order && o->B >= 2) {
-    CFEAR_TRY(o->d_order.ensure(ctx, B, what));
-    CFEAR_TRY(o->d_work.ensure(ctx, B, what, true));
-  }
-  return CFEAR_OK;
-}
-
-int cfear_odometry_create(cfear_ctx* ctx, int n_sequences, cfear_odometry** out) {
-  if (!ctx || !out || n_sequences <= 0) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_create: bad argument");
-  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  *out = nullptr;
-  cfear_odometry* o = new (std::nothrow) cfear_odometry();
-  if (!o) return cfear_fail(ctx, CFEAR_ERR_NOMEM, "odometry alloc");
-  if (ctx->tune_voxel_order != 0) {
-    delete o;
-    return cfear_fail(ctx, CFEAR_ERR_UNSUPPORTED, "odometry_create: cfear_tune VOXEL_ORDER = 1 (PCL <= 1.9's std::sort order) needs a host round trip per scan: per-call scans only "
-                      "(cfear_scan_create; the mirror classes of cfear_host.hpp use it)");
-  }
-  const int B = n_sequences, s = ctx->par.submap_scan_size;
-  o->filter = ctx->par.filter_type;
-  o->large_kernel = ctx->tune_large_kernel;
-  { int ncu = 0; if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->device) == hipSuccess && ncu > 0) o->n_cus = ncu; }
-  o->B = B; o->nslots = s + 1; o->cap_points = o->filter == CFEAR_FILTER_CACFAR ? odo_cfar_points(ctx) : ctx->A * ctx->par.k_strongest;
-  // cells per scan the blocks are sized for: cfear_tune MAX_CELLS; by default every filtered point (cannot overflow) - except for a submap of
-  // more than seven keyframes, where that default would be hundreds of MB per sequence (280 MB at submap_scan_size 50, k 40) for scans of a
-  // few hundred to ~1500 cells: 4096 then (launch/oxford_demo:62-71 works without a tune call; an overflow is loud, CFEAR_ERR_CAPACITY)
-  o->cap_cells = ctx->tune_max_cells > 0 ? std::min(ctx->tune_max_cells, o->cap_points) : (s > 7 ? std::min(o->cap_points, 4096) : o->cap_points);
-  // residual blocks of a registration <= keyframes x cells of the current scan (one match per source cell and keyframe,
-  // n_scan_normal.cpp:242,258); the association parks four results per source cell in the same scratch
-  o->pair_cap = std::max(s, 4) * o->cap_cells;
-  if (ctx->tune_nn_tie != 0) o->pair_cap = std::max(o->pair_cap, 8192);  // room for the kd descent's per-thread stacks (associate_pair_rule, 512-thread kernels)
-  o->with_kd = ctx->tune_nn_tie == 2;
-  const ScanLayout SL = scan_layout(o->cap_points, o->cap_cells, false, o->with_kd);
-  const ScratchLayout WL = scratch_layout(o->cap_points, o->pair_cap);
-  {  // refuse what cannot fit with a message that names the numbers (a bare NOMEM after gigabytes of partial allocations helps nobody)
-    size_t free_b = 0, total_b = 0;
-    const size_t per_seq = SL.total * (size_t)o->nslots + WL.total + sizeof(uint32_t) * 2 * (size_t)o->cap_points + sizeof(SeqState) + 4096;
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && per_seq * (size_t)B > free_b) {
-      char msg[512];
-      snprintf(msg, sizeof(msg), "odometry_create: %d sequences x %.1f MB (%d scan slots of %.2f MB for %d points / %d cells each + %.1f MB of scratch for %d residual "
-               "blocks) = %.1f GB, %.1f GB free: at most %zu sequences fit - or size the scans for fewer cells (cfear_tune CFEAR_TUNE_MAX_CELLS, now %d)",
-               B, per_seq / 1048576.0, o->nslots, SL.total / 1048576.0, o->cap_points, o->cap_cells, WL.total / 1048576.0, o->pair_cap,
-               per_seq * (double)B / 1073741824.0, free_b / 1073741824.0, free_b / per_seq, o->cap_cells);
-      delete o;
-      return cfear_fail(ctx, CFEAR_ERR_NOMEM, msg);
-    }
-  }
-  o->scan_stride = SL.total;
-  const int arc = odo_alloc_state(ctx, o, WL.total);
-  if (arc != CFEAR_OK) { cfear_odometry_destroy(ctx, o); return arc; }
-  std::vector<BlockScratch> hdrs((size_t)B);
-  std::vector<ScanDev> scan_hdrs((size_t)B * o->nslots);  // all headers built on the host, uploaded with one strided copy
-  for (int q = 0; q < B; q++) {
-    for (int j = 0; j < o->nslots; j++)
-      scan_hdrs[(size_t)q * o->nslots + j] = scan_header(o->d_scans + SL.total * ((size_t)q * o->nslots + j), o->cap_points, o->cap_cells, false, o->with_kd);
-    hdrs[q] = scratch_header(o->d_scratch + WL.total * (size_t)q, o->cap_points, o->pair_cap);
-  }
-  bool ok = hipMemcpy2D(o->d_scans, SL.total, scan_hdrs.data(), sizeof(ScanDev), sizeof(ScanDev), scan_hdrs.size(), hipMemcpyHostToDevice) == hipSuccess;
-  ok = ok && hipMemcpy(o->d_scratch_hdr, hdrs.data(), sizeof(BlockScratch) * hdrs.size(), hipMemcpyHostToDevice) == hipSuccess;
-  if (!ok) { cfear_odometry_destroy(ctx, o); return cfear_fail(ctx, CFEAR_ERR_HIP, "odometry state upload"); }
-  const int rc = cfear_odometry_reset(ctx, o);
-  if (rc != CFEAR_OK) { cfear_odometry_destroy(ctx, o); return rc; }
-  ok = hipEventCreateWithFlags(&o->ev_copied, hipEventDisableTiming) == hipSuccess;
-  o->overlap = ctx->tune_odo_overlap < 0 ? 0 : (ctx->tune_odo_overlap > 8 ? 8 : ctx->tune_odo_overlap);
-  if (o->overlap > B) o->overlap = B;
-  if (o->filter == CFEAR_FILTER_CACFAR) o->overlap = 0;  // (the filter-ahead streams are the k-strongest filter's)
-  if (ok && o->overlap) {
-    int least = 0, greatest = 0;  // numerically lower = higher priority
-    ok = hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess;
-    // CFEAR_TUNE_FILTER_CUS = F: the filter gets F compute units of its own, the odometry streams the others: the HBM-bound
-    // kernel and the latency-bound ones stop competing for a unit's registers and LDS. What the mask bits select was measured
-    // (tools/cu_mask_probe.py): the unit of masking on this GPU is a group of 8 consecutive bits - any bit set enables the
-    // whole group, 32 groups in all - so F is rounded to groups, and the groups are taken in a spread order (0, 4, 8, ...,
-    // then 2, 6, ..., then the odd ones) so that every quarter of the bit range contributes alike.
-    std::vector<uint32_t> mask_f, mask_o;
-    int ncu = 0;
-    if (ctx->tune_filter_cus > 0 && hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->device) == hipSuccess && ncu >= 16) {
-      const int ngroups = ncu / 8;
-      const int gf = std::max(1, std::min(ngroups - 1, (ctx->tune_filter_cus + 4) / 8));
-      std::vector<int> order;
-      for (int phase : {0, 2, 1, 3}) for (int g = phase; g < ngroups; g += 4) order.push_back(g);
-      mask_f.assign((size_t)(ncu + 31) / 32, 0u); mask_o.assign((size_t)(ncu + 31) / 32, 0u);
-      for (int r = 0; r < ngroups; r++) {
-        std::vector<uint32_t>& m = r < gf ? mask_f : mask_o;
-        for (int b = 0; b < 8; b++) { const int i = order[(size_t)r] * 8 + b; m[(size_t)i / 32] |= 1u << (i % 32); }
-      }
-      for (int i = ngroups * 8; i < ncu; i++) mask_o[(size_t)i / 32] |= 1u << (i % 32);
-    }
-    if (!mask_f.empty()) ok = ok && hipExtStreamCreateWithCUMask(&o->sf, (uint32_t)mask_f.size(), mask_f.data()) == hipSuccess;
-    else ok = ok && hipStreamCreateWithPriority(&o->sf, hipStreamNonBlocking, least) == hipSuccess;
-    for (int i = 0; ok && i < o->overlap; i++) {
-      hipStream_t st = nullptr;
-      if (!mask_o.empty()) ok = hipExtStreamCreateWithCUMask(&st, (uint32_t)mask_o.size(), mask_o.data()) == hipSuccess;
-      else ok = hipStreamCreateWithPriority(&st, hipStreamNonBlocking, greatest) == hipSuccess;
-      if (ok) o->so.push_back(st);
-      for (auto* v : {&o->ev_free[0], &o->ev_free[1], &o->ev_done}) {
-        hipEvent_t e = nullptr;
-        ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
-        if (ok) v->push_back(e);
-      }
-    }
-    for (hipEvent_t* e : {&o->ev_in, &o->ev_filt[0], &o->ev_filt[1]})
-      ok = ok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
-  }
-  if (!ok) { cfear_odometry_destroy(ctx, o); return cfear_fail(ctx, CFEAR_ERR_HIP, "odometry stream creation"); }
-  if (o->overlap) { ctx->aux_streams.push_back(o->sf); for (hipStream_t st : o->so) ctx->aux_streams.push_back(st); }
-  *out = o;
-  return CFEAR_OK;
-}
-
-// one sweep of every sequence from clouds on the device, on the context stream
-static int odo_step_clouds(cfear_ctx* ctx, cfear_odometry* o, const float* d_xyi, int capacity, const int* d_counts, bool filter_events) {
-  const OdoParams OP = odo_params(ctx, o);
-  int rc = CFEAR_OK;
-  if (o->profile && !filter_events) {  // (keeps filter_events / stage_events paired per step for the profile readers)
-    if ((rc = odo_timed_event(ctx, o, o->filter_events, ctx->stream)) != CFEAR_OK) return rc;
-    if ((rc = odo_timed_event(ctx, o, o->filter_events, ctx->stream)) != CFEAR_OK) return rc;
-  }
-  if (o->profile && (rc = odo_timed_event(ctx, o, o->stage_events, ctx->stream)) != CFEAR_OK) return rc;
-  launch_features_cloud_step(o, OP, d_xyi, capacity, d_counts, o->B, ctx->stream);
-  if (o->profile && (rc = odo_timed_event(ctx, o, o->stage_events, ctx->stream)) != CFEAR_OK) return rc;
-  launch_register_step(OP, o->B, ctx->stream, o);
-  if (o->profile && (rc = odo_timed_event(ctx, o, o->stage_events, ctx->stream)) != CFEAR_OK) return rc;
-  o->surf_ready = OP.cs.ctx != nullptr;
-  o->step_no++; o->sweeps++;
-  CFEAR_HIP_CHECK(ctx, hipGetLastError());
-  return CFEAR_OK;
-}
-
-int cfear_odometry_step_cloud_device(cfear_ctx* ctx, cfear_odometry* o, const float* d_xyi, int capacity, const int* d_counts) {
-  if (!ctx || !o || !d_xyi || !d_counts || capacity <= 0) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_step_cloud: bad argument");
-  CFEAR_TRY(odo_shape_check(ctx, o, "odometry_step_cloud"));
-  if (!o->cfg.src.empty())
-    return cfear_fail(ctx, CFEAR_ERR_UNSUPPORTED, "odometry_step_cloud: the object has a source map (cfear_odometry_set_sequence_sources), which the cloud route does not "
-                      "read - it takes one cloud per sequence; clear the map (NULL) first");
-  if (o->cfg.dets_mapped)
-    return cfear_fail(ctx, CFEAR_ERR_UNSUPPORTED, "odometry_step_cloud: the object has per-sequence detectors with a source map (cfear_odometry_set_sequence_detectors), "
-                      "which the cloud route does not read - it takes one cloud per sequence; clear them (NULL) first");
-  for (size_t q = 0; q < o->cfg.rows.size(); q++)
-    if (o->cfg.rows[q].k_strongest != ctx->par.k_strongest) {
-      char msg[256];
-      snprintf(msg, sizeof(msg), "odometry_step_cloud: row %d of the object's table has k_strongest = %d, the context %d - a cloud has no slots to take the k strongest "
-               "of; the cloud route runs with rows of the context's k_strongest only", (int)q, o->cfg.rows[q].k_strongest, ctx->par.k_strongest);
-      return cfear_fail(ctx, CFEAR_ERR_UNSUPPORTED, msg);
-    }
-  CFEAR_TRY(odo_seq_sync(ctx, o, "odometry_step_cloud"));
-  if (capacity > o->cap_points) {
-    char msg[256];
-    snprintf(msg, sizeof(msg), "odometry_step_cloud: capacity %d exceeds the %d points per scan this object was created for (A * k_strongest, or cfar_max_points with "
-             "filter_type CA-CFAR)", capacity, o->cap_points);
-    return cfear_fail(ctx, CFEAR_ERR_INVALID, msg);
-  }
-  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  CFEAR_TRY(odo_join(ctx, o));
-  CFEAR_TRY(odo_ensure_flags(ctx, o));  // counts beyond `capacity` are reported like every other truncation
-  return odo_step_clouds(ctx, o, d_xyi, capacity, d_counts, false);
-}
-
-int cfear_odometry_step_device(cfear_ctx* ctx, cfear_odometry* o, const uint8_t* d_polar) {
-  if (!ctx || !o || !d_polar) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_step: bad argument");
-  CFEAR_TRY(odo_shape_check(ctx, o, "odometry_step"));
-  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  CFEAR_TRY(odo_seq_sync(ctx, o, "odometry_step"));
-  if (o->filter == CFEAR_FILTER_CACFAR) {  // radar_driver.cpp:52-56, then the cloud route
-    int rc = CFEAR_OK;
-    if (o->profile && (rc = odo_timed_event(ctx, o, o->filter_events, ctx->stream)) != CFEAR_OK) return rc;
-    rc = odo_launch_cfar(ctx, o, d_polar, 1, o->d_cloud, o->d_cloud_n, o->d_cfar_rows, ctx->stream);
-    if (rc != CFEAR_OK) return rc;
-    if (o->profile && (rc = odo_timed_event(ctx, o, o->filter_events, ctx->stream)) != CFEAR_OK) return rc;
-    return odo_step_clouds(ctx, o, o->d_cloud, o->cap_points, o->d_cloud_n, true);
-  }
-  const OdoParams OP = odo_params(ctx, o);
-  const int buf = o->overlap ? (int)(o->step_no & 1) : 0;
-  hipStream_t sf = o->overlap ? o->sf : ctx->stream;
-  int rc = CFEAR_OK;
-  if (o->overlap) {
-    CFEAR_HIP_CHECK(ctx, hipEventRecord(o->ev_in, ctx->stream));  // the sweeps are ready at this point of the context stream
-    CFEAR_HIP_CHECK(ctx, hipStreamWaitEvent(sf, o->ev_in, 0));
-    if (o->filt_pending[buf])  // features(t-2) of every range has read this buffer
-      for (hipEvent_t e : o->ev_free[buf]) CFEAR_HIP_CHECK(ctx, hipStreamWaitEvent(sf, e, 0));
-  }
-  // radar_driver.cpp:58
-  if (o->profile && (rc = odo_timed_event(ctx, o, o->filter_events, sf)) != CFEAR_OK) return rc;
-  rc = cfear_launch_kstrongest(ctx, d_polar, odo_sources(o), o->d_slots[buf], sf, false, o->seq_zmin);  // (once per source sweep, at the smallest z_min of the rows; no peak flag: cloud_step_block does not read it)
-  if (rc != CFEAR_OK) return rc;
-  if (o->profile && (rc = odo_timed_event(ctx, o, o->filter_events, sf)) != CFEAR_OK) return rc;
-  if (o->overlap) {
-    CFEAR_HIP_CHECK(ctx, hipEventRecord(o->ev_filt[buf], sf));
-    // d_polar keeps its stream-order meaning for the caller: whatever the context stream is given after this call (the
-    // caller's next write into the buffer, its release to a caching allocator) waits for the filter, the only reader
-    CFEAR_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream, o->ev_filt[buf], 0));
-  }
-  const int nsub = o->overlap ? o->overlap : 1;
-  const int per = (o->B + nsub - 1) / nsub;
-  for (int i = 0; i < nsub; i++) {
-    OdoParams P = OP;
-    P.seq0 = i * per;
-    const int count = std::min(per, o->B - P.seq0);
-    if (count <= 0) break;
-    hipStream_t so = o->overlap ? o->so[i] : ctx->stream;
-    if (o->overlap) CFEAR_HIP_CHECK(ctx, hipStreamWaitEvent(so, o->ev_filt[buf], 0));
-    if (o->profile && (rc = odo_timed_event(ctx, o, o->stage_events, so)) != CFEAR_OK) return rc;
-    launch_features_step(ctx, o, P, o->d_slots[buf], count, so);
-    if (o->overlap) CFEAR_HIP_CHECK(ctx, hipEventRecord(o->ev_free[buf][i], so));
-    if (o->profile && (rc = odo_timed_event(ctx, o, o->stage_events, so)) != CFEAR_OK) return rc;
-    launch_register_step(P, count, so, o);
-    if (o->profile && (rc = odo_timed_event(ctx, o, o->stage_events, so)) != CFEAR_OK) return rc;
-  }
-  if (o->overlap) o->filt_pending[buf] = true;
-  o->surf_ready = OP.cs.ctx != nullptr;
-  o->step_no++; o->sweeps++;
-  CFEAR_HIP_CHECK(ctx, hipGetLastError());
-  return CFEAR_OK;
-}
-
-int cfear_odometry_phase_times(cfear_ctx* ctx, cfear_odometry* o, int enable, long long* host_ticks /*[B][32]*/) {
-  if (!ctx || !o) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_phase_times: bad argument");
-  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  CFEAR_TRY(odo_join(ctx, o));
-  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  const size_t bytes = sizeof(long long) * 32 * (size_t)o->B;
-  if (enable >= 1 && enable <= 4) {  // (any other non-zero value: read without changing the mode)
-    o->phase_detail = enable == 1 ? 1 : (enable == 4 ? 2 : 0);
-    o->wg_only = enable == 3;
-  }
-  if (!enable) {
-    o->d_phase_times.release();
-    return CFEAR_OK;
-  }
-  if (!o->d_phase_times) return o->d_phase_times.ensure(ctx, 32 * (size_t)o->B, "hipMalloc phase times", true);
-  if (host_ticks) {
-    CFEAR_HIP_CHECK(ctx, hipMemcpy(host_ticks, o->d_phase_times, bytes, hipMemcpyDeviceToHost));
-    CFEAR_HIP_CHECK(ctx, hipMemset(o->d_phase_times, 0, bytes));
-  }
-  return CFEAR_OK;
-}
-
-int cfear_odometry_profile(cfear_ctx* ctx, cfear_odometry* o, int enable) {
-  if (!ctx || !o) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_profile: bad argument");
-  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  CFEAR_TRY(odo_join(ctx, o));
-  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  o->filter_events.clear(); o->stage_events.clear(); o->pool_used = 0;  // the events go back to the pool
-  if (enable && o->pool.empty()) CFEAR_TRY(odo_grow_pool(ctx, o));  // created here, outside any timed region
-  o->profile = enable != 0;
-  return CFEAR_OK;
-}
-
-int cfear_odometry_profile_read(cfear_ctx* ctx, cfear_odometry* o, double* filter_seconds, int* filter_launches) {
-  if (!ctx || !o) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_profile_read: bad argument");
-  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  CFEAR_TRY(odo_join(ctx, o));
-  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  double tf = 0;
-  const int nf = (int)(o->filter_events.size() / 2);
-  for (int i = 0; i < nf; i++) {
-    float a = 0.f;
-    CFEAR_HIP_CHECK(ctx, hipEventElapsedTime(&a, o->filter_events[2 * i], o->filter_events[2 * i + 1]));
-    tf += a * 1e-3;
-  }
-  if (filter_seconds) *filter_seconds = tf;
-  if (filter_launches) *filter_launches = nf;
-  return CFEAR_OK;
-}
-
-int cfear_odometry_profile_read_stages(cfear_ctx* ctx, cfear_odometry* o, double* features_seconds, double* registration_seconds, int* launches) {
-  if (!ctx || !o) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_profile_read_stages: bad argument");
-  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  CFEAR_TRY(odo_join(ctx, o));
-  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  double tf = 0, tr = 0;
-  const int n = (int)(o->stage_events.size() / 3);
-  for (int i = 0; i < n; i++) {
-    float a = 0.f, b = 0.f;
-    CFEAR_HIP_CHECK(ctx, hipEventElapsedTime(&a, o->stage_events[3 * i], o->stage_events[3 * i + 1]));
-    CFEAR_HIP_CHECK(ctx, hipEventElapsedTime(&b, o->stage_events[3 * i + 1], o->stage_events[3 * i + 2]));
-    tf += a * 1e-3; tr += b * 1e-3;
-  }
-  if (features_seconds) *features_seconds = tf;
-  if (registration_seconds) *registration_seconds = tr;
-  if (launches) *launches = n;
-  return CFEAR_OK;
-}
-
-int cfear_odometry_step_host(cfear_ctx* ctx, cfear_odometry* o, const uint8_t* h_polar) {
-  if (!ctx || !o || !h_polar) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_step_host: bad argument");
-  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  const size_t bytes = (size_t)odo_sources(o) * ctx->A * ctx->R;  // (cfear_odometry_set_sequence_sources releases a staging buffer of another size)
-  CFEAR_TRY(o->d_polar.ensure(ctx, bytes + 64, "hipMalloc polar batch"));
-  // the staging buffer is reused: the copy waits for the filter of the previous sweep (its only reader), not for that
-  // sweep's features / registration
-  if (o->overlap && o->step_no > 0) CFEAR_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream, o->ev_filt[(o->step_no - 1) & 1], 0));
-  CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(o->d_polar, h_polar, bytes, hipMemcpyHostToDevice, ctx->stream));
-  // h_polar belongs to the caller again when this returns (pinned memory makes the copy truly asynchronous)
-  CFEAR_HIP_CHECK(ctx, hipEventRecord(o->ev_copied, ctx->stream));
-  const int rc = cfear_odometry_step_device(ctx, o, o->d_polar);
-  CFEAR_HIP_CHECK(ctx, hipEventSynchronize(o->ev_copied));
-  return rc;
-}
-
-// ---- replay of a recording without a host round trip per sweep (offline_odometry.cpp:103-125) -----------------------
-int cfear_host_alloc(cfear_ctx* ctx, size_t bytes, void** out) {
-  if (!ctx || !out || bytes == 0) return cfear_fail(ctx, CFEAR_ERR_INVALID, "host_alloc: bad argument");
-  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  *out = nullptr;
-  if (hipHostMalloc(out, bytes, hipHostMallocDefault) != hipSuccess) return cfear_fail(ctx, CFEAR_ERR_NOMEM, "hipHostMalloc");
-  return CFEAR_OK;
-}
-void cfear_host_free(cfear_ctx* ctx, void* p) {
-  if (!p) return;
-  if (ctx) (void)hipSetDevice(ctx->device);
-  (void)hipHostFree(p);
-}
-
-// chunk: sweeps per chunk the slot buffers must hold; staging: the host route also needs the two polar staging buffers of that many
-// sweeps (the device route filters the frames where they lie and never touches them: for thousands of sequences they would be
-// gigabytes allocated for nothing)
-static int replay_ensure(cfear_ctx* ctx, cfear_odometry* o, int chunk, bool staging, size_t n_records) {
-  if (!o->rp_ready) {  // events first, the stream last, the flag only when everything exists: a failure leaves nothing half-made behind
-    for (hipEvent_t* e : {&o->rp_filt[0], &o->rp_filt[1], &o->rp_used[0], &o->rp_used[1], &o->rp_in})
-      if (!*e) CFEAR_HIP_CHECK(ctx, hipEventCreateWithFlags(e, hipEventDisableTiming));
-    if (!o->rp_stream) {
-      CFEAR_HIP_CHECK(ctx, hipStreamCreateWithFlags(&o->rp_stream, hipStreamNonBlocking));
-      ctx->aux_streams.push_back(o->rp_stream);
-    }
-    o->rp_ready = true;
-  }
-  // (a CA-CFAR object's clouds are one per sequence whatever the sweeps they come from)
-  const size_t sweep = (size_t)odo_sources(o) * ctx->A * ctx->R, slots = (size_t)(o->filter == CFEAR_FILTER_CACFAR ? o->B : odo_sources(o)) * o->cap_points;
-  if (chunk > o->rp_chunk) {
-    CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(o->rp_stream));
-    CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    o->rp_chunk = 0;  // (until every buffer holds `chunk` sweeps)
-    o->rp_used_pending[0] = o->rp_used_pending[1] = false;
-    for (int i = 0; i < 2; i++) {
-      if (o->filter == CFEAR_FILTER_CACFAR) {  // a cloud of cap_points points + its count per sweep and sequence
-        CFEAR_TRY(o->rp_cloud[i].ensure(ctx, 3 * slots * chunk, "hipMalloc replay cloud buffers"));
-        CFEAR_TRY(o->rp_cloud_n[i].ensure(ctx, (size_t)o->B * chunk, "hipMalloc replay cloud buffers"));
-      } else {
-        CFEAR_TRY(o->rp_slots[i].ensure(ctx, slots * chunk, "hipMalloc replay slot buffers"));
-      }
-    }
-    if (o->filter == CFEAR_FILTER_CACFAR)
-      CFEAR_TRY(o->rp_cfar_rows.ensure(ctx, o->det_grid ? cfear_cfar_grid_scratch_ints(ctx, o->det_grid.get(), (size_t)chunk) : cfear_cfar_scratch_ints(ctx, (size_t)o->B * chunk),
-                                       "hipMalloc replay cfar rows"));
-    o->rp_chunk = chunk;
-  }
-  if (staging && chunk > o->rp_polar_chunk) {
-    CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(o->rp_stream));
-    CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    o->rp_polar_chunk = 0;
-    for (auto& polar : o->rp_polar) CFEAR_TRY(polar.ensure(ctx, sweep * chunk + 64, "hipMalloc replay staging"));
-    o->rp_polar_chunk = chunk;
-  }
-  if (n_records > o->d_records.size()) {
-    CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    CFEAR_TRY(o->d_records.ensure(ctx, n_records, "hipMalloc sweep records"));
-  }
-  return CFEAR_OK;
-}
-
-// frames: n_sweeps x B x A x R bytes on the host (copied chunk by chunk into the staging buffers) or on the device (filtered where
-// they lie); d_records: where the per-sweep records go on the device (null: none)
-static int replay_impl_queue(cfear_ctx* ctx, cfear_odometry* o, const uint8_t* frames, bool on_device, int n_sweeps, cfear_sweep_record* d_records,
-                             double* d_cov6) {
-  const int nsrc = odo_sources(o);  // input sweeps per step: the sequences, or the sources of a source map
-  const size_t sweep = (size_t)nsrc * ctx->A * ctx->R, slots = (size_t)(o->filter == CFEAR_FILTER_CACFAR ? o->B : nsrc) * o->cap_points;
-  // chunk: enough sweeps for the filter to run at its streaming rate (>= ~16 k azimuth rows per launch) and for the copy of the
-  // next chunk to hide behind the odometry kernels of this one, at most 256 MB per buffer (host route: of staged sweeps; device
-  // route: of filter slots - there is no staging)
-  const bool cfar = o->filter == CFEAR_FILTER_CACFAR;
-  const size_t filt_bytes = cfar ? sizeof(float) * 3 * slots : sizeof(uint32_t) * slots;  // the filter's output per sweep
-  const size_t per_sweep = on_device ? filt_bytes : std::max(sweep, filt_bytes);
-  int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)64, ((size_t)256 << 20) / per_sweep));
-  chunk = std::min(chunk, n_sweeps);
-  {  // buffers of an earlier call may hold more sweeps per chunk: at least as good
-    const int have = on_device ? o->rp_chunk : std::min(o->rp_chunk, o->rp_polar_chunk);
-    chunk = std::max(chunk, std::min(have, n_sweeps));
-  }
-  int rc = replay_ensure(ctx, o, chunk, !on_device, 0);
-  if (rc != CFEAR_OK) return rc;
-  const int nchunks = (n_sweeps + chunk - 1) / chunk;
-  OdoParams OP = odo_params(ctx, o);
-  if (!o->cov_on) OP.cs.ctx = nullptr;  // the replay routes do not record for cost surfaces
-  o->surf_ready = false;
-  // (the keyframe recorder is a stage behind the registration stage: with recording on the sweeps run as two launches, like the timed ones)
-  const bool persistent = o->B <= ctx->tune_replay_persistent_max && !OP.phase_times && !OP.wg_times && !o->kf_what;
-  if (on_device) {  // the sweeps are ready at this point of the context stream: the replay stream (which reads them) starts there
-    CFEAR_HIP_CHECK(ctx, hipEventRecord(o->rp_in, ctx->stream));
-    CFEAR_HIP_CHECK(ctx, hipStreamWaitEvent(o->rp_stream, o->rp_in, 0));
-  }
-  auto stage = [&](int c) -> int {  // copy + filter of chunk c on the replay stream
-    const int b = c & 1, t0 = c * chunk, cnt = std::min(chunk, n_sweeps - t0);
-    if (o->rp_used_pending[b]) CFEAR_HIP_CHECK(ctx, hipStreamWaitEvent(o->rp_stream, o->rp_used[b], 0));  // its slots were consumed
-    const uint8_t* src = frames + sweep * (size_t)t0;
-    if (!on_device) {
-      CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(o->rp_polar[b], src, sweep * (size_t)cnt, hipMemcpyHostToDevice, o->rp_stream));
-      src = o->rp_polar[b];
-    }
-    const int frc = cfar ? odo_launch_cfar(ctx, o, src, cnt, o->rp_cloud[b], o->rp_cloud_n[b], o->rp_cfar_rows, o->rp_stream)  // radar_driver.cpp:52-56
-                         : cfear_launch_kstrongest(ctx, src, cnt * nsrc, o->rp_slots[b], o->rp_stream, false, o->seq_zmin);  // radar_driver.cpp:58, pose-independent
-    if (frc != CFEAR_OK) return frc;
-    CFEAR_HIP_CHECK(ctx, hipEventRecord(o->rp_filt[b], o->rp_stream));
-    return CFEAR_OK;
-  };
-  rc = stage(0);
-  if (rc != CFEAR_OK) return rc;
-  for (int c = 0; c < nchunks; c++) {
-    const int b = c & 1, t0 = c * chunk, cnt = std::min(chunk, n_sweeps - t0);
-    CFEAR_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream, o->rp_filt[b], 0));
-    // odometrykeyframefuser.cpp:143-259 sweep after sweep. Few sequences: one persistent workgroup per sequence walks the whole
-    // chunk (no launch in between; a workgroup needs a compute unit's LDS to itself, so this pays while the sequences fit the
-    // chip at one per compute unit). Many sequences: the batched kernels, two launches per sweep, whose occupancy is what counts.
-    OP.cs.cov_out = d_cov6 ? d_cov6 + (size_t)t0 * o->B * 36 : nullptr;  // (the persistent kernels step it on per sweep)
-    if (persistent && cfar) {
-      cfear_launch_replay_chunk_cloud(o->rp_cloud[b], o->cap_points, o->rp_cloud_n[b], cnt, o->B, OP, o->d_states, o->d_scratch_hdr, o->d_cov_work, o->d_summaries,
-                                      o->d_poses_out, d_records ? d_records + (size_t)t0 * o->B : nullptr, ctx->stream);
-    } else if (persistent) {
-      cfear_launch_replay_chunk(o->rp_slots[b], cnt, o->B, ctx->d_trig, OP, o->d_states, o->d_scratch_hdr, o->d_cov_work, o->d_summaries,
-                                o->d_poses_out, d_records ? d_records + (size_t)t0 * o->B : nullptr, ctx->stream);
-    } else {
-      for (int t = 0; t < cnt; t++) {
-        OP.records = d_records ? d_records + (size_t)(t0 + t) * o->B : nullptr;
-        OP.cs.cov_out = d_cov6 ? d_cov6 + (size_t)(t0 + t) * o->B * 36 : nullptr;
-        if (cfar) odo_launch_sweep_cloud(o, OP, o->rp_cloud[b] + 3 * slots * (size_t)t, o->cap_points, o->rp_cloud_n[b] + (size_t)o->B * t, o->B, ctx->stream);
-        else odo_launch_sweep(ctx, o, OP, o->rp_slots[b] + slots * (size_t)t, o->B, ctx->stream);
-      }
-    }
-    CFEAR_HIP_CHECK(ctx, hipEventRecord(o->rp_used[b], ctx->stream));
-    o->rp_used_pending[b] = true;
-    o->step_no += cnt; o->sweeps += cnt;
-    if (c + 1 < nchunks && (rc = stage(c + 1)) != CFEAR_OK) return rc;  // (queued after this chunk's launches: a copy from pageable memory blocks the host)
-  }
-  CFEAR_HIP_CHECK(ctx, hipGetLastError());
-  return CFEAR_OK;
-}
-static int replay_impl(cfear_ctx* ctx, cfear_odometry* o, const uint8_t* frames, bool on_device, int n_sweeps, cfear_sweep_record* d_records,
-                       double* d_cov6) {
-  const int rc = replay_impl_queue(ctx, o, frames, on_device, n_sweeps, d_records, d_cov6);
-  if (rc != CFEAR_OK && o->rp_stream) {
-    // an error after work was queued: copies out of the caller's frames and kernels that read them may be in flight - nothing of
-    // this call is left running when it returns (the error text is kept)
-    const std::string keep = ctx->err;
-    (void)hipStreamSynchronize(o->rp_stream);
-    (void)hipStreamSynchronize(ctx->stream);
-    ctx->err = keep;
-  }
-  return rc;
-}
-
-static int replay_check(cfear_ctx* ctx, cfear_odometry* o, const uint8_t* frames, int n_sweeps) {
-  if (!ctx || !o || !frames || n_sweeps <= 0) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_replay: bad argument");
-  CFEAR_TRY(odo_shape_check(ctx, o, "odometry_replay"));
-  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  CFEAR_TRY(odo_seq_sync(ctx, o, "odometry_replay"));
-  // CA-CFAR reads the images as dwords: every chunk of the replay starts a whole number of sweeps (of B images, or of the sources the sequences'
-  // detectors share) after `frames`, so the base and the sweep size decide the alignment of all of them - refused here, before any chunk has
-  // advanced the sequences' state
-  if (o->filter == CFEAR_FILTER_CACFAR && ((reinterpret_cast<uintptr_t>(frames) & 3) != 0 || (n_sweeps > 1 && (((size_t)odo_sources(o) * ctx->A * ctx->R) & 3) != 0)))
-    return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_replay: filter_type CA-CFAR needs a 4-byte aligned recording and B * A * R a multiple of 4 (the detector reads whole "
-                      "dwords; B: the input sweeps per step)");
-  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  return odo_join(ctx, o);
-}
-
-int cfear_odometry_replay_host_cov(cfear_ctx* ctx, cfear_odometry* o, const uint8_t* h_frames, int n_sweeps, cfear_sweep_record* records, double* cov6) {
-  int rc = replay_check(ctx, o, h_frames, n_sweeps);
-  if (rc != CFEAR_OK) return rc;
-  if (records && (rc = replay_ensure(ctx, o, 0, false, (size_t)n_sweeps * o->B)) != CFEAR_OK) return rc;
-  const size_t ncov = cov6 ? (size_t)n_sweeps * o->B * 36 : 0;
-  if (ncov > o->d_cov_seq.size()) {
-    CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    CFEAR_TRY(o->d_cov_seq.ensure(ctx, ncov, "hipMalloc per-sweep covariances"));
-  }
-  rc = replay_impl(ctx, o, h_frames, false, n_sweeps, records ? o->d_records : nullptr, cov6 ? o->d_cov_seq : nullptr);
-  if (rc != CFEAR_OK) return rc;
-  if (records) CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(records, o->d_records, sizeof(cfear_sweep_record) * (size_t)n_sweeps * o->B, hipMemcpyDeviceToHost, ctx->stream));
-  if (cov6) CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(cov6, o->d_cov_seq, sizeof(double) * ncov, hipMemcpyDeviceToHost, ctx->stream));
-  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  return odo_capacity_check(ctx, o, "odometry_replay_host");
-}
-int cfear_odometry_replay_host(cfear_ctx* ctx, cfear_odometry* o, const uint8_t* h_frames, int n_sweeps, cfear_sweep_record* records) {
-  return cfear_odometry_replay_host_cov(ctx, o, h_frames, n_sweeps, records, nullptr);
-}
-
-int cfear_odometry_replay_device_cov(cfear_ctx* ctx, cfear_odometry* o, const uint8_t* d_frames, int n_sweeps, cfear_sweep_record* d_records, double* d_cov6) {
-  const int rc = replay_check(ctx, o, d_frames, n_sweeps);
-  if (rc != CFEAR_OK) return rc;
-  return replay_impl(ctx, o, d_frames, true, n_sweeps, d_records, d_cov6);  // asynchronous: nothing is waited for
-}
-int cfear_odometry_replay_device(cfear_ctx* ctx, cfear_odometry* o, const uint8_t* d_frames, int n_sweeps, cfear_sweep_record* d_records) {
-  return cfear_odometry_replay_device_cov(ctx, o, d_frames, n_sweeps, d_records, nullptr);
 }
 
 // ---- estimate_cov_by_sampling on the batched routes (cov_sampling_dev.h) ------------------------------------------------
@@ -2081,28 +1523,6 @@ int cfear_odometry_cov_samples(cfear_ctx* ctx, cfear_odometry* o, int sequence, 
     *sampled = c.n >= 2 ? c.sampled : 0;
   }
   return odo_capacity_check(ctx, o, "odometry_cov_samples");
-}
-
-// after a synchronisation of the context stream: has any scan of this object overflowed its cell capacity (CFEAR_TUNE_MAX_CELLS)?
-static int odo_capacity_check(cfear_ctx* ctx, cfear_odometry* o, const char* what) {
-  if (!o->d_flags) return CFEAR_OK;  // sized for every filtered point: cannot happen
-  int f = 0;
-  CFEAR_HIP_CHECK(ctx, hipMemcpy(&f, o->d_flags, sizeof(int), hipMemcpyDeviceToHost));
-  if (f & 2) {
-    char msg[320];
-    snprintf(msg, sizeof(msg), "%s: a sweep's cloud had more points than the %d this object is sized for (cfear_params.cfar_max_points with filter_type CA-CFAR; the "
-             "capacity argument of cfear_odometry_step_cloud_device): the first %d in (azimuth, range) order were kept, the results of that sequence are those "
-             "of a truncated cloud", what, o->cap_points, o->cap_points);
-    return cfear_fail(ctx, CFEAR_ERR_CAPACITY, msg);
-  }
-  if (f & 1) {
-    char msg[400];
-    snprintf(msg, sizeof(msg), "%s: a scan produced more than %d oriented surface points (%s): its first %d were kept, the results of that sequence are those of a "
-             "truncated scan", what, o->cap_cells, ctx->tune_max_cells > 0 ? "cfear_tune CFEAR_TUNE_MAX_CELLS of this object" :
-             "the default of objects with more than 7 keyframes: min(points per scan, 4096); raise it with cfear_tune CFEAR_TUNE_MAX_CELLS before cfear_odometry_create", o->cap_cells);
-    return cfear_fail(ctx, CFEAR_ERR_CAPACITY, msg);
-  }
-  return CFEAR_OK;
 }
 
 int cfear_odometry_poses(cfear_ctx* ctx, cfear_odometry* o, double* poses_xyt) {

@@ -77,7 +77,7 @@ int cfear_rotate_polar(cfear_ctx* ctx, const uint8_t* h_in, int in_rows, int in_
   int rc = cfear_upload_image(ctx, d, h_in, bytes);
   if (rc == CFEAR_OK) rc = cfear_rotate_polar_device(ctx, d, 1, in_rows, in_cols, d + bytes);
   hipError_t e = hipSuccess;
-  const bool staged = rc == CFEAR_OK && ctx->h_img && ctx->h_img_bytes >= bytes && ctx->ev_img_pending;
+  const bool staged = rc == CFEAR_OK && ctx->h_img && ctx->h_img.size() >= bytes && ctx->ev_img_pending;
   if (rc == CFEAR_OK) e = hipMemcpyAsync(staged ? static_cast<void*>(ctx->h_img) : static_cast<void*>(h_out), d + bytes, bytes, hipMemcpyDeviceToHost, ctx->stream);
   if (rc == CFEAR_OK && e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
   if (rc == CFEAR_OK && e == hipSuccess && staged) { memcpy(h_out, ctx->h_img, bytes); ctx->ev_img_pending = false; }

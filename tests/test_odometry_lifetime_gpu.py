@@ -186,6 +186,37 @@ def test_nothing_is_left_behind():
     assert free0 - free1 <= 0
 
 
+@pytest.mark.parametrize("params", [BASE, CFAR], ids=["k_strongest", "ca_cfar"])
+@pytest.mark.parametrize("overlap", [0, 2])
+def test_streams_are_given_back(params, overlap):
+    """An object's streams (the overlap mode's, the replay's) leave the context's list when the object goes: the context synchronizes after
+    the release, a second object on the same context runs like the first, and both like one on a fresh context. (With CA-CFAR the
+    library runs without overlap streams whatever the tune says: the replay stream is the one given back.)"""
+    fr = frames(4)
+
+    def context():
+        ctx = capi.Context(capi.default_params(**params), A, R)
+        ctx.tune(capi.TUNE_ODOMETRY_OVERLAP, overlap)
+        return ctx
+
+    def drive(ctx):
+        odo = ctx.odometry(B)
+        odo.step_host(fr[0]); odo.step_host(fr[1])
+        odo.replay_host(fr[2:4])  # (the replay stream exists from here on)
+        got = state(odo)
+        odo.release()
+        ctx.synchronize()  # waits for no stream that is gone
+        return got
+
+    ctx = context()
+    first, second = drive(ctx), drive(ctx)
+    ctx.close()
+    ctx = context()
+    fresh = drive(ctx)
+    ctx.close()
+    assert first == second and first == fresh
+
+
 def test_a_refused_call_leaves_the_object_usable():
     fr = frames(4)
 

@@ -1,12 +1,13 @@
 #!/bin/bash
-# Is the device code of the translation units with host code of the launch layer the same as at another commit?  usage: tools/device_asm_diff.sh [BASE_REV] (default HEAD)
-# Compiles the units below at BASE_REV and in the working tree with build.py's flags, device side
+# Is the device code of every translation unit (csrc/*.hip of this tree) the same as at another commit?  usage: tools/device_asm_diff.sh [BASE_REV] (default HEAD)
+# Compiles the units at BASE_REV and in the working tree with build.py's flags, device side
 # only, and compares the assembly after dropping what a pure host / namespace change may move: comments, .file / .ident, the per-compile
 # __hip_cuid symbol, the (anonymous namespace):: / cfear_dev:: qualifiers of demangled names, and the function index in block and function-end
 # labels (.LBB3_28, .Lfunc_end3), which moves whenever a function is added to or removed from a unit. The assembly is compared function by
 # function (a function's text, its kernel descriptor and its metadata entry; the rest of the unit counts as one more): per unit the lines
 # compared and differing in functions both trees have, then the functions only one tree has. The exit status is 1 only when a function both
-# trees have differs. The normalised files and whole-file diffs stay in $OUT (default /tmp/cfear_asm_diff).
+# trees have differs. A unit the base does not have is compared with nothing (its functions are "only in this tree"), and every unit's line ends
+# with the number of kernels it defines (odometry_run and odometry_seq: 0). The normalised files and whole-file diffs stay in $OUT (default /tmp/cfear_asm_diff).
 set -u
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 BASE=${1:-HEAD}
@@ -69,9 +70,10 @@ print(msg)
 sys.exit(1 if nosec else 0)
 PY
 }
-UNITS="pipeline register_step register_step_large replay cabi cfar drift kstrongest"
+UNITS=$(cd "$ROOT/$PKG/csrc" && ls *.hip | sed 's/\.hip$//')
 rc=0
 for u in $UNITS; do
+  [ -f "$OUT/base_src/$PKG/csrc/$u.hip" ] || echo > "$OUT/base_src/$PKG/csrc/$u.hip"  # (a unit that is new in this tree)
   ( hipcc $FLAGS --cuda-device-only -S "$OUT/base_src/$PKG/csrc/$u.hip" -o "$OUT/base/$u.raw.s" && norm "$OUT/base/$u.raw.s" > "$OUT/base/$u.s" ) &
   ( hipcc $FLAGS --cuda-device-only -S "$ROOT/$PKG/csrc/$u.hip" -o "$OUT/head/$u.raw.s" && norm "$OUT/head/$u.raw.s" > "$OUT/head/$u.s" ) &
 done
@@ -80,6 +82,6 @@ for u in $UNITS; do
   [ -s "$OUT/base/$u.s" ] && [ -s "$OUT/head/$u.s" ] || { echo "$u: compile failed"; rc=2; continue; }
   diff "$OUT/base/$u.s" "$OUT/head/$u.s" > "$OUT/$u.diff"
   r=$(compare "$OUT/base/$u.s" "$OUT/head/$u.s") || rc=1
-  echo "$u: $r"
+  echo "$u: $r; $(grep -c '\.amdhsa_kernel ' "$OUT/head/$u.s") kernels"
 done
 exit $rc
