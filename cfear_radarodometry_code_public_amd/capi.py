@@ -121,6 +121,7 @@ KEYFRAME_NODE_DTYPE = np.dtype([("index", "i4"), ("sweep", "i4"), ("n_cells", "i
 KEYFRAME_CELL_DTYPE = np.dtype([("mean", "f8", 2), ("normal", "f8", 2), ("cov", "f8", 3), ("scale", "f8"), ("nsamples", "i4"), ("pad_", "i4")])
 assert KEYFRAME_NODE_DTYPE.itemsize == C.sizeof(KeyframeNode) == 376 and KEYFRAME_CELL_DTYPE.itemsize == C.sizeof(KeyframeCell) == 72
 KF_NODES, KF_CELLS = 1, 2  # CFEAR_KF_NODES / CFEAR_KF_CELLS
+KF_CLOUD, KF_PEAKS = 4, 8  # CFEAR_KF_CLOUD / CFEAR_KF_PEAKS (cfear_odometry_set_keyframe_clouds)
 STATUS_CELLS_LOST, STATUS_POINTS_LOST, STATUS_KEYFRAMES_DROPPED = 1, 2, 4  # the bits of a sequence's word in cfear_odometry_status
 
 
@@ -162,6 +163,7 @@ EXPORTS = [
     "cfear_odometry_covariances", "cfear_odometry_status", "cfear_odometry_summary", "cfear_odometry_profile", "cfear_odometry_profile_read", "cfear_odometry_profile_read_stages", "cfear_odometry_phase_times", "cfear_time_kstrongest",
     "cfear_keyframe_constraint", "cfear_odometry_set_keyframe_recording", "cfear_odometry_keyframe_counts", "cfear_odometry_keyframe_nodes",
     "cfear_odometry_keyframe_cells", "cfear_odometry_keyframe_scans",
+    "cfear_odometry_set_keyframe_clouds", "cfear_odometry_keyframe_cloud_sizes", "cfear_odometry_keyframe_cloud", "cfear_odometry_keyframe_clouds",
     "cfear_drift_segments", "cfear_drift_plan_create", "cfear_drift_plan_release", "cfear_drift_device", "cfear_drift_host",
 ]
 
@@ -269,6 +271,10 @@ def lib():
         "cfear_odometry_keyframe_nodes": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, C.c_int, C.POINTER(C.c_int)]),
         "cfear_odometry_keyframe_cells": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, C.c_int, C.POINTER(C.c_int)]),
         "cfear_odometry_keyframe_scans": (C.c_int, [vp, vp, C.c_int, i32p, C.c_int, C.POINTER(vp)]),
+        "cfear_odometry_set_keyframe_clouds": (C.c_int, [vp, vp, C.c_int, C.c_int]),
+        "cfear_odometry_keyframe_cloud_sizes": (C.c_int, [vp, vp, C.c_int, C.c_int, i32p, i32p, C.c_int, C.POINTER(C.c_int)]),
+        "cfear_odometry_keyframe_cloud": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, f32p, C.c_int, C.POINTER(C.c_int)]),
+        "cfear_odometry_keyframe_clouds": (C.c_int, [vp, vp, C.c_int, i32p, C.c_int, C.c_int, C.POINTER(vp)]),
         "cfear_drift_segments": (C.c_int, [f64p, C.c_int, i32p, i32p, i32p, C.c_int, C.POINTER(C.c_int)]),
         "cfear_drift_plan_create": (C.c_int, [vp, f64p, C.c_int, C.POINTER(vp)]),
         "cfear_drift_plan_release": (None, [vp, vp]),
@@ -1025,11 +1031,24 @@ class Odometry:
         return buf
 
     # ---- the keyframe graph (AddToGraph, odometrykeyframefuser.cpp:428-445) ----
-    def record_keyframes(self, what=KF_NODES | KF_CELLS, max_keyframes=1024, max_cells=0):
+    def record_keyframes(self, what=KF_NODES | KF_CELLS, max_keyframes=1024, max_cells=0, max_points=0):
         """cfear_odometry_set_keyframe_recording: what = 0 (off), KF_NODES or KF_NODES | KF_CELLS; the capacities are per sequence (nodes;
-        cells summed over its keyframes). Switching on needs an object that has processed no sweep since it was created / reset."""
-        self._ctx._check(self._ctx._L.cfear_odometry_set_keyframe_recording(self._ctx._h, self._h, int(what), int(max_keyframes), int(max_cells)),
-                         "cfear_odometry_set_keyframe_recording")
+        cells summed over its keyframes). Switching on needs an object that has processed no sweep since it was created / reset.
+        what | KF_CLOUD (| KF_PEAKS) also records every node's motion-compensated filtered (and peaks) cloud
+        (cfear_odometry_set_keyframe_clouds): max_points per sequence, summed over both clouds of all its keyframes."""
+        what = int(what)
+        if what & KF_PEAKS and not what & KF_CLOUD:
+            raise CfearError("record_keyframes: KF_PEAKS needs KF_CLOUD (the peaks cloud is recorded beside the filtered cloud)")
+        if what & (KF_CLOUD | KF_PEAKS) and not what & KF_NODES:
+            raise CfearError("record_keyframes: KF_CLOUD needs KF_NODES (the clouds belong to recorded nodes)")
+        self._ctx._check(self._ctx._L.cfear_odometry_set_keyframe_recording(self._ctx._h, self._h, what & ~(KF_CLOUD | KF_PEAKS), int(max_keyframes),
+                                                                            int(max_cells)), "cfear_odometry_set_keyframe_recording")
+        if what & KF_CLOUD:
+            self.record_keyframe_clouds(what & (KF_CLOUD | KF_PEAKS), max_points)
+
+    def record_keyframe_clouds(self, what=KF_CLOUD | KF_PEAKS, max_points=0):
+        """cfear_odometry_set_keyframe_clouds on an object whose node recording is on: what = 0 (off, at any time), KF_CLOUD or KF_CLOUD | KF_PEAKS"""
+        self._ctx._check(self._ctx._L.cfear_odometry_set_keyframe_clouds(self._ctx._h, self._h, int(what), int(max_points)), "cfear_odometry_set_keyframe_clouds")
 
     def keyframe_counts(self):
         """-> (recorded [B], dropped [B]) keyframes per sequence"""
@@ -1060,6 +1079,34 @@ class Odometry:
         arr = (C.c_void_p * len(idx))()
         self._ctx._check(self._ctx._L.cfear_odometry_keyframe_scans(self._ctx._h, self._h, int(q), idx.ctypes.data, len(idx), arr), "cfear_odometry_keyframe_scans")
         return [Scan(self._ctx, C.c_void_p(h)) for h in arr]
+
+    def keyframe_cloud_sizes(self, q):
+        """-> (n_cloud [n], n_peaks [n]): points of the filtered and of the peaks cloud of every recorded node of sequence q"""
+        n = C.c_int()
+        self._ctx._check(self._ctx._L.cfear_odometry_keyframe_cloud_sizes(self._ctx._h, self._h, int(q), 0, None, None, 0, C.byref(n)), "cfear_odometry_keyframe_cloud_sizes")
+        nc, npk = np.zeros(max(n.value, 1), dtype=np.int32), np.zeros(max(n.value, 1), dtype=np.int32)
+        self._ctx._check(self._ctx._L.cfear_odometry_keyframe_cloud_sizes(self._ctx._h, self._h, int(q), 0, nc.ctypes.data, npk.ctypes.data, n.value, C.byref(n)),
+                         "cfear_odometry_keyframe_cloud_sizes")
+        return nc[:n.value], npk[:n.value]
+
+    def keyframe_cloud(self, q, i, peaks=False):
+        """the filtered (peaks=True: the peaks) cloud of keyframe i of sequence q -> float32 [n, 3]: x, y, intensity"""
+        n = C.c_int()
+        self._ctx._check(self._ctx._L.cfear_odometry_keyframe_cloud(self._ctx._h, self._h, int(q), int(i), int(bool(peaks)), None, 0, C.byref(n)),
+                         "cfear_odometry_keyframe_cloud")
+        out = np.zeros((max(n.value, 1), 3), dtype=np.float32)
+        self._ctx._check(self._ctx._L.cfear_odometry_keyframe_cloud(self._ctx._h, self._h, int(q), int(i), int(bool(peaks)), out.ctypes.data, n.value, C.byref(n)),
+                         "cfear_odometry_keyframe_cloud")
+        return out[:n.value]
+
+    def keyframe_clouds(self, q, indices, peaks=False):
+        """the recorded clouds of keyframes `indices` of sequence q as device Clouds (cfear_odometry_keyframe_clouds): ready for
+        Context.scan_create at any res, Cloud.download. -> list of Cloud"""
+        idx = np.ascontiguousarray(indices, dtype=np.int32).reshape(-1)
+        arr = (C.c_void_p * len(idx))()
+        self._ctx._check(self._ctx._L.cfear_odometry_keyframe_clouds(self._ctx._h, self._h, int(q), idx.ctypes.data, len(idx), int(bool(peaks)), arr),
+                         "cfear_odometry_keyframe_clouds")
+        return [Cloud(self._ctx, C.c_void_p(h)) for h in arr]
 
     def poses(self):
         out = np.zeros((self.B, 3))

@@ -257,10 +257,15 @@ __device__ __forceinline__ void point_regs_to_global(const PointRegs& R, float* 
 // and keeps the offset b * (K - k) + max(C_b - k, 0) in `win` (LDS, win_cap ints; more bearings than that: every lane bisects for itself).
 // Lane <-> item as before, not lane <-> physical slot: the rounds a wave takes and the branch chosen below follow A * k, as they do for an
 // object whose filter ran with k. K == k: the address is t, no pass in front.
+// PEAKS: only the slots with the peak bit (getPeaksFilteredPointCloud(peaks = true), radar_filters.cpp:327; the keyframe recorder's peaks
+// cloud - the window of a row with k < K is found on the valid bit either way). found: where the number of points before the clip at
+// `cap` goes (null: nobody asks).
+template <bool PEAKS = false>
 __device__ inline int cloud_step_block(const uint32_t* __restrict__ slots, int A, int k, int K, const double* __restrict__ trig,
                                        float range_res_f, float min_distance_f, int z_min, float* __restrict__ xyi, int cap, int compensate,
                                        double m0, double m1, double m2, int ccw, int* red_i, float* red_f, double* tab,
-                                       int tab_bearings, float bounds[4], PointRegs& PR, bool store = true, int* win = nullptr, int win_cap = 0) {
+                                       int tab_bearings, float bounds[4], PointRegs& PR, bool store = true, int* win = nullptr, int win_cap = 0,
+                                       int* found = nullptr) {
   // store = false: the caller can do without the cloud in S->xyi when the points are handed over in registers - 58 KB per
   // sweep that the compact feature path never reads back (the general branch below always writes it);
   // point_regs_to_global writes it later for a caller that turns out to need it.
@@ -297,7 +302,7 @@ __device__ inline int cloud_step_block(const uint32_t* __restrict__ slots, int A
   // z_min: a slot also has to reach this intensity (a sequence's own threshold behind a filter that ran with a lower one; 0: every valid slot).
   // One comparison for both: the valid bit sits right above the intensity byte
   const int valid_z = 256 + z_min;
-#define CFEAR_SLOT_VALID_Z(s) ((int)(((s) >> 16) & 0x1FFu) >= valid_z)
+#define CFEAR_SLOT_VALID_Z(s) (((int)(((s) >> 16) & 0x1FFu) >= valid_z) & (!PEAKS || CFEAR_SLOT_PEAK(s)))
   const int wv = threadIdx.x >> 6, ln = lane_id(), nwv = CFEAR_FEAT_BLOCK >> 6;
   // per-bearing table in LDS, six doubles each: principal angle, sin / cos of the compensation rotation at the bearing's
   // angle, its sweep fraction, cos / sin of the bearing (so that the per-point loop has no global load to wait for)
@@ -394,6 +399,7 @@ __device__ inline int cloud_step_block(const uint32_t* __restrict__ slots, int A
         mnx = fminf(mnx, x); mxx = fmaxf(mxx, x); mny = fminf(mny, y); mxy = fmaxf(mxy, y);
       }
     }
+    if (found) *found = total;
     total = total < cap ? total : cap;
     bounds[0] = mnx; bounds[1] = mxx; bounds[2] = mny; bounds[3] = mxy;
     block_bounds<CFEAR_FEAT_BLOCK>(bounds, red_f);  // (its barriers come after every store of the cloud: the general feature path may read it back)
@@ -481,6 +487,7 @@ __device__ inline int cloud_step_block(const uint32_t* __restrict__ slots, int A
   else if (tabbed) points_pass(std::true_type{}, std::false_type{});
   else if (small) points_pass(std::false_type{}, std::true_type{});
   else points_pass(std::false_type{}, std::false_type{});
+  if (found) *found = total;
   total = total < cap ? total : cap;
   bounds[0] = mnx; bounds[1] = mxx; bounds[2] = mny; bounds[3] = mxy;
   block_bounds<CFEAR_FEAT_BLOCK>(bounds, red_f);

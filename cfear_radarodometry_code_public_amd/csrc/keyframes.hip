@@ -5,6 +5,7 @@
 //   keyframe_record_kernel  a stage of its own behind the registration stage, one workgroup per sequence: the sequences that fused
 //                           append their node - and their scan's cells - to their own log. It reads what the stages left behind
 //                           (SeqState, the scan in last_slot, cov_work); no other kernel knows of it.
+//   keyframe_cloud_kernel   with a point log, in front of the recorder: the filtered and the peaks cloud of the sequences that fused.
 //   keyframe_scans_kernel   the batched twin of scan_from_cells_kernel: a workgroup per scan rebuilds a per-call scan from the log.
 //   cfear_keyframe_constraint  the rule of AddToGraph :435-440 for the host (keyframe_constraint.h: one function for both sides).
 #include "common.h"
@@ -14,6 +15,67 @@
 namespace {
 
 constexpr int BLOCK_K = 256;
+
+// The cloud stage (cfear_odometry_set_keyframe_clouds): cloud_nopeaks_ and cloud_peaks_ of the RadarScan a fused sweep ends with
+// (odometrykeyframefuser.cpp:147-149, 234-248; types.h:93-143), in front of the recorder on the same stream, a workgroup per sequence. A
+// sequence that fused - the recorder's own test - writes both clouds behind the points its log holds and leaves its verdict in cloud_word;
+// the recorder folds it into `fits` and commits the offsets, so only sequence q's workgroups touch q's words, in stream order.
+//   k-strongest routes: the points the feature stage built its cells from, through the same code on the same slots - cloud_step_block with
+//     the sequence's own row and the LDS layout of features_step_body (so the same branch, the same bearing table, the same bits) - and
+//     the motion the sweep was compensated with (KfLog::tmot, before the recorder moves it on). The peaks cloud is the same pass over the
+//     slots with the peak bit (getPeaksFilteredPointCloud(peaks = true) + Compensate, :149). The compaction is cloud_step_block's: ballots
+//     per wave and one scan across the waves, row-major over (bearing, slot) - no atomics.
+//   cloud routes (slots_all null): the compensated cloud sits in the scan's xyi (features_cloud_step_body); the peaks cloud is empty there
+//     (radar_driver.cpp:52-56).
+// A cloud that does not fit is cut at the room left (nothing is written past the sequence's region) and the keyframe is dropped whole.
+// (The general branch of cloud_step_block reads the three floats at its output pointer back in lanes that hold no point: with no room left
+// those belong to the next sequence's region - or to the slack at the buffer's end - may be in the middle of being written, and are discarded.)
+__global__ __launch_bounds__(BLOCK_F) void keyframe_cloud_kernel(KfLog L, OdoParams OP, const SeqState* states, const uint32_t* slots_all, const double* trig) {
+  __shared__ __attribute__((aligned(16))) unsigned char lds[FeatLdsC::total];
+  const int q = OP.seq0 + (int)blockIdx.x, tid = threadIdx.x;
+  const SeqState* st = states + q;
+  const int nkf = st->nkf, last = st->last_slot;
+  const bool fused = nkf > 0 && st->ring[nkf - 1] == last;
+  const int* c = L.counts + 4 * (size_t)q;
+  int* cw = L.cloud_word + 4 * (size_t)q;
+  const int rec = c[0], dropped = c[1], used = c[3];
+  if (!fused || dropped != 0 || rec >= L.max_kf) {  // (block-uniform) nothing to write, or a log that takes no more keyframes
+    if (tid == 0) { cw[0] = 0; cw[1] = 0; cw[2] = 0; cw[3] = 0; }
+    return;
+  }
+  const ScanDev* S = reinterpret_cast<const ScanDev*>(OP.scans_base + OP.scan_stride * ((size_t)q * (OP.submap + 1) + last));
+  const int room = max(L.max_points - used, 0);
+  float* dst = L.points + 3 * ((size_t)q * L.max_points + used);
+  int f0 = 0, f1 = 0, n0 = 0, n1 = 0;  // points of the two clouds: found, and written (cut at the room left)
+  if (!slots_all) {
+    f0 = S->n_points;
+    n0 = min(f0, room);
+    const float* src = S->xyi;
+    for (int i = tid; i < 3 * n0; i += BLOCK_F) dst[i] = src[i];
+  } else {
+    const double* tm = L.tmot + 6 * (size_t)q;
+    Aff2 TprevMot;
+    TprevMot.l0 = tm[0]; TprevMot.l1 = tm[1]; TprevMot.l2 = tm[2]; TprevMot.l3 = tm[3]; TprevMot.t0 = tm[4]; TprevMot.t1 = tm[5];
+    double mot[3]; aff_to_xyt(TprevMot, mot);
+    int src = q, compensate = OP.compensate, z_min = 0, k = OP.k;  // the sequence's own row (features_step_body)
+    if (const SeqRow row = seq_row(OP, q)) { src = row->source; compensate = row->compensate; z_min = row->z_min; k = row->k; }
+    const uint32_t* slots = slots_all + (size_t)src * OP.A * OP.k;
+    float bounds[4];
+    PointRegs PR;
+    n0 = cloud_step_block<false>(slots, OP.A, k, OP.k, trig, OP.fp.range_res, OP.fp.min_distance, z_min, dst, min(room, S->cap_points), compensate,
+                                           mot[0], mot[1], mot[2], OP.ccw, reinterpret_cast<int*>(lds + FeatLdsC::red_i), reinterpret_cast<float*>(lds + FeatLdsC::red_f),
+                                           reinterpret_cast<double*>(lds + FeatLdsC::pxy), (int)(CFEAR_CPT_CAP * 8 / (6 * sizeof(double))), bounds, PR, true,
+                                           reinterpret_cast<int*>(lds + FeatLdsC::vst), (int)((FeatLdsC::pxy - FeatLdsC::vst) / sizeof(int)), &f0);
+    if ((L.what & CFEAR_KF_PEAKS) && f0 <= room) {  // (block-uniform)
+      __syncthreads();  // the first pass has read its tables
+      n1 = cloud_step_block<true>(slots, OP.A, k, OP.k, trig, OP.fp.range_res, OP.fp.min_distance, z_min, dst + 3 * (size_t)n0, min(room - n0, S->cap_points), compensate,
+                                   mot[0], mot[1], mot[2], OP.ccw, reinterpret_cast<int*>(lds + FeatLdsC::red_i), reinterpret_cast<float*>(lds + FeatLdsC::red_f),
+                                   reinterpret_cast<double*>(lds + FeatLdsC::pxy), (int)(CFEAR_CPT_CAP * 8 / (6 * sizeof(double))), bounds, PR, true,
+                                   reinterpret_cast<int*>(lds + FeatLdsC::vst), (int)((FeatLdsC::pxy - FeatLdsC::vst) / sizeof(int)), &f1);
+    }
+  }
+  if (tid == 0) { cw[0] = (f0 <= room && f1 <= room - f0) ? 1 : 0; cw[1] = n0; cw[2] = n1; cw[3] = 0; }
+}
 
 __global__ __launch_bounds__(BLOCK_K) void keyframe_record_kernel(KfLog L, const unsigned char* scans_base, size_t scan_stride, int nslots, int seq0, int* flags,
                                                                   const SeqState* states, const double* cov_work /*[B][36]*/) {
@@ -39,7 +101,9 @@ __global__ __launch_bounds__(BLOCK_K) void keyframe_record_kernel(KfLog L, const
     const int rec = c[0], used = c[2];
     const bool with_cells = (L.what & CFEAR_KF_CELLS) != 0;
     // a gap-free prefix: after the first keyframe that did not fit nothing more is recorded
-    const bool fits = c[1] == 0 && rec < L.max_kf && (!with_cells || n <= L.max_cells - used);
+    // (with a point log: the cloud stage in front has written this keyframe's clouds behind the sequence's points and says whether they fit)
+    const int* cw = L.points ? L.cloud_word + 4 * (size_t)q : nullptr;
+    const bool fits = c[1] == 0 && rec < L.max_kf && (!with_cells || n <= L.max_cells - used) && (!cw || cw[0] == 1);
     if (!fits) {
       c[1] = c[1] + 1;
       if (flags) flags[1 + q] |= 4;  // (this sequence's own word: only its workgroups write it, and they run in stream order)
@@ -63,6 +127,11 @@ __global__ __launch_bounds__(BLOCK_K) void keyframe_record_kernel(KfLog L, const
         for (int i = 0; i < 36; i++) nd->information[i] = 0.0;
       }
       L.cell_off[(size_t)q * L.max_kf + rec] = used;
+      if (cw) {
+        int* po = L.point_off + 3 * ((size_t)q * L.max_kf + rec);
+        po[0] = c[3]; po[1] = cw[1]; po[2] = cw[2];
+        c[3] = c[3] + cw[1] + cw[2];
+      }
       c[0] = rec + 1;
       if (with_cells) c[2] = used + n;
       s_dst = with_cells ? used : -1;
@@ -132,6 +201,10 @@ __global__ __launch_bounds__(BLOCK_F) void keyframe_scans_kernel(const KfScanJob
 
 void cfear_launch_keyframe_record(const KfLog& L, const OdoParams& P, int count, hipStream_t st, const SeqState* states, const double* cov_work) {
   hipLaunchKernelGGL(keyframe_record_kernel, dim3(count), dim3(BLOCK_K), 0, st, L, P.scans_base, P.scan_stride, P.submap + 1, P.seq0, P.flags, states, cov_work);
+}
+
+void cfear_launch_keyframe_clouds(const KfLog& L, const OdoParams& P, int count, hipStream_t st, const SeqState* states, const uint32_t* slots, const double* trig) {
+  hipLaunchKernelGGL(keyframe_cloud_kernel, dim3(count), dim3(BLOCK_F), 0, st, L, P, states, slots, trig);
 }
 
 void cfear_launch_keyframe_scans(const KfScanJob* d_jobs, int m, const FeatureParams& P, hipStream_t st) {

@@ -131,6 +131,14 @@ struct cfear_odometry {
   DevBuf<int> d_kf_off;                    // [B][kf_max] a node's first cell in its sequence's cells
   DevBuf<int> d_kf_counts;                 // [B][4] nodes recorded, keyframes dropped, cells used, 0
   DevBuf<double> d_kf_tmot;                // [B][6] the recorder's copy of SeqState::Tmot (KfLog::tmot)
+  // ... and its point log (cfear_odometry_set_keyframe_clouds: kf_what & CFEAR_KF_CLOUD / CFEAR_KF_PEAKS): the cloud stage of keyframes.hip runs
+  // in front of the recorder; with CFEAR_KF_PEAKS the object's filters compute the slots' peak flag
+  int kf_max_points = 0;
+  DevBuf<float> d_kf_points;               // [B][kf_max_points][3] + one point: the general cloud pass reads the point at its output's start back whatever
+                                           // it wrote. With no room left that is the first point of the NEXT sequence's region (which its workgroup may be
+                                           // writing) or, for the last sequence, this slack; the value lands in lanes that hold no point and is discarded
+  DevBuf<int> d_kf_point_off;              // [B][kf_max][3] per node: first point, points of the filtered cloud, of the peaks cloud
+  DevBuf<int> d_kf_cloud_word;             // [B][4] the cloud stage's verdict and counts of the sweep (KfLog::cloud_word)
   // ---- streams (destroyed before everything above) ----
   Stream sf;               // overlap: the filter's
   std::vector<Stream> so;  // ... and the odometry streams
@@ -187,7 +195,8 @@ struct SweepPoints {
   static SweepPoints of_clouds(const float* d_xyi, int cap, const int* d_counts) { SweepPoints S; S.xyi = d_xyi; S.cap = cap; S.counts = d_counts; return S; }
 };
 // one sweep of `count` sequences from P.seq0 on, enqueued on `st`: features, then registration with the stages behind it. timed: three
-// events of the profile around the two (stage_events); consumed: recorded once features has read the points (null: nothing is)
+// events of the profile around the two (stage_events); consumed: recorded once the last stage that reads the points has (features; on an
+// object that records keyframe clouds the cloud stage behind the registration reads the slots again) (null: nothing is)
 __attribute__((visibility("hidden"))) int odo_launch_sweep(cfear_ctx* ctx, cfear_odometry* o, const OdoParams& P, const SweepPoints& src, int count, hipStream_t st,
                                                            bool timed, hipEvent_t consumed = nullptr);
 // the CA-CFAR stage of n_steps sweeps of every sequence into clouds of o->cap_points points each, [step][sequence]
@@ -204,6 +213,16 @@ __attribute__((visibility("hidden"))) int odo_upload_headers(cfear_ctx* ctx, cfe
 // ---- odometry_run.hip: what the keyframe route of pipeline.hip calls ----
 __attribute__((visibility("hidden"))) int odo_ensure_flags(cfear_ctx* ctx, cfear_odometry* o);
 __attribute__((visibility("hidden"))) int odo_kf_clear(cfear_ctx* ctx, cfear_odometry* o);
+// does the object's filter compute the slots' peak flag? (only for a point log with peaks clouds; refused where cfear_tune FILTER_PEAKS = 0 forbids it)
+inline bool odo_filter_peaks(const cfear_odometry* o) { return (o->kf_what & CFEAR_KF_PEAKS) != 0; }
+// (a CA-CFAR object runs no k-strongest filter and its peaks cloud is empty by definition: nothing to refuse there)
+inline int odo_peaks_check(cfear_ctx* ctx, const cfear_odometry* o, const char* what) {
+  if (!odo_filter_peaks(o) || ctx->tune_k1_peaks != 0 || o->filter == CFEAR_FILTER_CACFAR) return CFEAR_OK;
+  char msg[256];
+  snprintf(msg, sizeof(msg), "%s: the object records peaks clouds (CFEAR_KF_PEAKS), which need the filter's peak flag, and cfear_tune FILTER_PEAKS = 0 forbids it: "
+           "set the knob to -1 or 1, or record without CFEAR_KF_PEAKS", what);
+  return cfear_fail(ctx, CFEAR_ERR_INVALID, msg);
+}
 // odometry_seq.hip: cfear_set_params since the device table was built - the rows are checked against the new parameters and the table follows them
 __attribute__((visibility("hidden"))) int odo_seq_resync(cfear_ctx* ctx, cfear_odometry* o, const char* what);
 // before a step / replay / surface call: cfear_set_params since the table was built? The rows are checked against the new parameters

@@ -14,6 +14,7 @@ int odo_kf_clear(cfear_ctx* ctx, cfear_odometry* o) {
   std::vector<double> tm(6 * (size_t)o->B, 0.0);
   for (int q = 0; q < o->B; q++) tm[6 * (size_t)q] = tm[6 * (size_t)q + 3] = 1.0;
   CFEAR_HIP_CHECK(ctx, hipMemsetAsync(o->d_kf_counts, 0, sizeof(int) * 4 * (size_t)o->B, ctx->stream));
+  if (o->d_kf_cloud_word) CFEAR_HIP_CHECK(ctx, hipMemsetAsync(o->d_kf_cloud_word, 0, sizeof(int) * 4 * (size_t)o->B, ctx->stream));  // (the point log with the rest)
   CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(o->d_kf_tmot, tm.data(), sizeof(double) * tm.size(), hipMemcpyHostToDevice, ctx->stream));
   CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // (tm is read until here)
   return CFEAR_OK;
@@ -213,6 +214,7 @@ int cfear_odometry_step_device(cfear_ctx* ctx, cfear_odometry* o, const uint8_t*
   CFEAR_TRY(odo_shape_check(ctx, o, "odometry_step"));
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   CFEAR_TRY(odo_seq_sync(ctx, o, "odometry_step"));
+  CFEAR_TRY(odo_peaks_check(ctx, o, "odometry_step"));
   if (o->filter == CFEAR_FILTER_CACFAR) {  // radar_driver.cpp:52-56, then the cloud route
     if (o->profile) CFEAR_TRY(o->timers.take(ctx, ctx->stream, o->filter_events));
     CFEAR_TRY(odo_launch_cfar(ctx, o, d_polar, 1, o->d_cloud, o->d_cloud_n, o->d_cfar_rows, ctx->stream));
@@ -230,7 +232,7 @@ int cfear_odometry_step_device(cfear_ctx* ctx, cfear_odometry* o, const uint8_t*
   }
   // radar_driver.cpp:58
   if (o->profile) CFEAR_TRY(o->timers.take(ctx, sf, o->filter_events));
-  CFEAR_TRY(cfear_launch_kstrongest(ctx, d_polar, odo_sources(o), o->d_slots[buf], sf, false, o->seq_zmin));  // (once per source sweep, at the smallest z_min of the rows; no peak flag: cloud_step_block does not read it)
+  CFEAR_TRY(cfear_launch_kstrongest(ctx, d_polar, odo_sources(o), o->d_slots[buf], sf, odo_filter_peaks(o), o->seq_zmin));  // (once per source sweep, at the smallest z_min of the rows; no peak flag unless the object records peaks clouds: the feature stage does not read it)
   if (o->profile) CFEAR_TRY(o->timers.take(ctx, sf, o->filter_events));
   if (o->overlap) {
     CFEAR_HIP_CHECK(ctx, hipEventRecord(o->ev_filt[buf], sf));
@@ -247,7 +249,7 @@ int cfear_odometry_step_device(cfear_ctx* ctx, cfear_odometry* o, const uint8_t*
     if (count <= 0) break;
     hipStream_t so = o->overlap ? o->so[i] : ctx->stream;
     if (o->overlap) CFEAR_HIP_CHECK(ctx, hipStreamWaitEvent(so, o->ev_filt[buf], 0));
-    // (ev_free: features has consumed the slot buffer - recorded between the two stages)
+    // (ev_free: features has consumed the slot buffer - recorded between the two stages; behind the cloud stage on an object that records clouds)
     CFEAR_TRY(odo_launch_sweep(ctx, o, P, SweepPoints::of_slots(o->d_slots[buf]), count, so, o->profile, o->overlap ? (hipEvent_t)o->ev_free[buf][i] : nullptr));
   }
   if (o->overlap) o->filt_pending[buf] = true;
@@ -430,7 +432,7 @@ static int replay_impl_queue(cfear_ctx* ctx, cfear_odometry* o, const uint8_t* f
       src = o->rp_polar[b];
     }
     const int frc = cfar ? odo_launch_cfar(ctx, o, src, cnt, o->rp_cloud[b], o->rp_cloud_n[b], o->rp_cfar_rows, o->rp_stream)  // radar_driver.cpp:52-56
-                         : cfear_launch_kstrongest(ctx, src, cnt * nsrc, o->rp_slots[b], o->rp_stream, false, o->seq_zmin);  // radar_driver.cpp:58, pose-independent
+                         : cfear_launch_kstrongest(ctx, src, cnt * nsrc, o->rp_slots[b], o->rp_stream, odo_filter_peaks(o), o->seq_zmin);  // radar_driver.cpp:58, pose-independent
     if (frc != CFEAR_OK) return frc;
     CFEAR_HIP_CHECK(ctx, hipEventRecord(o->rp_filt[b], o->rp_stream));
     return CFEAR_OK;
@@ -486,6 +488,7 @@ static int replay_check(cfear_ctx* ctx, cfear_odometry* o, const uint8_t* frames
   CFEAR_TRY(odo_shape_check(ctx, o, "odometry_replay"));
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   CFEAR_TRY(odo_seq_sync(ctx, o, "odometry_replay"));
+  CFEAR_TRY(odo_peaks_check(ctx, o, "odometry_replay"));
   // CA-CFAR reads the images as dwords: every chunk of the replay starts a whole number of sweeps (of B images, or of the sources the sequences'
   // detectors share) after `frames`, so the base and the sweep size decide the alignment of all of them - refused here, before any chunk has
   // advanced the sequences' state

@@ -492,6 +492,8 @@ static KfLog odo_kf_log(const cfear_odometry* o) {
   KfLog L;
   L.what = o->kf_what; L.max_kf = o->kf_max; L.max_cells = o->kf_max_cells; L.pad_ = 0;
   L.nodes = o->d_kf_nodes; L.cells = o->d_kf_cells; L.cell_off = o->d_kf_off; L.counts = o->d_kf_counts; L.tmot = o->d_kf_tmot;
+  L.max_points = o->kf_max_points; L.pad2_ = 0;
+  L.points = o->d_kf_points; L.point_off = o->d_kf_point_off; L.cloud_word = o->d_kf_cloud_word;
   return L;
 }
 // the kernel parameters of one odometry step of `o` under the context's current settings
@@ -587,7 +589,8 @@ static void launch_register_kernel(const OdoParams& P_in, int count, hipStream_t
 }
 // ... and behind it, on the same stream, the cost-sampling stage (estimate_cov_by_sampling) and / or the copy of every sequence's cov_current
 // (the replay's per-sweep covariances): before the next sweep's features kernel may reuse a slot the registration read
-static void launch_register_step(const OdoParams& P, int count, hipStream_t st, cfear_odometry* o) {
+// src / trig: what the feature stage of this sweep read (the cloud stage of the keyframe log reads the slots again)
+static void launch_register_step(const OdoParams& P, int count, hipStream_t st, cfear_odometry* o, const SweepPoints& src, const double* trig) {
   launch_register_kernel(P, count, st, o);
   if (P.cs.m || P.cs.cov_out) {  // (cs.m: sampling on; cs.ctx alone: the surface recording only)
     if (CFEAR_COV_SAMPLING_NAIVE || P.rp.nn_tie != 0)  // (cov_sample_general)
@@ -597,6 +600,8 @@ static void launch_register_step(const OdoParams& P, int count, hipStream_t st, 
   }
   // ... and the keyframe recorder (AddToGraph, :234-248 behind the sampling of :202-208: cov_work holds cov_current): the same sequences on the
   // same stream, so the sub-batches of the overlap mode need nothing extra
+  // (with a point log the cloud stage goes first: it reads KfLog::tmot before the recorder moves it on, and the recorder commits its verdict)
+  if (o->kf_what & CFEAR_KF_CLOUD) cfear_launch_keyframe_clouds(odo_kf_log(o), P, count, st, o->d_states, src.slots, trig);
   if (o->kf_what) cfear_launch_keyframe_record(odo_kf_log(o), P, count, st, o->d_states, o->d_cov_work);
 }
 // one sweep of `count` sequences from P.seq0 on (odometry_obj.h): the features stage from the filter's slots or from clouds on the device, then the
@@ -609,12 +614,20 @@ int odo_launch_sweep(cfear_ctx* ctx, cfear_odometry* o, const OdoParams& P, cons
     hipLaunchKernelGGL(features_step_kernel<true>, dim3(count), dim3(BLOCK_F), 0, st, src.slots, ctx->d_trig, P, o->d_states, nullptr, o->d_scratch_hdr);
   else
     hipLaunchKernelGGL(features_step_kernel<false>, dim3(count), dim3(BLOCK_F), 0, st, src.slots, ctx->d_trig, P, o->d_states, nullptr, o->d_scratch_hdr);
-  if (consumed) {  // (the overlap mode's ev_free: the slot buffer may be filtered into again)
+  // the overlap mode's ev_free: the slot buffer may be filtered into again. An object that records keyframe clouds reads the slots once more
+  // behind the registration (the cloud stage), so there the event follows that stage: building the clouds in front of the registration into a
+  // staging area instead would build them for every sweep, not only for those that fuse, and keep 2 * A * k points per sequence beside the log
+  const bool late = consumed && (o->kf_what & CFEAR_KF_CLOUD) && src.slots;
+  if (consumed && !late) {
     const hipError_t e = hipEventRecord(consumed, st);
     if (e != hipSuccess) return cfear_fail(ctx, CFEAR_ERR_HIP, "hipEventRecord(o->ev_free[buf][i], so)", e);
   }
   if (timed) CFEAR_TRY(o->timers.take(ctx, st, o->stage_events));
-  launch_register_step(P, count, st, o);
+  launch_register_step(P, count, st, o, src, ctx->d_trig);
+  if (late) {
+    const hipError_t e = hipEventRecord(consumed, st);
+    if (e != hipSuccess) return cfear_fail(ctx, CFEAR_ERR_HIP, "hipEventRecord(o->ev_free[buf][i], so)", e);
+  }
   if (timed) CFEAR_TRY(o->timers.take(ctx, st, o->stage_events));
   return CFEAR_OK;
 }
@@ -1556,6 +1569,11 @@ int cfear_odometry_status(cfear_ctx* ctx, cfear_odometry* o, int32_t* per_sequen
 }
 
 // ---- the keyframe graph (AddToGraph, odometrykeyframefuser.cpp:428-445; keyframes.hip) -----------------------------------------------
+static void odo_kf_release_points(cfear_odometry* o) {
+  o->kf_what &= ~(CFEAR_KF_CLOUD | CFEAR_KF_PEAKS);
+  o->kf_max_points = 0;
+  o->d_kf_points.release(); o->d_kf_point_off.release(); o->d_kf_cloud_word.release();
+}
 int cfear_odometry_set_keyframe_recording(cfear_ctx* ctx, cfear_odometry* o, int what, int max_keyframes, int max_cells) {
   if (!ctx || !o) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_set_keyframe_recording: bad argument");
   if (what != 0 && what != CFEAR_KF_NODES && what != (CFEAR_KF_NODES | CFEAR_KF_CELLS))
@@ -1575,6 +1593,7 @@ int cfear_odometry_set_keyframe_recording(cfear_ctx* ctx, cfear_odometry* o, int
   }
   o->kf_what = 0;
   o->d_kf_nodes.release(); o->d_kf_cells.release(); o->d_kf_off.release(); o->d_kf_counts.release(); o->d_kf_tmot.release();
+  odo_kf_release_points(o);  // (sized by max_keyframes: the point log goes with the nodes; cfear_odometry_set_keyframe_clouds switches it on again)
   if (!what) return CFEAR_OK;
   const size_t B = (size_t)o->B;
   const char* msg = "hipMalloc keyframe log";
@@ -1715,6 +1734,141 @@ int cfear_odometry_keyframe_scans(cfear_ctx* ctx, cfear_odometry* o, int sequenc
   cfear_pool_free(ctx, work, work_bytes);
   if (rc != CFEAR_OK)
     for (int i = 0; i < m; i++) { cfear_scan_release(ctx, scans[i]); scans[i] = nullptr; }
+  return rc;
+}
+
+// ---- the point log: cloud_nopeaks_ / cloud_peaks_ of every node (types.h:93-143; keyframe_cloud_kernel) ----------------------------------
+int cfear_odometry_set_keyframe_clouds(cfear_ctx* ctx, cfear_odometry* o, int what, int max_points) {
+  if (!ctx || !o) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_set_keyframe_clouds: bad argument");
+  if (what != 0 && what != CFEAR_KF_CLOUD && what != (CFEAR_KF_CLOUD | CFEAR_KF_PEAKS))
+    return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_set_keyframe_clouds: what must be 0, CFEAR_KF_CLOUD or CFEAR_KF_CLOUD | CFEAR_KF_PEAKS (the peaks cloud is recorded "
+                      "beside the filtered cloud, not alone)");
+  if (what && !(o->kf_what & CFEAR_KF_NODES))
+    return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_set_keyframe_clouds: the clouds belong to recorded nodes - switch node recording on first "
+                      "(cfear_odometry_set_keyframe_recording with CFEAR_KF_NODES)");
+  if (what && max_points < 1) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_set_keyframe_clouds: max_points must be at least 1");
+  if ((what & CFEAR_KF_PEAKS) && ctx->tune_k1_peaks == 0 && o->filter != CFEAR_FILTER_CACFAR)
+    return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_set_keyframe_clouds: CFEAR_KF_PEAKS needs the filter's peak flag and cfear_tune FILTER_PEAKS = 0 forbids it: set the "
+                      "knob to -1 or 1, or record without CFEAR_KF_PEAKS");
+  if (what) CFEAR_SEQ_TRY(ctx, cfear_seq_fresh_check(odo_seq_object(ctx, o), "odometry_set_keyframe_clouds", msg));
+  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  CFEAR_TRY(odo_join(ctx, o));
+  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // no cloud stage is running: the buffers may go
+  odo_kf_release_points(o);
+  if (!what) return CFEAR_OK;
+  const size_t B = (size_t)o->B;
+  {  // refuse what cannot fit with the numbers (as cfear_odometry_create does)
+    size_t free_b = 0, total_b = 0;
+    const size_t per_seq = sizeof(float) * 3 * (size_t)max_points + sizeof(int) * (3 * (size_t)o->kf_max + 4);
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && per_seq * B > free_b) {
+      char msg[384];
+      snprintf(msg, sizeof(msg), "odometry_set_keyframe_clouds: %d sequences x %.2f MB (%d points of 12 bytes + the offsets of %d nodes per sequence) = %.2f GB, %.2f GB "
+               "free: at most %zu points per sequence fit", o->B, per_seq / 1048576.0, max_points, o->kf_max, per_seq * (double)B / 1073741824.0,
+               free_b / 1073741824.0, free_b / B / 12);
+      return cfear_fail(ctx, CFEAR_ERR_NOMEM, msg);
+    }
+  }
+  const char* msg = "hipMalloc keyframe point log";
+  // (+ one point: cloud_step_block's general branch reads the first point of its output back whatever it wrote - at the log's very end too)
+  CFEAR_TRY(o->d_kf_points.ensure(ctx, 3 * (B * (size_t)max_points + 1), msg));
+  CFEAR_TRY(o->d_kf_point_off.ensure(ctx, 3 * B * (size_t)o->kf_max, msg));
+  CFEAR_TRY(o->d_kf_cloud_word.ensure(ctx, 4 * B, msg));
+  o->kf_max_points = max_points;
+  CFEAR_TRY(odo_kf_clear(ctx, o));  // (no sweep has run: the rest of the log is empty already)
+  o->kf_what |= what;
+  return CFEAR_OK;
+}
+
+// the reading calls' start for the point log: odo_kf_read, then the log has clouds (and, for peaks = 1, peaks clouds)
+static int odo_kf_read_points(cfear_ctx* ctx, cfear_odometry* o, const char* what, int sequence, int peaks, int cnt[4]) {
+  CFEAR_TRY(odo_kf_read(ctx, o, what, sequence, cnt));
+  char msg[200];
+  if (!(o->kf_what & CFEAR_KF_CLOUD)) {
+    snprintf(msg, sizeof(msg), "%s: the log was switched on without CFEAR_KF_CLOUD (cfear_odometry_set_keyframe_clouds)", what);
+    return cfear_fail(ctx, CFEAR_ERR_INVALID, msg);
+  }
+  if (peaks != 0 && peaks != 1) { snprintf(msg, sizeof(msg), "%s: peaks must be 0 or 1", what); return cfear_fail(ctx, CFEAR_ERR_INVALID, msg); }
+  if (peaks && !(o->kf_what & CFEAR_KF_PEAKS)) {
+    snprintf(msg, sizeof(msg), "%s: the log was switched on without CFEAR_KF_PEAKS", what);
+    return cfear_fail(ctx, CFEAR_ERR_INVALID, msg);
+  }
+  return CFEAR_OK;
+}
+// (first point, points of the filtered cloud, of the peaks cloud) of nodes first .. first + m - 1 of a sequence
+static int odo_kf_point_offsets(cfear_ctx* ctx, cfear_odometry* o, int sequence, int first, int m, std::vector<int>& off) {
+  off.assign(3 * (size_t)std::max(m, 0), 0);
+  if (m > 0)
+    CFEAR_HIP_CHECK(ctx, hipMemcpy(off.data(), o->d_kf_point_off + 3 * ((size_t)sequence * o->kf_max + first), sizeof(int) * 3 * (size_t)m, hipMemcpyDeviceToHost));
+  return CFEAR_OK;
+}
+
+int cfear_odometry_keyframe_cloud_sizes(cfear_ctx* ctx, cfear_odometry* o, int sequence, int first, int32_t* n_cloud, int32_t* n_peaks, int capacity, int* n) {
+  int cnt[4];
+  CFEAR_TRY(odo_kf_read_points(ctx, o, "odometry_keyframe_cloud_sizes", sequence, 0, cnt));
+  if (first < 0 || capacity < 0) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_keyframe_cloud_sizes: bad argument");
+  if (n) *n = cnt[0];
+  const int m = std::min(capacity, cnt[0] - first);
+  std::vector<int> off;
+  CFEAR_TRY(odo_kf_point_offsets(ctx, o, sequence, first, m, off));
+  for (int i = 0; i < m; i++) {
+    if (n_cloud) n_cloud[i] = off[3 * (size_t)i + 1];
+    if (n_peaks) n_peaks[i] = off[3 * (size_t)i + 2];
+  }
+  return CFEAR_OK;
+}
+
+int cfear_odometry_keyframe_cloud(cfear_ctx* ctx, cfear_odometry* o, int sequence, int index, int peaks, float* xyi, int capacity, int* n) {
+  int cnt[4];
+  CFEAR_TRY(odo_kf_read_points(ctx, o, "odometry_keyframe_cloud", sequence, peaks, cnt));
+  if (index < 0 || index >= cnt[0] || capacity < 0 || (capacity > 0 && !xyi)) {
+    char msg[160];
+    snprintf(msg, sizeof(msg), "odometry_keyframe_cloud: keyframe %d of sequence %d (%d recorded), capacity %d", index, sequence, cnt[0], capacity);
+    return cfear_fail(ctx, CFEAR_ERR_INVALID, msg);
+  }
+  std::vector<int> off;
+  CFEAR_TRY(odo_kf_point_offsets(ctx, o, sequence, index, 1, off));
+  const int np = peaks ? off[2] : off[1];
+  const size_t at = (size_t)sequence * o->kf_max_points + off[0] + (peaks ? off[1] : 0);
+  if (n) *n = np;
+  const int m = std::min(capacity, np);
+  if (m > 0) CFEAR_HIP_CHECK(ctx, hipMemcpy(xyi, o->d_kf_points + 3 * at, sizeof(float) * 3 * (size_t)m, hipMemcpyDeviceToHost));
+  return CFEAR_OK;
+}
+
+int cfear_odometry_keyframe_clouds(cfear_ctx* ctx, cfear_odometry* o, int sequence, const int32_t* indices, int m, int peaks, cfear_cloud** clouds) {
+  int cnt[4];
+  CFEAR_TRY(odo_kf_read_points(ctx, o, "odometry_keyframe_clouds", sequence, peaks, cnt));
+  if (!indices || !clouds || m < 1) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_keyframe_clouds: bad argument");
+  for (int i = 0; i < m; i++) clouds[i] = nullptr;
+  for (int i = 0; i < m; i++)
+    if (indices[i] < 0 || indices[i] >= cnt[0]) {
+      char msg[160];
+      snprintf(msg, sizeof(msg), "odometry_keyframe_clouds: indices[%d] = %d, sequence %d has recorded %d keyframes", i, indices[i], sequence, cnt[0]);
+      return cfear_fail(ctx, CFEAR_ERR_INVALID, msg);
+    }
+  std::vector<int> off;
+  CFEAR_TRY(odo_kf_point_offsets(ctx, o, sequence, 0, cnt[0], off));
+  std::vector<int> counts((size_t)m);  // (read by the copies until the synchronisation below)
+  int rc = CFEAR_OK;
+  hipError_t e = hipSuccess;
+  for (int i = 0; i < m && rc == CFEAR_OK && e == hipSuccess; i++) {
+    const int* po = off.data() + 3 * (size_t)indices[i];
+    const int np = peaks ? po[2] : po[1];
+    const size_t at = (size_t)sequence * o->kf_max_points + po[0] + (peaks ? po[1] : 0);
+    counts[(size_t)i] = np;
+    rc = cfear_cloud_alloc(ctx, np, &clouds[i]);
+    if (rc != CFEAR_OK) break;
+    if (np > 0) e = hipMemcpyAsync(clouds[i]->d_xyi, o->d_kf_points + 3 * at, sizeof(float) * 3 * (size_t)np, hipMemcpyDeviceToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(clouds[i]->d_n, &counts[(size_t)i], sizeof(int), hipMemcpyHostToDevice, ctx->stream);
+  }
+  if (rc == CFEAR_OK) {
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) rc = cfear_fail(ctx, CFEAR_ERR_HIP, "odometry_keyframe_clouds", e);
+  } else {
+    (void)hipStreamSynchronize(ctx->stream);  // (counts is read until here)
+  }
+  if (rc != CFEAR_OK)
+    for (int i = 0; i < m; i++) { cfear_cloud_release(ctx, clouds[i]); clouds[i] = nullptr; }
   return rc;
 }
 

@@ -195,8 +195,44 @@ def read_g2o(path):
     return nodes
 
 
+def write_keyframe_clouds(path, clouds, peaks=None):
+    """The recorded clouds of one run as one .npz: clouds / peaks are per sequence a list of float32 [n, 3] arrays, one per node
+    (capi.Odometry.keyframe_cloud(q, i) / (q, i, peaks=True); peaks None: a run without peaks clouds). Per sequence q the file holds the
+    packed points `cloud_q` [N, 3] and `cloud_off_q` [nodes + 1] (node i is cloud_q[off[i]:off[i + 1]]), and `peaks_q` / `peaks_off_q`
+    alike. read_keyframe_clouds gives back the same bits. Pure Python (no device)."""
+    arrays = {"n_sequences": np.array(len(clouds), dtype=np.int64), "has_peaks": np.array(0 if peaks is None else 1, dtype=np.int64)}
+    if peaks is not None and len(peaks) != len(clouds):
+        raise ValueError("write_keyframe_clouds: %d sequences of clouds, %d of peaks" % (len(clouds), len(peaks)))
+    for name, per_seq in (("cloud", clouds), ("peaks", peaks)):
+        if per_seq is None:
+            continue
+        for q, lst in enumerate(per_seq):
+            lst = [np.ascontiguousarray(c, dtype=np.float32).reshape(-1, 3) for c in lst]
+            arrays["%s_off_%d" % (name, q)] = np.concatenate([[0], np.cumsum([len(c) for c in lst])]).astype(np.int64)
+            arrays["%s_%d" % (name, q)] = np.concatenate(lst, axis=0) if lst else np.zeros((0, 3), dtype=np.float32)
+    with open(path, "wb") as f:  # (a file object: np.savez would append .npz to a bare name)
+        np.savez(f, **arrays)
+
+
+def read_keyframe_clouds(path):
+    """write_keyframe_clouds' file -> (clouds, peaks): per sequence a list of float32 [n, 3] arrays, one per node; peaks is None for a file
+    without peaks clouds."""
+    out = []
+    with np.load(path) as z:
+        for name in ("cloud", "peaks"):
+            if name == "peaks" and not int(z["has_peaks"]):
+                out.append(None)
+                continue
+            per_seq = []
+            for q in range(int(z["n_sequences"])):
+                off, pts = z["%s_off_%d" % (name, q)], z["%s_%d" % (name, q)]
+                per_seq.append([np.array(pts[off[i]:off[i + 1]]) for i in range(len(off) - 1)])
+            out.append(per_seq)
+    return out[0], out[1]
+
+
 def replay_grid(frames, rows, A=None, R=None, gt=None, device=0, piece=256, context_params=None, options=None, drift_on="host", keyframes=None,
-                max_keyframes=None, max_cells=None):
+                max_keyframes=None, max_cells=None, max_points=None):
     """One recording under len(rows) parameter sets in one batched odometry object: frames uint8 [n, A, R], rows a list of capi.Params that
     agree in the object-wide fields (param_grid of one base does; k_strongest and submap_scan_size may be axes: the context then runs with
     the largest of each, grid_context_params, unless context_params says otherwise; so may cost: rows that differ from the context in cost
@@ -210,11 +246,13 @@ def replay_grid(frames, rows, A=None, R=None, gt=None, device=0, piece=256, cont
     default n: every sweep may fuse; max_cells per row, default 256 * n - 18 KB per sweep and row; a scan of the reference's presets has 150-400
     cells and about every second sweep fuses: size it yourself for a grid of many rows or dense scans, `keyframes_dropped` says when it was too small) and add `keyframes`: a list of
     per-row node arrays (KEYFRAME_NODE_DTYPE), `keyframes_dropped` [rows] and, with "cells", `keyframe_cells`: per row a list of cell
-    arrays (KEYFRAME_CELL_DTYPE), one per node."""
+    arrays (KEYFRAME_CELL_DTYPE), one per node. keyframes="clouds": the nodes and their two clouds (capi.KF_CLOUD | capi.KF_PEAKS; max_points per
+    row, default n * A * k_strongest of the context - 12 bytes a point: size it yourself for a long recording) -> `keyframe_clouds` and
+    `keyframe_peaks`: per row a list of float32 [points, 3] arrays (x, y, intensity), one per node - what write_keyframe_clouds takes."""
     if drift_on not in ("host", "device"):
         raise ValueError("replay_grid: drift_on is 'host' or 'device'")
-    if keyframes not in (None, "nodes", "cells"):
-        raise ValueError("replay_grid: keyframes is None, 'nodes' or 'cells'")
+    if keyframes not in (None, "nodes", "cells", "clouds"):
+        raise ValueError("replay_grid: keyframes is None, 'nodes', 'cells' or 'clouds'")
     frames = np.ascontiguousarray(frames, dtype=np.uint8)
     n, A, R = frames.shape
     rows = list(rows)
@@ -239,8 +277,9 @@ def replay_grid(frames, rows, A=None, R=None, gt=None, device=0, piece=256, cont
                 raise ValueError("replay_grid: %d option sets for %d rows" % (len(opts), len(rows)))
             odo.set_fuser_options(opts)
         if keyframes is not None:
-            odo.record_keyframes(capi.KF_NODES | (capi.KF_CELLS if keyframes == "cells" else 0), max_keyframes if max_keyframes is not None else n,
-                                 max_cells if max_cells is not None else 256 * n)
+            what = capi.KF_NODES | {"nodes": 0, "cells": capi.KF_CELLS, "clouds": capi.KF_CLOUD | capi.KF_PEAKS}[keyframes]
+            odo.record_keyframes(what, max_keyframes if max_keyframes is not None else n, max_cells if max_cells is not None else 256 * n,
+                                 max_points if max_points is not None else n * A * int(cpar.k_strongest))
         recs = [odo.replay_host(frames[t0:t0 + piece, None]) for t0 in range(0, n, piece)]
         rec = np.concatenate(recs, axis=0)
         poses = np.array(rec["pose"])
@@ -249,6 +288,9 @@ def replay_grid(frames, rows, A=None, R=None, gt=None, device=0, piece=256, cont
             graph = {"keyframes": [odo.keyframes(q) for q in range(len(rows))], "keyframes_dropped": odo.keyframe_counts()[1]}
             if keyframes == "cells":
                 graph["keyframe_cells"] = [[odo.keyframe_cells(q, i) for i in range(len(nodes))] for q, nodes in enumerate(graph["keyframes"])]
+            if keyframes == "clouds":
+                graph["keyframe_clouds"] = [[odo.keyframe_cloud(q, i) for i in range(len(nodes))] for q, nodes in enumerate(graph["keyframes"])]
+                graph["keyframe_peaks"] = [[odo.keyframe_cloud(q, i, peaks=True) for i in range(len(nodes))] for q, nodes in enumerate(graph["keyframes"])]
         scored = None
         if gt is not None and drift_on == "device":
             plan = ctx.drift_plan(np.asarray(gt)[:n])
@@ -312,9 +354,14 @@ def main(argv=None):
     ap.add_argument("--store_graph", default=None, metavar="PATH",
                     help="record the keyframe graph on the device (offline_odometry --store_graph) and write it to PATH as g2o text (write_g2o)")
     ap.add_argument("--max_keyframes", type=int, default=65536, help="with --store_graph: nodes the log holds (later keyframes are dropped and reported)")
+    ap.add_argument("--store_clouds", default=None, metavar="PATH",
+                    help="with --store_graph: also record every node's motion-compensated filtered and peaks cloud and write them to PATH (.npz, write_keyframe_clouds)")
+    ap.add_argument("--max_points", type=int, default=16777216, help="with --store_clouds: points the log holds, 12 bytes each (later keyframes are dropped and reported)")
     ap.add_argument("--trace", action="store_true",
                     help="keep per-sweep poses, Register summaries (outer / inner iteration counts, residuals), keyframe and cell counts in the result")
     args = ap.parse_args(argv)
+    if args.store_clouds and not args.store_graph:
+        ap.error("--store_clouds needs --store_graph (the clouds belong to the graph's nodes)")
     cost = {"P2P": 0, "P2L": 1, "P2D": 2}[args.cost_type]
     loss = {"None": 0, "Huber": 1, "Cauchy": 2, "SoftLOne": 3, "Combined": 4, "Tukey": 5}[args.loss_type]
     import time
@@ -359,7 +406,7 @@ def main(argv=None):
             ctx = capi.Context(p, img.shape[0], img.shape[1], device=args.device)
             odo = ctx.odometry(1)
             if args.store_graph:
-                odo.record_keyframes(capi.KF_NODES, args.max_keyframes, 0)
+                odo.record_keyframes(capi.KF_NODES | (capi.KF_CLOUD | capi.KF_PEAKS if args.store_clouds else 0), args.max_keyframes, 0, args.max_points)
             buf = ctx.pinned((max(1, args.piece), 1, img.shape[0], img.shape[1]))
         buf[fill, 0] = img
         fill += 1
@@ -390,6 +437,11 @@ def main(argv=None):
         write_g2o(args.store_graph, nodes)
         out["keyframes"] = int(len(nodes))
         out["keyframes_dropped"] = int(odo.keyframe_counts()[1][0])
+        if args.store_clouds:
+            write_keyframe_clouds(args.store_clouds, [[odo.keyframe_cloud(0, i) for i in range(len(nodes))]],
+                                  [[odo.keyframe_cloud(0, i, peaks=True) for i in range(len(nodes))]])
+            nc, npk = odo.keyframe_cloud_sizes(0)
+            out["cloud_points"], out["peaks_points"] = int(nc.sum()), int(npk.sum())
     print(json.dumps(out))
     if args.trace:
         out["poses"] = np.array(est)

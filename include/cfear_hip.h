@@ -132,7 +132,8 @@ int cfear_synchronize(cfear_ctx* ctx);
  * FILTER_PEAKS (default -1 = automatic): whether the k-strongest filter runs AxialNonMaxSupress and sets the peak flag, bit 25 of a slot. Automatic:
  * every entry that hands slots or a peaks cloud to the caller computes it (cfear_kstrongest_device / _host, cfear_time_kstrongest, cfear_filter_polar*);
  * the filters inside cfear_odometry_step_* / _replay_* do not - their slot buffers are internal and the cloud pass of those routes reads the valid
- * bit, the range and the intensity only, as the reference's odometry never reads cloud_peaks - and leave the bit 0. 1 = always computed, 0 = never
+ * bit, the range and the intensity only, as the reference's odometry never reads cloud_peaks - and leave the bit 0, unless the object records
+ * peaks clouds (cfear_odometry_set_keyframe_clouds with CFEAR_KF_PEAKS: its filters compute the flag). 1 = always computed, 0 = never
  * (the per-call entries included: their peak bits are then 0 and a peaks cloud is empty; for A/B timing and tests). Bits 0..24 do not depend on it. */
 enum { CFEAR_TUNE_FILTER_OCCUPANCY = 1, CFEAR_TUNE_FILTER_ROWS_PER_WAVE = 2, CFEAR_TUNE_ODOMETRY_OVERLAP = 3,
        CFEAR_TUNE_REPLAY_PERSISTENT_MAX = 4, CFEAR_TUNE_FILTER_CUS = 5, CFEAR_TUNE_REPEAT_SHORTCUT = 6, CFEAR_TUNE_MAX_CELLS = 7,
@@ -150,7 +151,7 @@ int cfear_kstrongest_launch_shape(cfear_ctx* ctx, int n_scans, int* rows_per_wav
  * Packed slot: bits 0..15 range bin | 16..23 intensity | 24 valid | 25 peak (AxialNonMaxSupress).
  * Per azimuth row k slots in ascending (intensity, range) order, unused slots = 0.
  * Bit 25 is set in the slots these entry points return. The internal slot buffers of the batched odometry routes (step, replay) are
- * filtered without the suppression and hold 0 there (cfear_tune FILTER_PEAKS). */
+ * filtered without the suppression and hold 0 there (cfear_tune FILTER_PEAKS) unless the object records peaks clouds (CFEAR_KF_PEAKS). */
 #define CFEAR_SLOT_RANGE(s) ((int)((s) & 0xFFFFu))
 #define CFEAR_SLOT_INTENSITY(s) ((int)(((s) >> 16) & 0xFFu))
 #define CFEAR_SLOT_VALID(s) ((int)(((s) >> 24) & 1u))
@@ -607,7 +608,8 @@ void cfear_host_free(cfear_ctx* ctx, void* p);
  * into the new keyframe's frame; offline_odometry --store_graph hands the result to the SLAM system downstream. With recording on, a
  * stage of its own behind the registration stage (and the cost sampling) appends the node - and the scan's cells - of every sequence
  * that fused to that sequence's log on the device: no host round trip per sweep, no change to any other kernel. cloud_nopeaks_ /
- * cloud_peaks_ are not recorded (the k-strongest routes never write the compensated cloud), nor Tgt / the stamp (`sweep` stands in). */
+ * cloud_peaks_ (types.h:93-143) are recorded by a stage of their own when asked for (cfear_odometry_set_keyframe_clouds below); Tgt and
+ * the stamp are not (`sweep` stands in). */
 typedef struct cfear_keyframe_node {
   int32_t index;          /* RadarScan::idx_: 0, 1, 2 ... per sequence since cfear_odometry_create / cfear_odometry_reset */
   int32_t sweep;          /* the sweep of the sequence that fused (0-based since create / reset): the stamp's stand-in */
@@ -628,6 +630,8 @@ typedef struct cfear_keyframe_cell {
 } cfear_keyframe_cell;    /* 72 bytes */
 #define CFEAR_KF_NODES 1
 #define CFEAR_KF_CELLS 2
+#define CFEAR_KF_CLOUD 4 /* cfear_odometry_set_keyframe_clouds: the motion-compensated filtered cloud of every node (cloud_nopeaks_) */
+#define CFEAR_KF_PEAKS 8 /* ... and its motion-compensated peaks cloud (cloud_peaks_); needs CFEAR_KF_CLOUD */
 /* The rule of AddToGraph :435-440, host only (no context, no device; the recorder runs the same function): from = the new keyframe's
  * pose, to = the previous one's, cov6 = cov_current of the sweep that fused -> t_be = Tfrom^-1 * Tto as (x, y, theta) and information =
  * C^-1 with C = cov6 whose leading 3x3 block is turned by the rotation of Tfrom^-1 (only that block: the (0,5) / (5,0) terms stay, as in
@@ -657,6 +661,35 @@ int cfear_odometry_keyframe_cells(cfear_ctx* ctx, cfear_odometry* odo, int seque
  * them). Memory from the context's pool; release each with cfear_scan_release. CFEAR_ERR_INVALID for an index outside the recorded
  * prefix or a log without CFEAR_KF_CELLS, CFEAR_ERR_EMPTY for a keyframe without cells; nothing is created then. Synchronous. */
 int cfear_odometry_keyframe_scans(cfear_ctx* ctx, cfear_odometry* odo, int sequence, const int32_t* indices, int m, cfear_scan** scans);
+/* The two clouds of a node: scan_ = RadarScan(Tcurrent, TprevMot, cloud_peaks, cloud, ...) (odometrykeyframefuser.cpp:234-248) keeps the
+ * motion-compensated filtered cloud (cloud_nopeaks_, :147) and the motion-compensated peaks cloud (cloud_peaks_, :149; types.h:93-143,
+ * types.cpp:76-86). what: 0 = off (releases the point log; allowed at any time), CFEAR_KF_CLOUD, or CFEAR_KF_CLOUD | CFEAR_KF_PEAKS;
+ * max_points: points per sequence, summed over both clouds of all its keyframes (12 bytes each). Switching on needs node recording
+ * (cfear_odometry_set_keyframe_recording with CFEAR_KF_NODES, which also releases the point log whenever it is called) and, like it, an
+ * object that has processed no sweep since create / reset; an object whose log cannot fit the device is refused with the per-sequence
+ * footprint in the message. While on, a stage in front of the recorder writes, for every sequence that fused:
+ *   the filtered cloud - exactly the points the sweep's cells were built from, in the reference's order (row-major over bearing and slot,
+ *     after the drop at range <= ceil(min_distance / range_res), radar_filters.cpp:309-337), compensated with the node's `motion`; on the
+ *     CA-CFAR / cfear_odometry_step_cloud_device routes the compensated input cloud;
+ *   the peaks cloud - the same pass over the slots with the peak bit (getPeaksFilteredPointCloud(peaks = true) + Compensate); such an
+ *     object's filter computes the flag (cfear_tune FILTER_PEAKS = 0 forced together with CFEAR_KF_PEAKS is refused, by this call and by the step / replay
+ *     entries: CFEAR_ERR_INVALID; not on a CA-CFAR object, which runs no such filter).
+ *     Bits 0..24 of the slots do not depend on it: poses, records, nodes and cells are those of an object without clouds, bit for bit.
+ *     On the cloud routes the peaks cloud has 0 points, as the reference's (radar_driver.cpp:52-56).
+ * A keyframe whose clouds do not fit is dropped whole - node, cells and clouds - with every later one, as for cells (a gap-free prefix,
+ * `dropped`, status bit 2); the odometry is untouched. cfear_odometry_reset empties the point log and keeps the setting. With
+ * ODOMETRY_OVERLAP streams the slot buffer is released to the next filter behind this stage instead of behind the feature stage. */
+int cfear_odometry_set_keyframe_clouds(cfear_ctx* ctx, cfear_odometry* odo, int what, int max_points);
+/* Points of the two clouds of nodes first, first + 1 ... of one sequence: at most `capacity` entries of each array (either may be NULL)
+ * are written; *n = the nodes recorded. n_peaks is 0 throughout on a log without CFEAR_KF_PEAKS. CFEAR_ERR_INVALID without CFEAR_KF_CLOUD. */
+int cfear_odometry_keyframe_cloud_sizes(cfear_ctx* ctx, cfear_odometry* odo, int sequence, int first, int32_t* n_cloud, int32_t* n_peaks, int capacity, int* n);
+/* One cloud of keyframe `index` to the host: x, y, intensity per point as cfear_cloud_download; peaks = 0: the filtered cloud, 1: the
+ * peaks cloud. At most `capacity` points are written; *n = the cloud's points. CFEAR_ERR_INVALID for an index outside the recorded prefix,
+ * a log without CFEAR_KF_CLOUD, or peaks = 1 on a log without CFEAR_KF_PEAKS. */
+int cfear_odometry_keyframe_cloud(cfear_ctx* ctx, cfear_odometry* odo, int sequence, int index, int peaks, float* xyi, int capacity, int* n);
+/* m clouds of one sequence, device to device, as handles of the context's pool: ready for cfear_scan_create (a map at any res),
+ * cfear_cloud_download and cfear_cloud_release. Errors as above; nothing is created then. Synchronous. */
+int cfear_odometry_keyframe_clouds(cfear_ctx* ctx, cfear_odometry* odo, int sequence, const int32_t* indices, int m, int peaks, cfear_cloud** clouds);
 
 /* ---- KITTI drift of a batch's trajectories on the device: the metric of include/cfear_hip/kitti_metric.hpp (kitti_drift,
  * kitti_drift_by_length; what the reference's evaluation worker computes per job, launch/oxford/eval/utils/worker:94-98) for every
