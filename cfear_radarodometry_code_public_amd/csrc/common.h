@@ -242,8 +242,16 @@ extern "C" __attribute__((visibility("hidden"))) int cfear_ensure_hstage(cfear_c
 extern "C" __attribute__((visibility("hidden"))) void* cfear_hpool_alloc(cfear_ctx* ctx, size_t bytes, size_t* got);  // null: no mirror (not an error)
 extern "C" __attribute__((visibility("hidden"))) void cfear_hpool_free(cfear_ctx* ctx, void* p, size_t bytes);
 extern "C" __attribute__((visibility("hidden"))) int cfear_upload_image(cfear_ctx* ctx, void* d_dst, const void* h_src, size_t bytes);
+static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
 // pipeline.hip
 extern "C" __attribute__((visibility("hidden"))) int cfear_cloud_alloc(cfear_ctx* ctx, int cap, cfear_cloud** out);
+// ... and a blank per-call scan of cap_points points and cap_cells cells (their cfear_cell records included; with_kd: and the kd-tree's arrays):
+// the handle, its block of the context's pool (*d_block) and in *hdr the header that belongs at the block's front. n_cells: what
+// cfear_scan_size answers without a round trip (-1: not known before the scan is built). With cfear_scan_release all another unit needs of a scan.
+namespace cfear_dev { struct ScanDev; }
+extern "C" __attribute__((visibility("hidden"))) int cfear_scan_alloc(cfear_ctx* ctx, int cap_points, int cap_cells, bool with_kd, int n_cells, cfear_scan** out,
+                                                                      cfear_dev::ScanDev** d_block, cfear_dev::ScanDev* hdr);
 // kstrongest.hip
 __attribute__((visibility("hidden"))) int cfear_launch_kstrongest(cfear_ctx* ctx, const uint8_t* d_polar, int n_scans, uint32_t* d_slots, hipStream_t stream,
                                                                    bool peaks /* false: slots nobody reads bit 25 of (the batched odometry routes) - written 0, no suppression */,

@@ -8,9 +8,27 @@
 //   keyframe_cloud_kernel   with a point log, in front of the recorder: the filtered and the peaks cloud of the sequences that fused.
 //   keyframe_scans_kernel   the batched twin of scan_from_cells_kernel: a workgroup per scan rebuilds a per-call scan from the log.
 //   cfear_keyframe_constraint  the rule of AddToGraph :435-440 for the host (keyframe_constraint.h: one function for both sides).
-#include "common.h"
-#include "keyframe_dev.h"
+// Behind the kernels the graph's host side: the log is cfear_odometry::kf (KeyframeLog, keyframe_dev.h). pipeline.hip's sweep launches the
+// recorder and the cloud stage through the two launchers of that header; the setters (cfear_odometry_set_keyframe_recording / _clouds)
+// and the reading routes (counts, nodes, cells, scans, cloud sizes, cloud, clouds) are here. A scan rebuilt from the log is a per-call
+// scan of pipeline.hip: cfear_scan_alloc makes the blank one, cfear_scan_release takes it back.
+#include <algorithm>
+
+#include "odometry_obj.h"
 #include "keyframe_constraint.h"
+
+namespace cfear_dev {
+// One scan to rebuild from the log (cfear_odometry_keyframe_scans): the header of its block, its cells in the log and the working memory
+// of its workgroup (the uniform grid's cursors; under NN_TIE_RULE = 2 the kd build's activation stack). Known to this unit only.
+struct KfScanJob {
+  ScanDev hdr;                     // written to the front of the block by the kernel (hdr's pointers point into the block)
+  ScanDev* dst;                    // the block
+  const cfear_keyframe_cell* src;  // n cells
+  int n, part_doubles;
+  int* vcur;                       // [CFEAR_GRID_CAP + 4]
+  double* part;                    // [part_doubles], or null
+};
+}  // namespace cfear_dev
 
 namespace {
 
@@ -207,9 +225,301 @@ void cfear_launch_keyframe_clouds(const KfLog& L, const OdoParams& P, int count,
   hipLaunchKernelGGL(keyframe_cloud_kernel, dim3(count), dim3(BLOCK_F), 0, st, L, P, states, slots, trig);
 }
 
-void cfear_launch_keyframe_scans(const KfScanJob* d_jobs, int m, const FeatureParams& P, hipStream_t st) {
+// ... and m scans from the log, a workgroup each
+static void cfear_launch_keyframe_scans(const KfScanJob* d_jobs, int m, const FeatureParams& P, hipStream_t st) {
   hipLaunchKernelGGL(keyframe_scans_kernel, dim3(m), dim3(BLOCK_F), 0, st, d_jobs, P);
 }
+
+// ---- the host side: setters and reading routes over cfear_odometry::kf -----------------------------------------------------------------
+// the reading calls' common start: recording on, the context stream drained; `cnt`: the sequence's four counters (sequence < 0: none)
+static int odo_kf_read(cfear_ctx* ctx, cfear_odometry* o, const char* what, int sequence, int cnt[4]) {
+  char msg[160];
+  if (!ctx || !o) { snprintf(msg, sizeof(msg), "%s: bad argument", what); return cfear_fail(ctx, CFEAR_ERR_INVALID, msg); }
+  if (!o->kf.what) { snprintf(msg, sizeof(msg), "%s: keyframe recording is off (cfear_odometry_set_keyframe_recording)", what); return cfear_fail(ctx, CFEAR_ERR_INVALID, msg); }
+  if (cnt && (sequence < 0 || sequence >= o->B)) { snprintf(msg, sizeof(msg), "%s: sequence %d of %d", what, sequence, o->B); return cfear_fail(ctx, CFEAR_ERR_INVALID, msg); }
+  CFEAR_TRY(odo_drain(ctx, o));
+  if (cnt) CFEAR_HIP_CHECK(ctx, hipMemcpy(cnt, o->kf.view().counts + 4 * (size_t)sequence, sizeof(int) * 4, hipMemcpyDeviceToHost));
+  return CFEAR_OK;
+}
+// ... for the point log: odo_kf_read, then the log has clouds (and, for peaks = 1, peaks clouds)
+static int odo_kf_read_points(cfear_ctx* ctx, cfear_odometry* o, const char* what, int sequence, int peaks, int cnt[4]) {
+  CFEAR_TRY(odo_kf_read(ctx, o, what, sequence, cnt));
+  const auto refuse = [&](const char* text) {
+    char msg[200];
+    snprintf(msg, sizeof(msg), "%s: %s", what, text);
+    return cfear_fail(ctx, CFEAR_ERR_INVALID, msg);
+  };
+  if (!o->kf.records_clouds()) return refuse("the log was switched on without CFEAR_KF_CLOUD (cfear_odometry_set_keyframe_clouds)");
+  if (peaks != 0 && peaks != 1) return refuse("peaks must be 0 or 1");
+  if (peaks && !o->kf.records_peaks()) return refuse("the log was switched on without CFEAR_KF_PEAKS");
+  return CFEAR_OK;
+}
+// where the cells of keyframes 0 .. recorded - 1 of a sequence start in its cells, and (entry `recorded`) where they end
+static int odo_kf_offsets(cfear_ctx* ctx, const KfLog& L, int sequence, const int cnt[4], std::vector<int>& off) {
+  off.assign((size_t)cnt[0] + 1, 0);
+  if (cnt[0] > 0) CFEAR_HIP_CHECK(ctx, hipMemcpy(off.data(), L.cell_off + (size_t)sequence * L.max_kf, sizeof(int) * (size_t)cnt[0], hipMemcpyDeviceToHost));
+  off[(size_t)cnt[0]] = cnt[2];
+  return CFEAR_OK;
+}
+// (first point, points of the filtered cloud, of the peaks cloud) of nodes first .. first + m - 1 of a sequence
+static int odo_kf_point_offsets(cfear_ctx* ctx, const KfLog& L, int sequence, int first, int m, std::vector<int>& off) {
+  off.assign(3 * (size_t)std::max(m, 0), 0);
+  if (m > 0)
+    CFEAR_HIP_CHECK(ctx, hipMemcpy(off.data(), L.point_off + 3 * ((size_t)sequence * L.max_kf + first), sizeof(int) * 3 * (size_t)m, hipMemcpyDeviceToHost));
+  return CFEAR_OK;
+}
+// ... and from a node's three, where its filtered (peaks = 0) or peaks cloud lies in the log's points; *n: its points
+static const float* odo_kf_cloud_span(const KfLog& L, int sequence, const int po[3], int peaks, int* n) {
+  *n = peaks ? po[2] : po[1];
+  return L.points + 3 * ((size_t)sequence * L.max_points + po[0] + (peaks ? po[1] : 0));
+}
+// entry i of a caller's list of keyframes of a sequence that has recorded `recorded`
+static int odo_kf_index_check(cfear_ctx* ctx, const char* what, int i, int index, int sequence, int recorded) {
+  if (index >= 0 && index < recorded) return CFEAR_OK;
+  char msg[160];
+  snprintf(msg, sizeof(msg), "%s: indices[%d] = %d, sequence %d has recorded %d keyframes", what, i, index, sequence, recorded);
+  return cfear_fail(ctx, CFEAR_ERR_INVALID, msg);
+}
+// the one keyframe a caller reads into `capacity` records at `dst`
+static int odo_kf_one_check(cfear_ctx* ctx, const char* what, int index, int sequence, int recorded, int capacity, const void* dst) {
+  if (index >= 0 && index < recorded && capacity >= 0 && (capacity == 0 || dst)) return CFEAR_OK;
+  char msg[160];
+  snprintf(msg, sizeof(msg), "%s: keyframe %d of sequence %d (%d recorded), capacity %d", what, index, sequence, recorded, capacity);
+  return cfear_fail(ctx, CFEAR_ERR_INVALID, msg);
+}
+
+extern "C" {
+
+int cfear_odometry_set_keyframe_recording(cfear_ctx* ctx, cfear_odometry* o, int what, int max_keyframes, int max_cells) {
+  if (!ctx || !o) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_set_keyframe_recording: bad argument");
+  if (what != 0 && what != CFEAR_KF_NODES && what != (CFEAR_KF_NODES | CFEAR_KF_CELLS))
+    return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_set_keyframe_recording: what must be 0, CFEAR_KF_NODES or CFEAR_KF_NODES | CFEAR_KF_CELLS");
+  const bool cells = (what & CFEAR_KF_CELLS) != 0;
+  if (what && (max_keyframes < 1 || (cells && max_cells < 1)))
+    return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_set_keyframe_recording: max_keyframes (and with CFEAR_KF_CELLS max_cells) must be at least 1");
+  if (what) CFEAR_SEQ_TRY(ctx, cfear_seq_fresh_check(odo_seq_object(ctx, o), "odometry_set_keyframe_recording", msg));
+  CFEAR_TRY(odo_drain(ctx, o));  // no recorder is running: the buffers may go
+  if (o->kf.what && o->d_flags) {  // a full log is the log's condition, not the object's: its status bit goes with the log
+    std::vector<int> f((size_t)o->B + 1);
+    CFEAR_HIP_CHECK(ctx, hipMemcpy(f.data(), o->d_flags, sizeof(int) * f.size(), hipMemcpyDeviceToHost));
+    for (int q = 1; q <= o->B; q++) f[(size_t)q] &= ~4;
+    CFEAR_HIP_CHECK(ctx, hipMemcpy(o->d_flags, f.data(), sizeof(int) * f.size(), hipMemcpyHostToDevice));
+  }
+  KeyframeLog& K = o->kf;
+  K.release();
+  if (!what) return CFEAR_OK;
+  const size_t B = (size_t)o->B;
+  const char* msg = "hipMalloc keyframe log";
+  CFEAR_TRY(odo_ensure_flags(ctx, o));  // (a full log is reported in the sequence's status word)
+  CFEAR_TRY(K.d_nodes.ensure(ctx, B * (size_t)max_keyframes, msg));
+  CFEAR_TRY(K.d_cell_off.ensure(ctx, B * (size_t)max_keyframes, msg));
+  CFEAR_TRY(K.d_counts.ensure(ctx, 4 * B, msg));
+  CFEAR_TRY(K.d_tmot.ensure(ctx, 6 * B, msg));
+  if (cells) CFEAR_TRY(K.d_cells.ensure(ctx, B * (size_t)max_cells, msg));
+  K.max_kf = max_keyframes; K.max_cells = cells ? max_cells : 0;
+  CFEAR_TRY(K.clear(ctx, o->B));
+  K.what = what;
+  return CFEAR_OK;
+}
+
+// the point log: cloud_nopeaks_ / cloud_peaks_ of every node (types.h:93-143; keyframe_cloud_kernel)
+int cfear_odometry_set_keyframe_clouds(cfear_ctx* ctx, cfear_odometry* o, int what, int max_points) {
+  if (!ctx || !o) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_set_keyframe_clouds: bad argument");
+  if (what != 0 && what != CFEAR_KF_CLOUD && what != (CFEAR_KF_CLOUD | CFEAR_KF_PEAKS))
+    return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_set_keyframe_clouds: what must be 0, CFEAR_KF_CLOUD or CFEAR_KF_CLOUD | CFEAR_KF_PEAKS (the peaks cloud is recorded "
+                      "beside the filtered cloud, not alone)");
+  KeyframeLog& K = o->kf;
+  if (what && !(K.what & CFEAR_KF_NODES))
+    return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_set_keyframe_clouds: the clouds belong to recorded nodes - switch node recording on first "
+                      "(cfear_odometry_set_keyframe_recording with CFEAR_KF_NODES)");
+  if (what && max_points < 1) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_set_keyframe_clouds: max_points must be at least 1");
+  if ((what & CFEAR_KF_PEAKS) && ctx->tune_k1_peaks == 0 && o->filter != CFEAR_FILTER_CACFAR)
+    return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_set_keyframe_clouds: CFEAR_KF_PEAKS needs the filter's peak flag and cfear_tune FILTER_PEAKS = 0 forbids it: set the "
+                      "knob to -1 or 1, or record without CFEAR_KF_PEAKS");
+  if (what) CFEAR_SEQ_TRY(ctx, cfear_seq_fresh_check(odo_seq_object(ctx, o), "odometry_set_keyframe_clouds", msg));
+  CFEAR_TRY(odo_drain(ctx, o));  // no cloud stage is running: the buffers may go
+  K.release_points();
+  if (!what) return CFEAR_OK;
+  const size_t B = (size_t)o->B;
+  {  // refuse what cannot fit with the numbers (as cfear_odometry_create does)
+    size_t free_b = 0, total_b = 0;
+    const size_t per_seq = sizeof(float) * 3 * (size_t)max_points + sizeof(int) * (3 * (size_t)K.max_kf + 4);
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && per_seq * B > free_b) {
+      char msg[384];
+      snprintf(msg, sizeof(msg), "odometry_set_keyframe_clouds: %d sequences x %.2f MB (%d points of 12 bytes + the offsets of %d nodes per sequence) = %.2f GB, %.2f GB "
+               "free: at most %zu points per sequence fit", o->B, per_seq / 1048576.0, max_points, K.max_kf, per_seq * (double)B / 1073741824.0,
+               free_b / 1073741824.0, free_b / B / 12);
+      return cfear_fail(ctx, CFEAR_ERR_NOMEM, msg);
+    }
+  }
+  const char* msg = "hipMalloc keyframe point log";
+  // (+ one point: cloud_step_block's general branch reads the first point of its output back whatever it wrote - at the log's very end too)
+  CFEAR_TRY(K.d_points.ensure(ctx, 3 * (B * (size_t)max_points + 1), msg));
+  CFEAR_TRY(K.d_point_off.ensure(ctx, 3 * B * (size_t)K.max_kf, msg));
+  CFEAR_TRY(K.d_cloud_word.ensure(ctx, 4 * B, msg));
+  K.max_points = max_points;
+  CFEAR_TRY(K.clear(ctx, o->B));  // (no sweep has run: the rest of the log is empty already)
+  K.what |= what;
+  return CFEAR_OK;
+}
+
+int cfear_odometry_keyframe_counts(cfear_ctx* ctx, cfear_odometry* o, int32_t* recorded, int32_t* dropped) {
+  CFEAR_TRY(odo_kf_read(ctx, o, "odometry_keyframe_counts", -1, nullptr));
+  std::vector<int> c(4 * (size_t)o->B);
+  CFEAR_HIP_CHECK(ctx, hipMemcpy(c.data(), o->kf.view().counts, sizeof(int) * c.size(), hipMemcpyDeviceToHost));
+  for (int q = 0; q < o->B; q++) {
+    if (recorded) recorded[q] = c[4 * (size_t)q];
+    if (dropped) dropped[q] = c[4 * (size_t)q + 1];
+  }
+  return CFEAR_OK;
+}
+
+int cfear_odometry_keyframe_nodes(cfear_ctx* ctx, cfear_odometry* o, int sequence, int first, cfear_keyframe_node* nodes, int capacity, int* n) {
+  int cnt[4];
+  CFEAR_TRY(odo_kf_read(ctx, o, "odometry_keyframe_nodes", sequence, cnt));
+  if (first < 0 || capacity < 0 || (capacity > 0 && !nodes)) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_keyframe_nodes: bad argument");
+  if (n) *n = cnt[0];
+  const KfLog L = o->kf.view();
+  const int m = std::min(capacity, cnt[0] - first);
+  if (m > 0)
+    CFEAR_HIP_CHECK(ctx, hipMemcpy(nodes, L.nodes + (size_t)sequence * L.max_kf + first, sizeof(cfear_keyframe_node) * (size_t)m, hipMemcpyDeviceToHost));
+  return CFEAR_OK;
+}
+
+int cfear_odometry_keyframe_cells(cfear_ctx* ctx, cfear_odometry* o, int sequence, int index, cfear_keyframe_cell* cells, int capacity, int* n) {
+  int cnt[4];
+  CFEAR_TRY(odo_kf_read(ctx, o, "odometry_keyframe_cells", sequence, cnt));
+  const KfLog L = o->kf.view();
+  if (!(L.what & CFEAR_KF_CELLS)) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_keyframe_cells: the log was switched on without CFEAR_KF_CELLS");
+  CFEAR_TRY(odo_kf_one_check(ctx, "odometry_keyframe_cells", index, sequence, cnt[0], capacity, cells));
+  std::vector<int> off;
+  CFEAR_TRY(odo_kf_offsets(ctx, L, sequence, cnt, off));
+  const int nc = off[(size_t)index + 1] - off[(size_t)index];
+  if (n) *n = nc;
+  const int m = std::min(capacity, nc);
+  if (m > 0)
+    CFEAR_HIP_CHECK(ctx, hipMemcpy(cells, L.cells + (size_t)sequence * L.max_cells + off[(size_t)index], sizeof(cfear_keyframe_cell) * (size_t)m, hipMemcpyDeviceToHost));
+  return CFEAR_OK;
+}
+
+int cfear_odometry_keyframe_scans(cfear_ctx* ctx, cfear_odometry* o, int sequence, const int32_t* indices, int m, cfear_scan** scans) {
+  int cnt[4];
+  CFEAR_TRY(odo_kf_read(ctx, o, "odometry_keyframe_scans", sequence, cnt));
+  const KfLog L = o->kf.view();
+  if (!(L.what & CFEAR_KF_CELLS)) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_keyframe_scans: the log was switched on without CFEAR_KF_CELLS");
+  if (!indices || !scans || m < 1) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_keyframe_scans: bad argument");
+  for (int i = 0; i < m; i++) scans[i] = nullptr;
+  std::vector<int> off;
+  CFEAR_TRY(odo_kf_offsets(ctx, L, sequence, cnt, off));
+  const bool kd = ctx->tune_nn_tie == 2;
+  int nmax = 0;
+  for (int i = 0; i < m; i++) {
+    CFEAR_TRY(odo_kf_index_check(ctx, "odometry_keyframe_scans", i, indices[i], sequence, cnt[0]));
+    const int nc = off[(size_t)indices[i] + 1] - off[(size_t)indices[i]];
+    if (nc < 1) {
+      char msg[160];
+      snprintf(msg, sizeof(msg), "odometry_keyframe_scans: keyframe %d of sequence %d has no cells (reference: 'error, cloud empty' + exit)", indices[i], sequence);
+      return cfear_fail(ctx, CFEAR_ERR_EMPTY, msg);
+    }
+    nmax = std::max(nmax, nc);
+  }
+  // working memory of the m workgroups (one block of the pool): the job table, the grid cursors and - parity mode - the kd build's stacks
+  const size_t part_doubles = kd ? 7 * (size_t)std::max(nmax, ctx->A * ctx->par.k_strongest) : 0;
+  const size_t jobs_b = align_up(sizeof(KfScanJob) * (size_t)m, 256), vcur_b = align_up(sizeof(int) * (CFEAR_GRID_CAP + 4), 256), part_b = align_up(sizeof(double) * part_doubles, 256);
+  void* work = nullptr;
+  size_t work_bytes = 0;
+  CFEAR_TRY(cfear_pool_alloc(ctx, jobs_b + (vcur_b + part_b) * (size_t)m, &work, &work_bytes));
+  unsigned char* wb = static_cast<unsigned char*>(work);
+  std::vector<KfScanJob> jobs((size_t)m);
+  int rc = CFEAR_OK;
+  for (int i = 0; i < m && rc == CFEAR_OK; i++) {
+    const int nc = off[(size_t)indices[i] + 1] - off[(size_t)indices[i]];
+    KfScanJob& J = jobs[(size_t)i];
+    rc = cfear_scan_alloc(ctx, nc, nc, kd, nc, &scans[i], &J.dst, &J.hdr);
+    if (rc != CFEAR_OK) break;
+    J.src = L.cells + (size_t)sequence * L.max_cells + off[(size_t)indices[i]];
+    J.n = nc; J.part_doubles = (int)part_doubles;
+    J.vcur = reinterpret_cast<int*>(wb + jobs_b + (vcur_b + part_b) * (size_t)i);
+    J.part = kd ? reinterpret_cast<double*>(wb + jobs_b + (vcur_b + part_b) * (size_t)i + vcur_b) : nullptr;
+  }
+  hipError_t e = hipSuccess;
+  if (rc == CFEAR_OK) {
+    e = hipMemcpyAsync(wb, jobs.data(), sizeof(KfScanJob) * (size_t)m, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) {
+      cfear_launch_keyframe_scans(reinterpret_cast<const KfScanJob*>(wb), m, odo_params(ctx, o).fp /* the context's feature parameters */, ctx->stream);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // the job table is read until here
+    if (e != hipSuccess) rc = cfear_fail(ctx, CFEAR_ERR_HIP, "odometry_keyframe_scans", e);
+  }
+  cfear_pool_free(ctx, work, work_bytes);
+  if (rc != CFEAR_OK)
+    for (int i = 0; i < m; i++) { cfear_scan_release(ctx, scans[i]); scans[i] = nullptr; }
+  return rc;
+}
+
+int cfear_odometry_keyframe_cloud_sizes(cfear_ctx* ctx, cfear_odometry* o, int sequence, int first, int32_t* n_cloud, int32_t* n_peaks, int capacity, int* n) {
+  int cnt[4];
+  CFEAR_TRY(odo_kf_read_points(ctx, o, "odometry_keyframe_cloud_sizes", sequence, 0, cnt));
+  if (first < 0 || capacity < 0) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_keyframe_cloud_sizes: bad argument");
+  if (n) *n = cnt[0];
+  const int m = std::min(capacity, cnt[0] - first);
+  std::vector<int> off;
+  CFEAR_TRY(odo_kf_point_offsets(ctx, o->kf.view(), sequence, first, m, off));
+  for (int i = 0; i < m; i++) {
+    if (n_cloud) n_cloud[i] = off[3 * (size_t)i + 1];
+    if (n_peaks) n_peaks[i] = off[3 * (size_t)i + 2];
+  }
+  return CFEAR_OK;
+}
+
+int cfear_odometry_keyframe_cloud(cfear_ctx* ctx, cfear_odometry* o, int sequence, int index, int peaks, float* xyi, int capacity, int* n) {
+  int cnt[4];
+  CFEAR_TRY(odo_kf_read_points(ctx, o, "odometry_keyframe_cloud", sequence, peaks, cnt));
+  CFEAR_TRY(odo_kf_one_check(ctx, "odometry_keyframe_cloud", index, sequence, cnt[0], capacity, xyi));
+  const KfLog L = o->kf.view();
+  std::vector<int> off;
+  CFEAR_TRY(odo_kf_point_offsets(ctx, L, sequence, index, 1, off));
+  int np = 0;
+  const float* src = odo_kf_cloud_span(L, sequence, off.data(), peaks, &np);
+  if (n) *n = np;
+  const int m = std::min(capacity, np);
+  if (m > 0) CFEAR_HIP_CHECK(ctx, hipMemcpy(xyi, src, sizeof(float) * 3 * (size_t)m, hipMemcpyDeviceToHost));
+  return CFEAR_OK;
+}
+
+int cfear_odometry_keyframe_clouds(cfear_ctx* ctx, cfear_odometry* o, int sequence, const int32_t* indices, int m, int peaks, cfear_cloud** clouds) {
+  int cnt[4];
+  CFEAR_TRY(odo_kf_read_points(ctx, o, "odometry_keyframe_clouds", sequence, peaks, cnt));
+  if (!indices || !clouds || m < 1) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_keyframe_clouds: bad argument");
+  for (int i = 0; i < m; i++) clouds[i] = nullptr;
+  for (int i = 0; i < m; i++) CFEAR_TRY(odo_kf_index_check(ctx, "odometry_keyframe_clouds", i, indices[i], sequence, cnt[0]));
+  const KfLog L = o->kf.view();
+  std::vector<int> off;
+  CFEAR_TRY(odo_kf_point_offsets(ctx, L, sequence, 0, cnt[0], off));
+  std::vector<int> counts((size_t)m);  // (read by the copies until the synchronisation below)
+  int rc = CFEAR_OK;
+  hipError_t e = hipSuccess;
+  for (int i = 0; i < m && rc == CFEAR_OK && e == hipSuccess; i++) {
+    int& np = counts[(size_t)i];
+    const float* src = odo_kf_cloud_span(L, sequence, off.data() + 3 * (size_t)indices[i], peaks, &np);
+    rc = cfear_cloud_alloc(ctx, np, &clouds[i]);
+    if (rc != CFEAR_OK) break;
+    if (np > 0) e = hipMemcpyAsync(clouds[i]->d_xyi, src, sizeof(float) * 3 * (size_t)np, hipMemcpyDeviceToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(clouds[i]->d_n, &counts[(size_t)i], sizeof(int), hipMemcpyHostToDevice, ctx->stream);
+  }
+  if (rc == CFEAR_OK) {
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) rc = cfear_fail(ctx, CFEAR_ERR_HIP, "odometry_keyframe_clouds", e);
+  } else {
+    (void)hipStreamSynchronize(ctx->stream);  // (counts is read until here)
+  }
+  if (rc != CFEAR_OK)
+    for (int i = 0; i < m; i++) { cfear_cloud_release(ctx, clouds[i]); clouds[i] = nullptr; }
+  return rc;
+}
+
+}  // extern "C"
 
 extern "C" int cfear_keyframe_constraint(const double from_xyt[3], const double to_xyt[3], const double cov6[36], double t_be_xyt[3], double information[36]) {
   if (!from_xyt || !to_xyt || !cov6 || !t_be_xyt || !information) return CFEAR_ERR_INVALID;

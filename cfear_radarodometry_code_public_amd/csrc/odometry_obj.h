@@ -1,7 +1,8 @@
 // odometry_obj.h -- the batched odometry object (cfear_odometry) and the few helpers that more than one translation unit needs:
-// pipeline.hip (the kernels, the launch layer that names them, the scan and scratch layouts, the reading, surface, cov-sampling and
-// keyframe routes), odometry_run.hip (the object's life: creation, reset, destruction, the steps, the profile, the replay) and
-// odometry_seq.hip (the per-sequence configuration: setters, getters, the device table). The latter two hold no kernel.
+// pipeline.hip (the step's kernels, the launch layer that names them, the scan and scratch layouts, the surface and cov-sampling routes),
+// odometry_run.hip (the object's life: creation, reset, destruction, the steps, the profile, the replay, and the plain reads: poses,
+// covariances, status, summary), odometry_seq.hip (the per-sequence configuration: setters, getters, the device table) and keyframes.hip
+// (the keyframe graph: its three kernels, its setters and its reading routes over KeyframeLog, keyframe_dev.h). The middle two hold no kernel.
 #pragma once
 #include <memory>
 
@@ -9,6 +10,7 @@
 #include "odometry_step_dev.h"
 #include "surface_dev.h"
 #include "seq_config.h"
+#include "keyframe_dev.h"
 
 struct cfear_cfar_grid_delete { void operator()(cfear_cfar_grid* g) const { cfear_cfar_grid_destroy(g); } };
 typedef std::unique_ptr<cfear_cfar_grid, cfear_cfar_grid_delete> cfear_cfar_grid_ptr;
@@ -123,22 +125,9 @@ struct cfear_odometry {
   // per-sequence CA-CFAR detectors over shared sweeps: the filter stage runs cfear_launch_cfar_grid
   cfear_cfar_grid_ptr det_grid;        // the plan and device tables of cfg.dets and their source map (destroyed with the object: its streams are idle then)
   long long sweeps = 0;               // sweeps processed since cfear_odometry_create / cfear_odometry_reset
-  // the keyframe graph (cfear_odometry_set_keyframe_recording): while kf_what != 0 the recorder stage of keyframes.hip runs behind every
-  // registration stage and appends the keyframes of the sequences that fused to these
-  int kf_what = 0, kf_max = 0, kf_max_cells = 0;
-  DevBuf<cfear_keyframe_node> d_kf_nodes;  // [B][kf_max]
-  DevBuf<cfear_keyframe_cell> d_kf_cells;  // [B][kf_max_cells] (CFEAR_KF_CELLS)
-  DevBuf<int> d_kf_off;                    // [B][kf_max] a node's first cell in its sequence's cells
-  DevBuf<int> d_kf_counts;                 // [B][4] nodes recorded, keyframes dropped, cells used, 0
-  DevBuf<double> d_kf_tmot;                // [B][6] the recorder's copy of SeqState::Tmot (KfLog::tmot)
-  // ... and its point log (cfear_odometry_set_keyframe_clouds: kf_what & CFEAR_KF_CLOUD / CFEAR_KF_PEAKS): the cloud stage of keyframes.hip runs
-  // in front of the recorder; with CFEAR_KF_PEAKS the object's filters compute the slots' peak flag
-  int kf_max_points = 0;
-  DevBuf<float> d_kf_points;               // [B][kf_max_points][3] + one point: the general cloud pass reads the point at its output's start back whatever
-                                           // it wrote. With no room left that is the first point of the NEXT sequence's region (which its workgroup may be
-                                           // writing) or, for the last sequence, this slack; the value lands in lanes that hold no point and is discarded
-  DevBuf<int> d_kf_point_off;              // [B][kf_max][3] per node: first point, points of the filtered cloud, of the peaks cloud
-  DevBuf<int> d_kf_cloud_word;             // [B][4] the cloud stage's verdict and counts of the sweep (KfLog::cloud_word)
+  // the keyframe graph (cfear_odometry_set_keyframe_recording / _clouds, keyframes.hip): while kf.what != 0 the recorder stage runs behind
+  // every registration stage - with a point log the cloud stage in front of it - and appends the keyframes of the sequences that fused
+  KeyframeLog kf;
   // ---- streams (destroyed before everything above) ----
   Stream sf;               // overlap: the filter's
   std::vector<Stream> so;  // ... and the odometry streams
@@ -166,6 +155,13 @@ static int odo_join(cfear_ctx* ctx, cfear_odometry* o) {
       CFEAR_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream, o->ev_done[i], 0));
     }
   }
+  return CFEAR_OK;
+}
+// ... and wait for it: nothing of the object is in flight (a blocking read; before a buffer is replaced)
+static int odo_drain(cfear_ctx* ctx, cfear_odometry* o) {
+  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  CFEAR_TRY(odo_join(ctx, o));
+  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   return CFEAR_OK;
 }
 static int odo_sources(const cfear_odometry* o) { return o->cfg.sources(o->B); }
@@ -210,11 +206,10 @@ __attribute__((visibility("hidden"))) int odo_capacity_check(cfear_ctx* ctx, cfe
 __attribute__((visibility("hidden"))) void odo_block_bytes(const cfear_odometry* o, size_t* scan_bytes, size_t* scratch_bytes);
 // ... and the headers of all of them, built on the host and uploaded ("odometry state upload")
 __attribute__((visibility("hidden"))) int odo_upload_headers(cfear_ctx* ctx, cfear_odometry* o, size_t scratch_bytes);
-// ---- odometry_run.hip: what the keyframe route of pipeline.hip calls ----
+// ---- odometry_run.hip: what the keyframe setters of keyframes.hip call ----
 __attribute__((visibility("hidden"))) int odo_ensure_flags(cfear_ctx* ctx, cfear_odometry* o);
-__attribute__((visibility("hidden"))) int odo_kf_clear(cfear_ctx* ctx, cfear_odometry* o);
 // does the object's filter compute the slots' peak flag? (only for a point log with peaks clouds; refused where cfear_tune FILTER_PEAKS = 0 forbids it)
-inline bool odo_filter_peaks(const cfear_odometry* o) { return (o->kf_what & CFEAR_KF_PEAKS) != 0; }
+inline bool odo_filter_peaks(const cfear_odometry* o) { return o->kf.records_peaks(); }
 // (a CA-CFAR object runs no k-strongest filter and its peaks cloud is empty by definition: nothing to refuse there)
 inline int odo_peaks_check(cfear_ctx* ctx, const cfear_odometry* o, const char* what) {
   if (!odo_filter_peaks(o) || ctx->tune_k1_peaks != 0 || o->filter == CFEAR_FILTER_CACFAR) return CFEAR_OK;

@@ -1,5 +1,5 @@
 // odometry_run.hip -- the life of a batched odometry object (struct cfear_odometry, odometry_obj.h): creation, reset and destruction, the step
-// entry points, the phase times and the profile, and the replay of a recording. No kernel is defined here: the sweeps go through the launch
+// entry points, the phase times and the profile, the replay of a recording, and the plain reads (poses, covariances, status, summary). No kernel is defined here: the sweeps go through the launch
 // layer of pipeline.hip (odo_params, odo_launch_sweep, odo_launch_cfar), the filters through kstrongest.hip / cfar.hip, the persistent replay
 // through replay.hip; the sizes and schedules are odometry_plan.h's.
 #include <algorithm>
@@ -8,17 +8,6 @@
 
 #include "odometry_obj.h"
 #include "odometry_plan.h"
-
-// an empty keyframe log: no nodes, no drops, and the recorder's copy of Tmot the identity the states start with
-int odo_kf_clear(cfear_ctx* ctx, cfear_odometry* o) {
-  std::vector<double> tm(6 * (size_t)o->B, 0.0);
-  for (int q = 0; q < o->B; q++) tm[6 * (size_t)q] = tm[6 * (size_t)q + 3] = 1.0;
-  CFEAR_HIP_CHECK(ctx, hipMemsetAsync(o->d_kf_counts, 0, sizeof(int) * 4 * (size_t)o->B, ctx->stream));
-  if (o->d_kf_cloud_word) CFEAR_HIP_CHECK(ctx, hipMemsetAsync(o->d_kf_cloud_word, 0, sizeof(int) * 4 * (size_t)o->B, ctx->stream));  // (the point log with the rest)
-  CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(o->d_kf_tmot, tm.data(), sizeof(double) * tm.size(), hipMemcpyHostToDevice, ctx->stream));
-  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // (tm is read until here)
-  return CFEAR_OK;
-}
 
 // the overflow flags of `o`, all clear: created with the object when a scan can overflow its cells or the filter's clouds their points, by
 // cfear_odometry_step_cloud_device otherwise (the caller's clouds may) when it is first used
@@ -87,7 +76,7 @@ int cfear_odometry_reset(cfear_ctx* ctx, cfear_odometry* o) {
   CFEAR_HIP_CHECK(ctx, hipMemsetAsync(o->d_poses_out, 0, sizeof(double) * 3 * (size_t)o->B, ctx->stream));
   CFEAR_HIP_CHECK(ctx, hipMemsetAsync(o->d_cov_work, 0, sizeof(double) * 36 * (size_t)o->B, ctx->stream));
   if (o->d_flags) CFEAR_HIP_CHECK(ctx, hipMemsetAsync(o->d_flags, 0, sizeof(int) * ((size_t)o->B + 1), ctx->stream));
-  if (o->kf_what) CFEAR_TRY(odo_kf_clear(ctx, o));  // (the setting stays, the log starts again at keyframe 0)
+  if (o->kf.what) CFEAR_TRY(o->kf.clear(ctx, o->B));  // (the setting stays, the log starts again at keyframe 0)
   o->order_ready = false;
   o->surf_ready = false;
   o->sweeps = 0;  // (the parameter table, the source map and the fuser options stay)
@@ -418,7 +407,7 @@ static int replay_impl_queue(cfear_ctx* ctx, cfear_odometry* o, const uint8_t* f
   if (!o->cov_on) OP.cs.ctx = nullptr;  // the replay routes do not record for cost surfaces
   o->surf_ready = false;
   // (the keyframe recorder is a stage behind the registration stage: with recording on the sweeps run as two launches, like the timed ones)
-  const bool persistent = o->B <= ctx->tune_replay_persistent_max && !OP.phase_times && !OP.wg_times && !o->kf_what;
+  const bool persistent = o->B <= ctx->tune_replay_persistent_max && !OP.phase_times && !OP.wg_times && !o->kf.what;
   if (on_device) {  // the sweeps are ready at this point of the context stream: the replay stream (which reads them) starts there
     CFEAR_HIP_CHECK(ctx, hipEventRecord(o->rp_in, ctx->stream));
     CFEAR_HIP_CHECK(ctx, hipStreamWaitEvent(o->rp_stream, o->rp_in, 0));
@@ -526,6 +515,53 @@ int cfear_odometry_replay_device_cov(cfear_ctx* ctx, cfear_odometry* o, const ui
 }
 int cfear_odometry_replay_device(cfear_ctx* ctx, cfear_odometry* o, const uint8_t* d_frames, int n_sweeps, cfear_sweep_record* d_records) {
   return cfear_odometry_replay_device_cov(ctx, o, d_frames, n_sweeps, d_records, nullptr);
+}
+
+// ---- the plain reads: what the last sweep left, through the context stream ---------------------------------------------------------------
+int cfear_odometry_poses(cfear_ctx* ctx, cfear_odometry* o, double* poses_xyt) {
+  if (!ctx || !o || !poses_xyt) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_poses: bad argument");
+  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  CFEAR_TRY(odo_join(ctx, o));
+  CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(poses_xyt, o->d_poses_out, sizeof(double) * 3 * (size_t)o->B, hipMemcpyDeviceToHost, ctx->stream));
+  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  return odo_capacity_check(ctx, o, "odometry_poses");
+}
+
+int cfear_odometry_covariances(cfear_ctx* ctx, cfear_odometry* o, double* cov6) {
+  if (!ctx || !o || !cov6) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_covariances: bad argument");
+  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  CFEAR_TRY(odo_join(ctx, o));
+  CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(cov6, o->d_cov_work, sizeof(double) * 36 * (size_t)o->B, hipMemcpyDeviceToHost, ctx->stream));
+  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  return odo_capacity_check(ctx, o, "odometry_covariances");
+}
+
+int cfear_odometry_status(cfear_ctx* ctx, cfear_odometry* o, int32_t* per_sequence) {
+  if (!ctx || !o) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_status: bad argument");
+  CFEAR_TRY(odo_drain(ctx, o));
+  if (per_sequence) {
+    if (o->d_flags) CFEAR_HIP_CHECK(ctx, hipMemcpy(per_sequence, o->d_flags + 1, sizeof(int) * (size_t)o->B, hipMemcpyDeviceToHost));
+    else memset(per_sequence, 0, sizeof(int) * (size_t)o->B);
+  }
+  return odo_capacity_check(ctx, o, "odometry_status");
+}
+
+int cfear_odometry_summary(cfear_ctx* ctx, cfear_odometry* o, int sequence, cfear_reg_summary* summary, int* n_cells,
+                           int* n_keyframes) {
+  if (!ctx || !o || sequence < 0 || sequence >= o->B) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_summary: bad argument");
+  CFEAR_TRY(odo_drain(ctx, o));
+  if (summary) CFEAR_HIP_CHECK(ctx, hipMemcpy(summary, o->d_summaries + sequence, sizeof(cfear_reg_summary), hipMemcpyDeviceToHost));
+  if (n_cells || n_keyframes) {
+    SeqState st;
+    CFEAR_HIP_CHECK(ctx, hipMemcpy(&st, o->d_states + sequence, sizeof(st), hipMemcpyDeviceToHost));
+    if (n_keyframes) *n_keyframes = st.nkf;
+    if (n_cells) {  // cells of the scan built by the last step
+      ScanDev h;
+      CFEAR_HIP_CHECK(ctx, hipMemcpy(&h, o->d_scans + o->scan_stride * ((size_t)sequence * o->nslots + st.last_slot), sizeof(h), hipMemcpyDeviceToHost));
+      *n_cells = h.n_cells;
+    }
+  }
+  return odo_capacity_check(ctx, o, "odometry_summary");
 }
 
 }  // extern "C"

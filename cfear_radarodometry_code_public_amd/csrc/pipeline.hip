@@ -10,10 +10,12 @@
 //                          unit so that the serial Levenberg-Marquardt controllers of different sequences overlap):
 //                          association, robust normal equations, LM, outer loop, keyframe logic
 // Per-call entry points (clouds, scans, Register, GetCost, cost-sampling covariance) use the same device code.
-// The object itself (struct cfear_odometry) is odometry_obj.h's; its life - creation, reset, destruction, the step entry points, the profile
-// and the replay - is odometry_run.hip's, over the launch layer of this file (odo_params, odo_launch_sweep, odo_launch_cfar); its per-sequence configuration - the setters and getters of rows, source
+// The object itself (struct cfear_odometry) is odometry_obj.h's; its life - creation, reset, destruction, the step entry points, the profile,
+// the replay and the plain reads - is odometry_run.hip's, over the launch layer of this file (odo_params, odo_launch_sweep, odo_launch_cfar); its per-sequence configuration - the setters and getters of rows, source
 // map, shapes, detectors and fuser options, the device table (seq_table_upload) and odo_seq_sync's re-check - lives in odometry_seq.hip
 // over seq_config.h. This file reads the configuration through o->cfg (effective(), sources(), other_cost()) and never writes it.
+// The keyframe graph - its kernels, its log (o->kf), its setters and reading routes - is keyframes.hip's: the sweep here launches its two
+// stages, and cfear_scan_alloc hands it the blank per-call scans it rebuilds from the log.
 #include <math.h>
 #include <cmath>
 #include <stdlib.h>
@@ -24,7 +26,6 @@
 #include "odometry_obj.h"
 #include "odometry_plan.h"
 #include "cov_sampling_dev.h"
-#include "keyframe_dev.h"
 
 namespace {
 
@@ -352,8 +353,6 @@ __global__ __launch_bounds__(1024) void order_groups_kernel(const unsigned* work
   }
 }
 // ---- host-side helpers ---------------------------------------------------------------------------
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 FeatureParams feature_params(const cfear_ctx* ctx) {
   FeatureParams P;
   P.nn_tie = ctx->tune_nn_tie;
@@ -488,14 +487,6 @@ static int check_tie_rule_scans(cfear_ctx* ctx, cfear_scan* const* scans, int n,
     }
   return CFEAR_OK;
 }
-static KfLog odo_kf_log(const cfear_odometry* o) {
-  KfLog L;
-  L.what = o->kf_what; L.max_kf = o->kf_max; L.max_cells = o->kf_max_cells; L.pad_ = 0;
-  L.nodes = o->d_kf_nodes; L.cells = o->d_kf_cells; L.cell_off = o->d_kf_off; L.counts = o->d_kf_counts; L.tmot = o->d_kf_tmot;
-  L.max_points = o->kf_max_points; L.pad2_ = 0;
-  L.points = o->d_kf_points; L.point_off = o->d_kf_point_off; L.cloud_word = o->d_kf_cloud_word;
-  return L;
-}
 // the kernel parameters of one odometry step of `o` under the context's current settings
 OdoParams odo_params(const cfear_ctx* ctx, const cfear_odometry* o) {
   OdoParams OP;
@@ -601,8 +592,8 @@ static void launch_register_step(const OdoParams& P, int count, hipStream_t st, 
   // ... and the keyframe recorder (AddToGraph, :234-248 behind the sampling of :202-208: cov_work holds cov_current): the same sequences on the
   // same stream, so the sub-batches of the overlap mode need nothing extra
   // (with a point log the cloud stage goes first: it reads KfLog::tmot before the recorder moves it on, and the recorder commits its verdict)
-  if (o->kf_what & CFEAR_KF_CLOUD) cfear_launch_keyframe_clouds(odo_kf_log(o), P, count, st, o->d_states, src.slots, trig);
-  if (o->kf_what) cfear_launch_keyframe_record(odo_kf_log(o), P, count, st, o->d_states, o->d_cov_work);
+  if (o->kf.records_clouds()) cfear_launch_keyframe_clouds(o->kf.view(), P, count, st, o->d_states, src.slots, trig);
+  if (o->kf.what) cfear_launch_keyframe_record(o->kf.view(), P, count, st, o->d_states, o->d_cov_work);
 }
 // one sweep of `count` sequences from P.seq0 on (odometry_obj.h): the features stage from the filter's slots or from clouds on the device, then the
 // registration stage and what runs behind it
@@ -617,7 +608,7 @@ int odo_launch_sweep(cfear_ctx* ctx, cfear_odometry* o, const OdoParams& P, cons
   // the overlap mode's ev_free: the slot buffer may be filtered into again. An object that records keyframe clouds reads the slots once more
   // behind the registration (the cloud stage), so there the event follows that stage: building the clouds in front of the registration into a
   // staging area instead would build them for every sweep, not only for those that fuse, and keep 2 * A * k points per sequence beside the log
-  const bool late = consumed && (o->kf_what & CFEAR_KF_CLOUD) && src.slots;
+  const bool late = consumed && o->kf.records_clouds() && src.slots;
   if (consumed && !late) {
     const hipError_t e = hipEventRecord(consumed, st);
     if (e != hipSuccess) return cfear_fail(ctx, CFEAR_ERR_HIP, "hipEventRecord(o->ev_free[buf][i], so)", e);
@@ -936,6 +927,22 @@ int voxel_order_stdsort(cfear_ctx* ctx, const cfear_cloud* cloud, int cap_points
 }
 }  // namespace
 extern "C" {
+// a blank per-call scan (common.h)
+__attribute__((visibility("hidden"))) int cfear_scan_alloc(cfear_ctx* ctx, int cap_points, int cap_cells, bool with_kd, int n_cells, cfear_scan** out, ScanDev** d_block,
+                                                           ScanDev* hdr) {
+  cfear_scan* s = new (std::nothrow) cfear_scan();
+  if (!s) return cfear_fail(ctx, CFEAR_ERR_NOMEM, "scan alloc");
+  s->cap_points = cap_points; s->with_kd = with_kd; s->n_cells = n_cells;
+  void* blk = nullptr;
+  const int rc = cfear_pool_alloc(ctx, scan_layout(cap_points, cap_cells, true, with_kd).total, &blk, &s->bytes);
+  if (rc != CFEAR_OK) { delete s; return rc; }
+  s->d_block = static_cast<unsigned char*>(blk);
+  *hdr = scan_header(s->d_block, cap_points, cap_cells, true, with_kd);
+  *d_block = reinterpret_cast<ScanDev*>(s->d_block);
+  *out = s;
+  return CFEAR_OK;
+}
+
 int cfear_scan_create(cfear_ctx* ctx, const cfear_cloud* cloud, cfear_scan** scan) {
   if (!ctx || !cloud || !scan) return cfear_fail(ctx, CFEAR_ERR_INVALID, "scan_create: bad argument");
   CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
@@ -945,46 +952,34 @@ int cfear_scan_create(cfear_ctx* ctx, const cfear_cloud* cloud, cfear_scan** sca
   BlockScratch B;
   int rc = ensure_ctx_scratch(ctx, std::max(cap, ctx->A * ctx->par.k_strongest), &B);
   if (rc != CFEAR_OK) return rc;
-  cfear_scan* s = new (std::nothrow) cfear_scan();
-  if (!s) return cfear_fail(ctx, CFEAR_ERR_NOMEM, "scan alloc");
-  s->cap_points = cap; s->with_kd = ctx->tune_nn_tie == 2;
-  const ScanLayout L = scan_layout(cap, cap, true, ctx->tune_nn_tie == 2);
-  { void* blk = nullptr; rc = cfear_pool_alloc(ctx, L.total, &blk, &s->bytes); if (rc != CFEAR_OK) { delete s; return rc; } s->d_block = static_cast<unsigned char*>(blk); }
-  const ScanDev h = scan_header(s->d_block, cap, cap, true, ctx->tune_nn_tie == 2);
-  ScanDev back;
+  cfear_scan* s = nullptr;
+  ScanDev* d_scan = nullptr;
+  ScanDev h, back;
+  CFEAR_TRY(cfear_scan_alloc(ctx, cap, cap, ctx->tune_nn_tie == 2, -1, &s, &d_scan, &h));
   DevBuf<int> d_vorder;  // (freed on every way out, each of them behind the synchronisation below)
   // the header goes in and comes back through the context's pinned staging (from / to the stack the two small copies are pageable: the runtime
   // stages and waits for each - on the per-sweep route two of the ~15 host round trips of a sweep)
   constexpr size_t HS = (sizeof(ScanDev) + 63) & ~(size_t)63;
   rc = cfear_ensure_hstage(ctx, 2 * HS);
-  if (rc != CFEAR_OK) { cfear_pool_free(ctx, s->d_block, s->bytes); delete s; return rc; }
+  if (rc != CFEAR_OK) { cfear_scan_release(ctx, s); return rc; }
   memcpy(ctx->h_stage, &h, sizeof(h));
-  hipError_t e = hipMemcpyAsync(s->d_block, ctx->h_stage, sizeof(h), hipMemcpyHostToDevice, ctx->stream);
+  hipError_t e = hipMemcpyAsync(d_scan, ctx->h_stage, sizeof(h), hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess) {
     if (ctx->tune_voxel_order == 1) {  // PCL <= 1.9's intra-voxel order (parity mode): ranks from a host std::sort
       const int nv = voxel_order_stdsort(ctx, cloud, cap, &d_vorder);
-      if (nv < 0) { cfear_pool_free(ctx, s->d_block, s->bytes); delete s; return nv; }
+      if (nv < 0) { cfear_scan_release(ctx, s); return nv; }
       if (d_vorder) { B.vrank = d_vorder; B.vperm = d_vorder + nv; }
     }
     const FeatureParams P = feature_params(ctx);
-    hipLaunchKernelGGL(features_kernel, dim3(1), dim3(BLOCK_F), 0, ctx->stream, reinterpret_cast<ScanDev*>(s->d_block), cloud->d_xyi,
-                       cloud->d_n, P, B);
+    hipLaunchKernelGGL(features_kernel, dim3(1), dim3(BLOCK_F), 0, ctx->stream, d_scan, cloud->d_xyi, cloud->d_n, P, B);
     e = hipGetLastError();
   }
   // the reference exits on an empty cloud (pointnormal.cpp:72-75); report it instead
-  if (e == hipSuccess) e = hipMemcpyAsync(ctx->h_stage + HS, s->d_block, sizeof(back), hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(ctx->h_stage + HS, d_scan, sizeof(back), hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
   if (e == hipSuccess) memcpy(&back, ctx->h_stage + HS, sizeof(back));
-  if (e != hipSuccess) {
-    cfear_pool_free(ctx, s->d_block, s->bytes);
-    delete s;
-    return cfear_fail(ctx, CFEAR_ERR_HIP, "scan_create", e);
-  }
-  if (back.status != 0) {
-    cfear_pool_free(ctx, s->d_block, s->bytes);
-    delete s;
-    return cfear_fail(ctx, CFEAR_ERR_EMPTY, "scan_create: empty cloud (reference: 'error, cloud empty' + exit)");
-  }
+  if (e != hipSuccess) { cfear_scan_release(ctx, s); return cfear_fail(ctx, CFEAR_ERR_HIP, "scan_create", e); }
+  if (back.status != 0) { cfear_scan_release(ctx, s); return cfear_fail(ctx, CFEAR_ERR_EMPTY, "scan_create: empty cloud (reference: 'error, cloud empty' + exit)"); }
   s->n_cells = back.n_cells;
   *scan = s;
   return CFEAR_OK;
@@ -999,21 +994,18 @@ int cfear_scan_from_cells(cfear_ctx* ctx, const cfear_cell* cells, int n, cfear_
   BlockScratch B;
   int rc = ensure_ctx_scratch(ctx, std::max(n, ctx->A * ctx->par.k_strongest), &B);
   if (rc != CFEAR_OK) return rc;
-  cfear_scan* s = new (std::nothrow) cfear_scan();
-  if (!s) return cfear_fail(ctx, CFEAR_ERR_NOMEM, "scan alloc");
-  s->cap_points = n; s->with_kd = ctx->tune_nn_tie == 2;
-  const ScanLayout L = scan_layout(n, n, true, ctx->tune_nn_tie == 2);
-  { void* blk = nullptr; rc = cfear_pool_alloc(ctx, L.total, &blk, &s->bytes); if (rc != CFEAR_OK) { delete s; return rc; } s->d_block = static_cast<unsigned char*>(blk); }
-  const ScanDev h = scan_header(s->d_block, n, n, true, ctx->tune_nn_tie == 2);
-  hipError_t e = hipMemcpyAsync(s->d_block, &h, sizeof(h), hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(s->d_block + L.cells, cells, sizeof(cfear_cell) * (size_t)n, hipMemcpyHostToDevice, ctx->stream);
+  cfear_scan* s = nullptr;
+  ScanDev* d_scan = nullptr;
+  ScanDev h;
+  CFEAR_TRY(cfear_scan_alloc(ctx, n, n, ctx->tune_nn_tie == 2, n, &s, &d_scan, &h));
+  hipError_t e = hipMemcpyAsync(d_scan, &h, sizeof(h), hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(h.cells, cells, sizeof(cfear_cell) * (size_t)n, hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(scan_from_cells_kernel, dim3(1), dim3(BLOCK_F), 0, ctx->stream, reinterpret_cast<ScanDev*>(s->d_block), n, feature_params(ctx), B);
+    hipLaunchKernelGGL(scan_from_cells_kernel, dim3(1), dim3(BLOCK_F), 0, ctx->stream, d_scan, n, feature_params(ctx), B);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // h and the caller's cells are read until here
-  if (e != hipSuccess) { cfear_pool_free(ctx, s->d_block, s->bytes); delete s; return cfear_fail(ctx, CFEAR_ERR_HIP, "scan_from_cells", e); }
-  s->n_cells = n;
+  if (e != hipSuccess) { cfear_scan_release(ctx, s); return cfear_fail(ctx, CFEAR_ERR_HIP, "scan_from_cells", e); }
   *scan = s;
   return CFEAR_OK;
 }
@@ -1404,7 +1396,7 @@ int cfear_cov_by_sampling(cfear_ctx* ctx, cfear_scan* const* scans, int n, const
   return CFEAR_OK;
 }
 
-// ---- batched odometry: the object's life is odometry_run.hip's; here the routes that read it or run kernels of their own ----------
+// ---- batched odometry: the object's life is odometry_run.hip's; here the routes that run kernels of this file --------------------
 // the [B] records of the registrations (cost sampling and surface recording share them), all 'nothing recorded'. The streams are idle.
 static int odo_ensure_cov_ctx(cfear_ctx* ctx, cfear_odometry* o, const char* what) {
   return o->d_cov_ctx.ensure(ctx, (size_t)o->B, what, true);
@@ -1536,360 +1528,6 @@ int cfear_odometry_cov_samples(cfear_ctx* ctx, cfear_odometry* o, int sequence, 
     *sampled = c.n >= 2 ? c.sampled : 0;
   }
   return odo_capacity_check(ctx, o, "odometry_cov_samples");
-}
-
-int cfear_odometry_poses(cfear_ctx* ctx, cfear_odometry* o, double* poses_xyt) {
-  if (!ctx || !o || !poses_xyt) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_poses: bad argument");
-  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  CFEAR_TRY(odo_join(ctx, o));
-  CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(poses_xyt, o->d_poses_out, sizeof(double) * 3 * (size_t)o->B, hipMemcpyDeviceToHost, ctx->stream));
-  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  return odo_capacity_check(ctx, o, "odometry_poses");
-}
-
-int cfear_odometry_covariances(cfear_ctx* ctx, cfear_odometry* o, double* cov6) {
-  if (!ctx || !o || !cov6) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_covariances: bad argument");
-  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  CFEAR_TRY(odo_join(ctx, o));
-  CFEAR_HIP_CHECK(ctx, hipMemcpyAsync(cov6, o->d_cov_work, sizeof(double) * 36 * (size_t)o->B, hipMemcpyDeviceToHost, ctx->stream));
-  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  return odo_capacity_check(ctx, o, "odometry_covariances");
-}
-
-int cfear_odometry_status(cfear_ctx* ctx, cfear_odometry* o, int32_t* per_sequence) {
-  if (!ctx || !o) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_status: bad argument");
-  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  CFEAR_TRY(odo_join(ctx, o));
-  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  if (per_sequence) {
-    if (o->d_flags) CFEAR_HIP_CHECK(ctx, hipMemcpy(per_sequence, o->d_flags + 1, sizeof(int) * (size_t)o->B, hipMemcpyDeviceToHost));
-    else memset(per_sequence, 0, sizeof(int) * (size_t)o->B);
-  }
-  return odo_capacity_check(ctx, o, "odometry_status");
-}
-
-// ---- the keyframe graph (AddToGraph, odometrykeyframefuser.cpp:428-445; keyframes.hip) -----------------------------------------------
-static void odo_kf_release_points(cfear_odometry* o) {
-  o->kf_what &= ~(CFEAR_KF_CLOUD | CFEAR_KF_PEAKS);
-  o->kf_max_points = 0;
-  o->d_kf_points.release(); o->d_kf_point_off.release(); o->d_kf_cloud_word.release();
-}
-int cfear_odometry_set_keyframe_recording(cfear_ctx* ctx, cfear_odometry* o, int what, int max_keyframes, int max_cells) {
-  if (!ctx || !o) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_set_keyframe_recording: bad argument");
-  if (what != 0 && what != CFEAR_KF_NODES && what != (CFEAR_KF_NODES | CFEAR_KF_CELLS))
-    return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_set_keyframe_recording: what must be 0, CFEAR_KF_NODES or CFEAR_KF_NODES | CFEAR_KF_CELLS");
-  const bool cells = (what & CFEAR_KF_CELLS) != 0;
-  if (what && (max_keyframes < 1 || (cells && max_cells < 1)))
-    return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_set_keyframe_recording: max_keyframes (and with CFEAR_KF_CELLS max_cells) must be at least 1");
-  if (what) CFEAR_SEQ_TRY(ctx, cfear_seq_fresh_check(odo_seq_object(ctx, o), "odometry_set_keyframe_recording", msg));
-  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  CFEAR_TRY(odo_join(ctx, o));
-  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // no recorder is running: the buffers may go
-  if (o->kf_what && o->d_flags) {  // a full log is the log's condition, not the object's: its status bit goes with the log
-    std::vector<int> f((size_t)o->B + 1);
-    CFEAR_HIP_CHECK(ctx, hipMemcpy(f.data(), o->d_flags, sizeof(int) * f.size(), hipMemcpyDeviceToHost));
-    for (int q = 1; q <= o->B; q++) f[(size_t)q] &= ~4;
-    CFEAR_HIP_CHECK(ctx, hipMemcpy(o->d_flags, f.data(), sizeof(int) * f.size(), hipMemcpyHostToDevice));
-  }
-  o->kf_what = 0;
-  o->d_kf_nodes.release(); o->d_kf_cells.release(); o->d_kf_off.release(); o->d_kf_counts.release(); o->d_kf_tmot.release();
-  odo_kf_release_points(o);  // (sized by max_keyframes: the point log goes with the nodes; cfear_odometry_set_keyframe_clouds switches it on again)
-  if (!what) return CFEAR_OK;
-  const size_t B = (size_t)o->B;
-  const char* msg = "hipMalloc keyframe log";
-  CFEAR_TRY(odo_ensure_flags(ctx, o));  // (a full log is reported in the sequence's status word)
-  CFEAR_TRY(o->d_kf_nodes.ensure(ctx, B * (size_t)max_keyframes, msg));
-  CFEAR_TRY(o->d_kf_off.ensure(ctx, B * (size_t)max_keyframes, msg));
-  CFEAR_TRY(o->d_kf_counts.ensure(ctx, 4 * B, msg));
-  CFEAR_TRY(o->d_kf_tmot.ensure(ctx, 6 * B, msg));
-  if (cells) CFEAR_TRY(o->d_kf_cells.ensure(ctx, B * (size_t)max_cells, msg));
-  o->kf_max = max_keyframes; o->kf_max_cells = cells ? max_cells : 0;
-  CFEAR_TRY(odo_kf_clear(ctx, o));
-  o->kf_what = what;
-  return CFEAR_OK;
-}
-
-// the reading calls' common start: recording on, the context stream drained; `cnt`: the sequence's four counters (sequence < 0: none)
-static int odo_kf_read(cfear_ctx* ctx, cfear_odometry* o, const char* what, int sequence, int cnt[4]) {
-  char msg[160];
-  if (!ctx || !o) { snprintf(msg, sizeof(msg), "%s: bad argument", what); return cfear_fail(ctx, CFEAR_ERR_INVALID, msg); }
-  if (!o->kf_what) { snprintf(msg, sizeof(msg), "%s: keyframe recording is off (cfear_odometry_set_keyframe_recording)", what); return cfear_fail(ctx, CFEAR_ERR_INVALID, msg); }
-  if (cnt && (sequence < 0 || sequence >= o->B)) { snprintf(msg, sizeof(msg), "%s: sequence %d of %d", what, sequence, o->B); return cfear_fail(ctx, CFEAR_ERR_INVALID, msg); }
-  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  CFEAR_TRY(odo_join(ctx, o));
-  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  if (cnt) CFEAR_HIP_CHECK(ctx, hipMemcpy(cnt, o->d_kf_counts + 4 * (size_t)sequence, sizeof(int) * 4, hipMemcpyDeviceToHost));
-  return CFEAR_OK;
-}
-
-int cfear_odometry_keyframe_counts(cfear_ctx* ctx, cfear_odometry* o, int32_t* recorded, int32_t* dropped) {
-  CFEAR_TRY(odo_kf_read(ctx, o, "odometry_keyframe_counts", -1, nullptr));
-  std::vector<int> c(4 * (size_t)o->B);
-  CFEAR_HIP_CHECK(ctx, hipMemcpy(c.data(), o->d_kf_counts, sizeof(int) * c.size(), hipMemcpyDeviceToHost));
-  for (int q = 0; q < o->B; q++) {
-    if (recorded) recorded[q] = c[4 * (size_t)q];
-    if (dropped) dropped[q] = c[4 * (size_t)q + 1];
-  }
-  return CFEAR_OK;
-}
-
-int cfear_odometry_keyframe_nodes(cfear_ctx* ctx, cfear_odometry* o, int sequence, int first, cfear_keyframe_node* nodes, int capacity, int* n) {
-  int cnt[4];
-  CFEAR_TRY(odo_kf_read(ctx, o, "odometry_keyframe_nodes", sequence, cnt));
-  if (first < 0 || capacity < 0 || (capacity > 0 && !nodes)) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_keyframe_nodes: bad argument");
-  if (n) *n = cnt[0];
-  const int m = std::min(capacity, cnt[0] - first);
-  if (m > 0)
-    CFEAR_HIP_CHECK(ctx, hipMemcpy(nodes, o->d_kf_nodes + (size_t)sequence * o->kf_max + first, sizeof(cfear_keyframe_node) * (size_t)m, hipMemcpyDeviceToHost));
-  return CFEAR_OK;
-}
-
-// where the cells of keyframes 0 .. recorded - 1 of a sequence start in its cells, and (entry `recorded`) where they end
-static int odo_kf_offsets(cfear_ctx* ctx, cfear_odometry* o, int sequence, const int cnt[4], std::vector<int>& off) {
-  off.assign((size_t)cnt[0] + 1, 0);
-  if (cnt[0] > 0) CFEAR_HIP_CHECK(ctx, hipMemcpy(off.data(), o->d_kf_off + (size_t)sequence * o->kf_max, sizeof(int) * (size_t)cnt[0], hipMemcpyDeviceToHost));
-  off[(size_t)cnt[0]] = cnt[2];
-  return CFEAR_OK;
-}
-
-int cfear_odometry_keyframe_cells(cfear_ctx* ctx, cfear_odometry* o, int sequence, int index, cfear_keyframe_cell* cells, int capacity, int* n) {
-  int cnt[4];
-  CFEAR_TRY(odo_kf_read(ctx, o, "odometry_keyframe_cells", sequence, cnt));
-  if (!(o->kf_what & CFEAR_KF_CELLS)) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_keyframe_cells: the log was switched on without CFEAR_KF_CELLS");
-  if (index < 0 || index >= cnt[0] || capacity < 0 || (capacity > 0 && !cells)) {
-    char msg[160];
-    snprintf(msg, sizeof(msg), "odometry_keyframe_cells: keyframe %d of sequence %d (%d recorded), capacity %d", index, sequence, cnt[0], capacity);
-    return cfear_fail(ctx, CFEAR_ERR_INVALID, msg);
-  }
-  std::vector<int> off;
-  CFEAR_TRY(odo_kf_offsets(ctx, o, sequence, cnt, off));
-  const int nc = off[(size_t)index + 1] - off[(size_t)index];
-  if (n) *n = nc;
-  const int m = std::min(capacity, nc);
-  if (m > 0)
-    CFEAR_HIP_CHECK(ctx, hipMemcpy(cells, o->d_kf_cells + (size_t)sequence * o->kf_max_cells + off[(size_t)index], sizeof(cfear_keyframe_cell) * (size_t)m, hipMemcpyDeviceToHost));
-  return CFEAR_OK;
-}
-
-int cfear_odometry_keyframe_scans(cfear_ctx* ctx, cfear_odometry* o, int sequence, const int32_t* indices, int m, cfear_scan** scans) {
-  int cnt[4];
-  CFEAR_TRY(odo_kf_read(ctx, o, "odometry_keyframe_scans", sequence, cnt));
-  if (!(o->kf_what & CFEAR_KF_CELLS)) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_keyframe_scans: the log was switched on without CFEAR_KF_CELLS");
-  if (!indices || !scans || m < 1) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_keyframe_scans: bad argument");
-  for (int i = 0; i < m; i++) scans[i] = nullptr;
-  std::vector<int> off;
-  CFEAR_TRY(odo_kf_offsets(ctx, o, sequence, cnt, off));
-  const bool kd = ctx->tune_nn_tie == 2;
-  int nmax = 0;
-  for (int i = 0; i < m; i++) {
-    char msg[160];
-    if (indices[i] < 0 || indices[i] >= cnt[0]) {
-      snprintf(msg, sizeof(msg), "odometry_keyframe_scans: indices[%d] = %d, sequence %d has recorded %d keyframes", i, indices[i], sequence, cnt[0]);
-      return cfear_fail(ctx, CFEAR_ERR_INVALID, msg);
-    }
-    const int nc = off[(size_t)indices[i] + 1] - off[(size_t)indices[i]];
-    if (nc < 1) {
-      snprintf(msg, sizeof(msg), "odometry_keyframe_scans: keyframe %d of sequence %d has no cells (reference: 'error, cloud empty' + exit)", indices[i], sequence);
-      return cfear_fail(ctx, CFEAR_ERR_EMPTY, msg);
-    }
-    nmax = std::max(nmax, nc);
-  }
-  // working memory of the m workgroups (one block of the pool): the job table, the grid cursors and - parity mode - the kd build's stacks
-  const size_t part_doubles = kd ? 7 * (size_t)std::max(nmax, ctx->A * ctx->par.k_strongest) : 0;
-  const size_t jobs_b = align_up(sizeof(KfScanJob) * (size_t)m, 256), vcur_b = align_up(sizeof(int) * (GRID_CAP + 4), 256), part_b = align_up(sizeof(double) * part_doubles, 256);
-  void* work = nullptr;
-  size_t work_bytes = 0;
-  CFEAR_TRY(cfear_pool_alloc(ctx, jobs_b + (vcur_b + part_b) * (size_t)m, &work, &work_bytes));
-  unsigned char* wb = static_cast<unsigned char*>(work);
-  std::vector<KfScanJob> jobs((size_t)m);
-  int rc = CFEAR_OK;
-  for (int i = 0; i < m && rc == CFEAR_OK; i++) {
-    const int nc = off[(size_t)indices[i] + 1] - off[(size_t)indices[i]];
-    cfear_scan* s = new (std::nothrow) cfear_scan();
-    if (!s) { rc = cfear_fail(ctx, CFEAR_ERR_NOMEM, "scan alloc"); break; }
-    s->cap_points = nc; s->with_kd = kd; s->n_cells = nc;
-    void* blk = nullptr;
-    rc = cfear_pool_alloc(ctx, scan_layout(nc, nc, true, kd).total, &blk, &s->bytes);
-    if (rc != CFEAR_OK) { delete s; break; }
-    s->d_block = static_cast<unsigned char*>(blk);
-    scans[i] = s;
-    KfScanJob& J = jobs[(size_t)i];
-    J.hdr = scan_header(s->d_block, nc, nc, true, kd);
-    J.dst = reinterpret_cast<ScanDev*>(s->d_block);
-    J.src = o->d_kf_cells + (size_t)sequence * o->kf_max_cells + off[(size_t)indices[i]];
-    J.n = nc; J.part_doubles = (int)part_doubles;
-    J.vcur = reinterpret_cast<int*>(wb + jobs_b + (vcur_b + part_b) * (size_t)i);
-    J.part = kd ? reinterpret_cast<double*>(wb + jobs_b + (vcur_b + part_b) * (size_t)i + vcur_b) : nullptr;
-  }
-  hipError_t e = hipSuccess;
-  if (rc == CFEAR_OK) {
-    e = hipMemcpyAsync(wb, jobs.data(), sizeof(KfScanJob) * (size_t)m, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) {
-      cfear_launch_keyframe_scans(reinterpret_cast<const KfScanJob*>(wb), m, feature_params(ctx), ctx->stream);
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // the job table is read until here
-    if (e != hipSuccess) rc = cfear_fail(ctx, CFEAR_ERR_HIP, "odometry_keyframe_scans", e);
-  }
-  cfear_pool_free(ctx, work, work_bytes);
-  if (rc != CFEAR_OK)
-    for (int i = 0; i < m; i++) { cfear_scan_release(ctx, scans[i]); scans[i] = nullptr; }
-  return rc;
-}
-
-// ---- the point log: cloud_nopeaks_ / cloud_peaks_ of every node (types.h:93-143; keyframe_cloud_kernel) ----------------------------------
-int cfear_odometry_set_keyframe_clouds(cfear_ctx* ctx, cfear_odometry* o, int what, int max_points) {
-  if (!ctx || !o) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_set_keyframe_clouds: bad argument");
-  if (what != 0 && what != CFEAR_KF_CLOUD && what != (CFEAR_KF_CLOUD | CFEAR_KF_PEAKS))
-    return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_set_keyframe_clouds: what must be 0, CFEAR_KF_CLOUD or CFEAR_KF_CLOUD | CFEAR_KF_PEAKS (the peaks cloud is recorded "
-                      "beside the filtered cloud, not alone)");
-  if (what && !(o->kf_what & CFEAR_KF_NODES))
-    return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_set_keyframe_clouds: the clouds belong to recorded nodes - switch node recording on first "
-                      "(cfear_odometry_set_keyframe_recording with CFEAR_KF_NODES)");
-  if (what && max_points < 1) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_set_keyframe_clouds: max_points must be at least 1");
-  if ((what & CFEAR_KF_PEAKS) && ctx->tune_k1_peaks == 0 && o->filter != CFEAR_FILTER_CACFAR)
-    return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_set_keyframe_clouds: CFEAR_KF_PEAKS needs the filter's peak flag and cfear_tune FILTER_PEAKS = 0 forbids it: set the "
-                      "knob to -1 or 1, or record without CFEAR_KF_PEAKS");
-  if (what) CFEAR_SEQ_TRY(ctx, cfear_seq_fresh_check(odo_seq_object(ctx, o), "odometry_set_keyframe_clouds", msg));
-  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  CFEAR_TRY(odo_join(ctx, o));
-  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // no cloud stage is running: the buffers may go
-  odo_kf_release_points(o);
-  if (!what) return CFEAR_OK;
-  const size_t B = (size_t)o->B;
-  {  // refuse what cannot fit with the numbers (as cfear_odometry_create does)
-    size_t free_b = 0, total_b = 0;
-    const size_t per_seq = sizeof(float) * 3 * (size_t)max_points + sizeof(int) * (3 * (size_t)o->kf_max + 4);
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && per_seq * B > free_b) {
-      char msg[384];
-      snprintf(msg, sizeof(msg), "odometry_set_keyframe_clouds: %d sequences x %.2f MB (%d points of 12 bytes + the offsets of %d nodes per sequence) = %.2f GB, %.2f GB "
-               "free: at most %zu points per sequence fit", o->B, per_seq / 1048576.0, max_points, o->kf_max, per_seq * (double)B / 1073741824.0,
-               free_b / 1073741824.0, free_b / B / 12);
-      return cfear_fail(ctx, CFEAR_ERR_NOMEM, msg);
-    }
-  }
-  const char* msg = "hipMalloc keyframe point log";
-  // (+ one point: cloud_step_block's general branch reads the first point of its output back whatever it wrote - at the log's very end too)
-  CFEAR_TRY(o->d_kf_points.ensure(ctx, 3 * (B * (size_t)max_points + 1), msg));
-  CFEAR_TRY(o->d_kf_point_off.ensure(ctx, 3 * B * (size_t)o->kf_max, msg));
-  CFEAR_TRY(o->d_kf_cloud_word.ensure(ctx, 4 * B, msg));
-  o->kf_max_points = max_points;
-  CFEAR_TRY(odo_kf_clear(ctx, o));  // (no sweep has run: the rest of the log is empty already)
-  o->kf_what |= what;
-  return CFEAR_OK;
-}
-
-// the reading calls' start for the point log: odo_kf_read, then the log has clouds (and, for peaks = 1, peaks clouds)
-static int odo_kf_read_points(cfear_ctx* ctx, cfear_odometry* o, const char* what, int sequence, int peaks, int cnt[4]) {
-  CFEAR_TRY(odo_kf_read(ctx, o, what, sequence, cnt));
-  char msg[200];
-  if (!(o->kf_what & CFEAR_KF_CLOUD)) {
-    snprintf(msg, sizeof(msg), "%s: the log was switched on without CFEAR_KF_CLOUD (cfear_odometry_set_keyframe_clouds)", what);
-    return cfear_fail(ctx, CFEAR_ERR_INVALID, msg);
-  }
-  if (peaks != 0 && peaks != 1) { snprintf(msg, sizeof(msg), "%s: peaks must be 0 or 1", what); return cfear_fail(ctx, CFEAR_ERR_INVALID, msg); }
-  if (peaks && !(o->kf_what & CFEAR_KF_PEAKS)) {
-    snprintf(msg, sizeof(msg), "%s: the log was switched on without CFEAR_KF_PEAKS", what);
-    return cfear_fail(ctx, CFEAR_ERR_INVALID, msg);
-  }
-  return CFEAR_OK;
-}
-// (first point, points of the filtered cloud, of the peaks cloud) of nodes first .. first + m - 1 of a sequence
-static int odo_kf_point_offsets(cfear_ctx* ctx, cfear_odometry* o, int sequence, int first, int m, std::vector<int>& off) {
-  off.assign(3 * (size_t)std::max(m, 0), 0);
-  if (m > 0)
-    CFEAR_HIP_CHECK(ctx, hipMemcpy(off.data(), o->d_kf_point_off + 3 * ((size_t)sequence * o->kf_max + first), sizeof(int) * 3 * (size_t)m, hipMemcpyDeviceToHost));
-  return CFEAR_OK;
-}
-
-int cfear_odometry_keyframe_cloud_sizes(cfear_ctx* ctx, cfear_odometry* o, int sequence, int first, int32_t* n_cloud, int32_t* n_peaks, int capacity, int* n) {
-  int cnt[4];
-  CFEAR_TRY(odo_kf_read_points(ctx, o, "odometry_keyframe_cloud_sizes", sequence, 0, cnt));
-  if (first < 0 || capacity < 0) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_keyframe_cloud_sizes: bad argument");
-  if (n) *n = cnt[0];
-  const int m = std::min(capacity, cnt[0] - first);
-  std::vector<int> off;
-  CFEAR_TRY(odo_kf_point_offsets(ctx, o, sequence, first, m, off));
-  for (int i = 0; i < m; i++) {
-    if (n_cloud) n_cloud[i] = off[3 * (size_t)i + 1];
-    if (n_peaks) n_peaks[i] = off[3 * (size_t)i + 2];
-  }
-  return CFEAR_OK;
-}
-
-int cfear_odometry_keyframe_cloud(cfear_ctx* ctx, cfear_odometry* o, int sequence, int index, int peaks, float* xyi, int capacity, int* n) {
-  int cnt[4];
-  CFEAR_TRY(odo_kf_read_points(ctx, o, "odometry_keyframe_cloud", sequence, peaks, cnt));
-  if (index < 0 || index >= cnt[0] || capacity < 0 || (capacity > 0 && !xyi)) {
-    char msg[160];
-    snprintf(msg, sizeof(msg), "odometry_keyframe_cloud: keyframe %d of sequence %d (%d recorded), capacity %d", index, sequence, cnt[0], capacity);
-    return cfear_fail(ctx, CFEAR_ERR_INVALID, msg);
-  }
-  std::vector<int> off;
-  CFEAR_TRY(odo_kf_point_offsets(ctx, o, sequence, index, 1, off));
-  const int np = peaks ? off[2] : off[1];
-  const size_t at = (size_t)sequence * o->kf_max_points + off[0] + (peaks ? off[1] : 0);
-  if (n) *n = np;
-  const int m = std::min(capacity, np);
-  if (m > 0) CFEAR_HIP_CHECK(ctx, hipMemcpy(xyi, o->d_kf_points + 3 * at, sizeof(float) * 3 * (size_t)m, hipMemcpyDeviceToHost));
-  return CFEAR_OK;
-}
-
-int cfear_odometry_keyframe_clouds(cfear_ctx* ctx, cfear_odometry* o, int sequence, const int32_t* indices, int m, int peaks, cfear_cloud** clouds) {
-  int cnt[4];
-  CFEAR_TRY(odo_kf_read_points(ctx, o, "odometry_keyframe_clouds", sequence, peaks, cnt));
-  if (!indices || !clouds || m < 1) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_keyframe_clouds: bad argument");
-  for (int i = 0; i < m; i++) clouds[i] = nullptr;
-  for (int i = 0; i < m; i++)
-    if (indices[i] < 0 || indices[i] >= cnt[0]) {
-      char msg[160];
-      snprintf(msg, sizeof(msg), "odometry_keyframe_clouds: indices[%d] = %d, sequence %d has recorded %d keyframes", i, indices[i], sequence, cnt[0]);
-      return cfear_fail(ctx, CFEAR_ERR_INVALID, msg);
-    }
-  std::vector<int> off;
-  CFEAR_TRY(odo_kf_point_offsets(ctx, o, sequence, 0, cnt[0], off));
-  std::vector<int> counts((size_t)m);  // (read by the copies until the synchronisation below)
-  int rc = CFEAR_OK;
-  hipError_t e = hipSuccess;
-  for (int i = 0; i < m && rc == CFEAR_OK && e == hipSuccess; i++) {
-    const int* po = off.data() + 3 * (size_t)indices[i];
-    const int np = peaks ? po[2] : po[1];
-    const size_t at = (size_t)sequence * o->kf_max_points + po[0] + (peaks ? po[1] : 0);
-    counts[(size_t)i] = np;
-    rc = cfear_cloud_alloc(ctx, np, &clouds[i]);
-    if (rc != CFEAR_OK) break;
-    if (np > 0) e = hipMemcpyAsync(clouds[i]->d_xyi, o->d_kf_points + 3 * at, sizeof(float) * 3 * (size_t)np, hipMemcpyDeviceToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(clouds[i]->d_n, &counts[(size_t)i], sizeof(int), hipMemcpyHostToDevice, ctx->stream);
-  }
-  if (rc == CFEAR_OK) {
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) rc = cfear_fail(ctx, CFEAR_ERR_HIP, "odometry_keyframe_clouds", e);
-  } else {
-    (void)hipStreamSynchronize(ctx->stream);  // (counts is read until here)
-  }
-  if (rc != CFEAR_OK)
-    for (int i = 0; i < m; i++) { cfear_cloud_release(ctx, clouds[i]); clouds[i] = nullptr; }
-  return rc;
-}
-
-int cfear_odometry_summary(cfear_ctx* ctx, cfear_odometry* o, int sequence, cfear_reg_summary* summary, int* n_cells,
-                           int* n_keyframes) {
-  if (!ctx || !o || sequence < 0 || sequence >= o->B) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_summary: bad argument");
-  CFEAR_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  CFEAR_TRY(odo_join(ctx, o));
-  CFEAR_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  if (summary) CFEAR_HIP_CHECK(ctx, hipMemcpy(summary, o->d_summaries + sequence, sizeof(cfear_reg_summary), hipMemcpyDeviceToHost));
-  if (n_cells || n_keyframes) {
-    SeqState st;
-    CFEAR_HIP_CHECK(ctx, hipMemcpy(&st, o->d_states + sequence, sizeof(st), hipMemcpyDeviceToHost));
-    if (n_keyframes) *n_keyframes = st.nkf;
-    if (n_cells) {  // cells of the scan built by the last step
-      ScanDev h;
-      CFEAR_HIP_CHECK(ctx, hipMemcpy(&h, o->d_scans + o->scan_stride * ((size_t)sequence * o->nslots + st.last_slot), sizeof(h), hipMemcpyDeviceToHost));
-      *n_cells = h.n_cells;
-    }
-  }
-  return odo_capacity_check(ctx, o, "odometry_summary");
 }
 
 }  // extern "C"
