@@ -120,6 +120,55 @@ KEYFRAME_NODE_DTYPE = np.dtype([("index", "i4"), ("sweep", "i4"), ("n_cells", "i
                                 ("t_be", "f8", 3), ("information", "f8", (6, 6))])
 KEYFRAME_CELL_DTYPE = np.dtype([("mean", "f8", 2), ("normal", "f8", 2), ("cov", "f8", 3), ("scale", "f8"), ("nsamples", "i4"), ("pad_", "i4")])
 assert KEYFRAME_NODE_DTYPE.itemsize == C.sizeof(KeyframeNode) == 376 and KEYFRAME_CELL_DTYPE.itemsize == C.sizeof(KeyframeCell) == 72
+KF_EDGE_MAX_FROM = 16  # CFEAR_KF_EDGE_MAX_FROM
+
+
+# cfear_keyframe_edge_job / cfear_keyframe_edge (include/cfear_hip.h): a constraint between any keyframes of a log - keyframe `to`
+# registered against the fixed keyframes `from` (cfear_odometry_keyframe_edges)
+class KeyframeEdgeJob(C.Structure):
+    _fields_ = [("sequence", C.c_int32), ("to", C.c_int32), ("n_from", C.c_int32), ("ref", C.c_int32), ("flags", C.c_int32), ("pad_", C.c_int32),
+                ("from_", C.c_int32 * KF_EDGE_MAX_FROM), ("guess_xyt", C.c_double * 3)]
+
+
+class KeyframeEdge(C.Structure):
+    _fields_ = [("sequence", C.c_int32), ("to", C.c_int32), ("from_", C.c_int32), ("n_from", C.c_int32), ("status", C.c_int32), ("success", C.c_int32),
+                ("usable", C.c_int32), ("outer_iterations", C.c_int32), ("num_residuals", C.c_int32), ("num_residual_blocks", C.c_int32),
+                ("assoc_path", C.c_int32), ("pad_", C.c_int32), ("pose", C.c_double * 3), ("t_be", C.c_double * 3), ("final_cost", C.c_double),
+                ("score", C.c_double), ("information", C.c_double * 36)]
+
+
+KEYFRAME_EDGE_JOB_DTYPE = np.dtype([("sequence", "i4"), ("to", "i4"), ("n_from", "i4"), ("ref", "i4"), ("flags", "i4"), ("pad_", "i4"),
+                                    ("from", "i4", KF_EDGE_MAX_FROM), ("guess_xyt", "f8", 3)])
+KEYFRAME_EDGE_DTYPE = np.dtype([("sequence", "i4"), ("to", "i4"), ("from", "i4"), ("n_from", "i4"), ("status", "i4"), ("success", "i4"), ("usable", "i4"),
+                                ("outer_iterations", "i4"), ("num_residuals", "i4"), ("num_residual_blocks", "i4"), ("assoc_path", "i4"), ("pad_", "i4"),
+                                ("pose", "f8", 3), ("t_be", "f8", 3), ("final_cost", "f8"), ("score", "f8"), ("information", "f8", (6, 6))])
+assert KEYFRAME_EDGE_JOB_DTYPE.itemsize == C.sizeof(KeyframeEdgeJob) == 112 and KEYFRAME_EDGE_DTYPE.itemsize == C.sizeof(KeyframeEdge) == 400
+
+
+def keyframe_edge_jobs(jobs):
+    """A job list for Odometry.keyframe_edges as a structured array of KEYFRAME_EDGE_JOB_DTYPE. jobs: such an array (returned as it is,
+    contiguous), or a list whose entries are dicts - sequence, to, from (an index or a list of up to 16), and optionally ref (0) and guess
+    (x, y, theta; absent or None: `to`'s recorded pose) - or tuples (sequence, to, from[, ref[, guess]]). Pure numpy (no device)."""
+    if isinstance(jobs, np.ndarray) and jobs.dtype == KEYFRAME_EDGE_JOB_DTYPE:
+        return np.ascontiguousarray(jobs).reshape(-1)
+    out = np.zeros(len(jobs), dtype=KEYFRAME_EDGE_JOB_DTYPE)
+    for k, j in enumerate(jobs):
+        if isinstance(j, dict):
+            seq, to, frm, ref, guess = j["sequence"], j["to"], j["from"], j.get("ref", 0), j.get("guess")
+        else:
+            j = tuple(j)
+            seq, to, frm = j[:3]
+            ref, guess = (j[3] if len(j) > 3 else 0), (j[4] if len(j) > 4 else None)
+        frm = [int(v) for v in np.atleast_1d(frm)]
+        if not 1 <= len(frm) <= KF_EDGE_MAX_FROM:
+            raise CfearError("keyframe_edge_jobs: job %d names %d `from` keyframes (1 .. %d)" % (k, len(frm), KF_EDGE_MAX_FROM))
+        out[k]["sequence"], out[k]["to"], out[k]["n_from"], out[k]["ref"] = int(seq), int(to), len(frm), int(ref)
+        out[k]["from"][:len(frm)] = frm
+        if guess is not None:
+            out[k]["flags"], out[k]["guess_xyt"] = 1, np.asarray(guess, dtype=np.float64).reshape(3)
+    return out
+
+
 KF_NODES, KF_CELLS = 1, 2  # CFEAR_KF_NODES / CFEAR_KF_CELLS
 KF_CLOUD, KF_PEAKS = 4, 8  # CFEAR_KF_CLOUD / CFEAR_KF_PEAKS (cfear_odometry_set_keyframe_clouds)
 STATUS_CELLS_LOST, STATUS_POINTS_LOST, STATUS_KEYFRAMES_DROPPED = 1, 2, 4  # the bits of a sequence's word in cfear_odometry_status
@@ -162,7 +211,7 @@ EXPORTS = [
     "cfear_odometry_set_sequence_detectors", "cfear_odometry_sequence_detector",
     "cfear_odometry_covariances", "cfear_odometry_status", "cfear_odometry_summary", "cfear_odometry_profile", "cfear_odometry_profile_read", "cfear_odometry_profile_read_stages", "cfear_odometry_phase_times", "cfear_time_kstrongest",
     "cfear_keyframe_constraint", "cfear_odometry_set_keyframe_recording", "cfear_odometry_keyframe_counts", "cfear_odometry_keyframe_nodes",
-    "cfear_odometry_keyframe_cells", "cfear_odometry_keyframe_scans",
+    "cfear_odometry_keyframe_cells", "cfear_odometry_keyframe_scans", "cfear_odometry_keyframe_edges",
     "cfear_odometry_set_keyframe_clouds", "cfear_odometry_keyframe_cloud_sizes", "cfear_odometry_keyframe_cloud", "cfear_odometry_keyframe_clouds",
     "cfear_drift_segments", "cfear_drift_plan_create", "cfear_drift_plan_release", "cfear_drift_device", "cfear_drift_host",
 ]
@@ -271,6 +320,7 @@ def lib():
         "cfear_odometry_keyframe_nodes": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, C.c_int, C.POINTER(C.c_int)]),
         "cfear_odometry_keyframe_cells": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, C.c_int, C.POINTER(C.c_int)]),
         "cfear_odometry_keyframe_scans": (C.c_int, [vp, vp, C.c_int, i32p, C.c_int, C.POINTER(vp)]),
+        "cfear_odometry_keyframe_edges": (C.c_int, [vp, vp, vp, C.c_int, vp, f64p, vp]),
         "cfear_odometry_set_keyframe_clouds": (C.c_int, [vp, vp, C.c_int, C.c_int]),
         "cfear_odometry_keyframe_cloud_sizes": (C.c_int, [vp, vp, C.c_int, C.c_int, i32p, i32p, C.c_int, C.POINTER(C.c_int)]),
         "cfear_odometry_keyframe_cloud": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, f32p, C.c_int, C.POINTER(C.c_int)]),
@@ -1079,6 +1129,19 @@ class Odometry:
         arr = (C.c_void_p * len(idx))()
         self._ctx._check(self._ctx._L.cfear_odometry_keyframe_scans(self._ctx._h, self._h, int(q), idx.ctypes.data, len(idx), arr), "cfear_odometry_keyframe_scans")
         return [Scan(self._ctx, C.c_void_p(h)) for h in arr]
+
+    def keyframe_edges(self, jobs, details=False):
+        """cfear_odometry_keyframe_edges: constraints between any keyframes of the log, all jobs registered in one launch. jobs: a structured
+        array of KEYFRAME_EDGE_JOB_DTYPE, or a list of dicts / tuples (keyframe_edge_jobs). -> the edges (KEYFRAME_EDGE_DTYPE), one per job;
+        details=True: (edges, cov6 [m, 6, 6], [RegSummary] * m) - every job's covariance and summary as Context.register returns them."""
+        J = keyframe_edge_jobs(jobs)
+        m = len(J)
+        edges = np.zeros(m, dtype=KEYFRAME_EDGE_DTYPE)
+        cov = np.zeros((m, 6, 6)) if details else None
+        sums = (RegSummary * max(m, 1))() if details else None
+        self._ctx._check(self._ctx._L.cfear_odometry_keyframe_edges(self._ctx._h, self._h, J.ctypes.data, m, edges.ctypes.data, cov.ctypes.data if details else None,
+                                                                    sums if details else None), "cfear_odometry_keyframe_edges")
+        return (edges, cov, [sums[i] for i in range(m)]) if details else edges
 
     def keyframe_cloud_sizes(self, q):
         """-> (n_cloud [n], n_peaks [n]): points of the filtered and of the peaks cloud of every recorded node of sequence q"""

@@ -252,6 +252,8 @@ extern "C" __attribute__((visibility("hidden"))) int cfear_cloud_alloc(cfear_ctx
 namespace cfear_dev { struct ScanDev; }
 extern "C" __attribute__((visibility("hidden"))) int cfear_scan_alloc(cfear_ctx* ctx, int cap_points, int cap_cells, bool with_kd, int n_cells, cfear_scan** out,
                                                                       cfear_dev::ScanDev** d_block, cfear_dev::ScanDev* hdr);
+// ... and the bytes of its block (what a call that builds scans of its own reports to the tools)
+extern "C" __attribute__((visibility("hidden"))) size_t cfear_scan_bytes(const cfear_scan* s);
 // kstrongest.hip
 __attribute__((visibility("hidden"))) int cfear_launch_kstrongest(cfear_ctx* ctx, const uint8_t* d_polar, int n_scans, uint32_t* d_slots, hipStream_t stream,
                                                                    bool peaks /* false: slots nobody reads bit 25 of (the batched odometry routes) - written 0, no suppression */,

@@ -7,10 +7,12 @@
 //                           (SeqState, the scan in last_slot, cov_work); no other kernel knows of it.
 //   keyframe_cloud_kernel   with a point log, in front of the recorder: the filtered and the peaks cloud of the sequences that fused.
 //   keyframe_scans_kernel   the batched twin of scan_from_cells_kernel: a workgroup per scan rebuilds a per-call scan from the log.
+//   keyframe_edges_kernel   constraints between ANY keyframes of a log (cfear_odometry_keyframe_edges): a workgroup per job registers
+//                           keyframe `to` against 1 .. 16 fixed keyframes on scans rebuilt from the log and applies the constraint rule.
 //   cfear_keyframe_constraint  the rule of AddToGraph :435-440 for the host (keyframe_constraint.h: one function for both sides).
 // Behind the kernels the graph's host side: the log is cfear_odometry::kf (KeyframeLog, keyframe_dev.h). pipeline.hip's sweep launches the
 // recorder and the cloud stage through the two launchers of that header; the setters (cfear_odometry_set_keyframe_recording / _clouds)
-// and the reading routes (counts, nodes, cells, scans, cloud sizes, cloud, clouds) are here. A scan rebuilt from the log is a per-call
+// and the reading routes (counts, nodes, cells, scans, edges, cloud sizes, cloud, clouds) are here. A scan rebuilt from the log is a per-call
 // scan of pipeline.hip: cfear_scan_alloc makes the blank one, cfear_scan_release takes it back.
 #include <algorithm>
 
@@ -27,6 +29,16 @@ struct KfScanJob {
   int n, part_doubles;
   int* vcur;                       // [CFEAR_GRID_CAP + 4]
   double* part;                    // [part_doubles], or null
+};
+// One job of cfear_odometry_keyframe_edges as its workgroup reads it: nodes of the job's sequence (their poses are read from the log on
+// the device), positions in the call's scan table (every distinct keyframe of the call is rebuilt once) and the job's slice of the
+// call's match / assoc arrays.
+struct KfEdgeJob {
+  int sequence, to, n_from, ref;
+  int has_guess, to_scan, pair_cap, pad_;
+  int from[CFEAR_KF_EDGE_MAX_FROM], from_scan[CFEAR_KF_EDGE_MAX_FROM];
+  double guess[3];
+  unsigned long long pair_off;  // the slice's first pair (a multiple of 64: the arrays of every slice start 256-byte aligned)
 };
 }  // namespace cfear_dev
 
@@ -215,6 +227,71 @@ __global__ __launch_bounds__(BLOCK_F) void keyframe_scans_kernel(const KfScanJob
   if (P.nn_tie == 2) kd_build_block(S, B);
 }
 
+// Constraints between any keyframes of a log (cfear_odometry_keyframe_edges): a workgroup per job runs register_kernel's registration -
+// Register(scans = from[0 .. n_from - 1] + [to]) - on scans rebuilt from the log, the `from` keyframes fixed at their node poses, under
+// the row of the job's sequence, and ends with the rule of a node's own edge (keyframe_constraint) on the result.
+//   prologue  the scan pointers into RegLds::scanptr, the n_from + 1 poses into the registration's parameter array itself (as the step
+//             kernel keeps them: register_block normalises in place), the job's covariance zeroed
+//   epilogue  one thread: the constraint and the 400-byte record. The 6x6 Gauss-Jordan works in the LDS match array, which the
+//             registration no longer reads - static LDS stays RegLds::total + the match array, as register_kernel's
+// Match / assoc arrays: the job's own slice (job.pair_off, job.pair_cap pairs) of the call's two arrays.
+__global__ __launch_bounds__(BLOCK_R, 3) void keyframe_edges_kernel(const KfEdgeJob* jobs, ScanDev* const* scan_tab, KfLog L, OdoParams OP, double* match_base,
+                                                                    int* assoc_base, double* cov_all /*[m][36]*/, cfear_reg_summary* sums /*[m]*/,
+                                                                    cfear_keyframe_edge* edges /*[m]*/) {
+  __shared__ __attribute__((aligned(16))) unsigned char lds[RegLds::total];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const KfEdgeJob* J = jobs + b;
+  const int q = J->sequence, nf = J->n_from, n = nf + 1;
+  const cfear_keyframe_node* nodes = L.nodes + (size_t)q * L.max_kf;
+  ScanDev** sp = reinterpret_cast<ScanDev**>(lds + RegLds::scanptr);
+  double* poses = reinterpret_cast<double*>(lds + RegLds::par);
+  double* cov = cov_all + 36 * (size_t)b;
+  if (tid < nf) {
+    sp[tid] = scan_tab[J->from_scan[tid]];
+    const cfear_keyframe_node* nd = nodes + J->from[tid];
+    poses[3 * tid] = nd->pose[0]; poses[3 * tid + 1] = nd->pose[1]; poses[3 * tid + 2] = nd->pose[2];
+  }
+  if (tid == 64) {
+    sp[nf] = scan_tab[J->to_scan];
+    const double* g = J->has_guess ? J->guess : nodes[J->to].pose;
+    poses[3 * nf] = g[0]; poses[3 * nf + 1] = g[1]; poses[3 * nf + 2] = g[2];
+  }
+  if (tid >= 128 && tid < 164) cov[tid - 128] = 0.0;  // (in/out for register_block: a registration without a usable solution leaves it)
+  __syncthreads();
+  RegScratch W;
+  {
+    const size_t c = (size_t)J->pair_cap;
+    double* m = match_base + 8 * (size_t)J->pair_off;
+    W.tmx = m; W.tmy = m + c; W.a0 = m + 2 * c; W.a1 = m + 3 * c; W.a2 = m + 4 * c; W.sx = m + 5 * c; W.sy = m + 6 * c; W.w = m + 7 * c;
+    W.assoc = assoc_base + 3 * (size_t)J->pair_off; W.cap = J->pair_cap; W.acap = 3 * J->pair_cap;
+    W.red = reinterpret_cast<double*>(lds + RegLds::red_d);
+    W.red_i = reinterpret_cast<int*>(lds + RegLds::red_i);
+  }
+  cfear_reg_summary* sum = sums + b;
+  (void)register_block<-1, false>(sp, n, poses, cov, OP.rp, W, poses, reinterpret_cast<RegShared*>(lds + RegLds::regsh), sum, nullptr, nullptr, seq_row(OP, q));
+  // (register_block ends behind a barrier: what its controller wave wrote - the pose in LDS, the covariance and the summary - is this thread's to read)
+  if (tid != 0) return;
+  cfear_keyframe_edge* E = edges + b;
+  const int ref = J->from[J->ref];
+  E->sequence = q; E->to = J->to; E->from = ref; E->n_from = nf;
+  const int path = sum->assoc_path, usable = sum->usable;
+  E->status = path < 0 ? CFEAR_ERR_UNSUPPORTED : 0;  // (registration_dev.h: the kd descent's stack did not fit the match scratch)
+  E->success = sum->success; E->usable = usable; E->outer_iterations = sum->outer_iterations;
+  E->num_residuals = sum->num_residuals; E->num_residual_blocks = sum->num_residual_blocks; E->assoc_path = path; E->pad_ = 0;
+  E->final_cost = sum->final_cost; E->score = sum->score;
+  const double from_xyt[3] = {poses[3 * nf], poses[3 * nf + 1], poses[3 * nf + 2]};
+  E->pose[0] = from_xyt[0]; E->pose[1] = from_xyt[1]; E->pose[2] = from_xyt[2];
+  if (usable) {
+    const cfear_keyframe_node* nd = nodes + ref;
+    const double to_xyt[3] = {nd->pose[0], nd->pose[1], nd->pose[2]};
+    // (a covariance that cannot be inverted leaves inf / NaN, as in the nodes)
+    (void)cfear_kf::keyframe_constraint(from_xyt, to_xyt, cov, E->t_be, E->information, lds_match_base());
+  } else {
+    for (int i = 0; i < 3; i++) E->t_be[i] = 0.0;
+    for (int i = 0; i < 36; i++) E->information[i] = 0.0;
+  }
+}
+
 }  // namespace
 
 void cfear_launch_keyframe_record(const KfLog& L, const OdoParams& P, int count, hipStream_t st, const SeqState* states, const double* cov_work) {
@@ -286,6 +363,53 @@ static int odo_kf_one_check(cfear_ctx* ctx, const char* what, int index, int seq
   char msg[160];
   snprintf(msg, sizeof(msg), "%s: keyframe %d of sequence %d (%d recorded), capacity %d", what, index, sequence, recorded, capacity);
   return cfear_fail(ctx, CFEAR_ERR_INVALID, msg);
+}
+// the cells of one recorded keyframe: n >= 1 cells from `first` on in its sequence's cells
+struct KfSpan { int sequence, first, n; };
+// m per-call scans from m spans of the log in one launch of keyframe_scans_kernel (cfear_odometry_keyframe_scans, and the distinct
+// keyframes of cfear_odometry_keyframe_edges). Synchronous; on an error nothing is left allocated. blocks: their device blocks, if asked for.
+static int odo_kf_build_scans(cfear_ctx* ctx, cfear_odometry* o, const KfLog& L, const KfSpan* spans, int m, cfear_scan** scans, const char* what,
+                              std::vector<ScanDev*>* blocks = nullptr) {
+  const bool kd = ctx->tune_nn_tie == 2;
+  int nmax = 0;
+  for (int i = 0; i < m; i++) nmax = std::max(nmax, spans[i].n);
+  // working memory of the m workgroups (one block of the pool): the job table, the grid cursors and - parity mode - the kd build's stacks
+  const size_t part_doubles = kd ? 7 * (size_t)std::max(nmax, ctx->A * ctx->par.k_strongest) : 0;
+  const size_t jobs_b = align_up(sizeof(KfScanJob) * (size_t)m, 256), vcur_b = align_up(sizeof(int) * (CFEAR_GRID_CAP + 4), 256), part_b = align_up(sizeof(double) * part_doubles, 256);
+  void* work = nullptr;
+  size_t work_bytes = 0;
+  CFEAR_TRY(cfear_pool_alloc(ctx, jobs_b + (vcur_b + part_b) * (size_t)m, &work, &work_bytes));
+  unsigned char* wb = static_cast<unsigned char*>(work);
+  std::vector<KfScanJob> jobs((size_t)m);
+  int rc = CFEAR_OK;
+  for (int i = 0; i < m && rc == CFEAR_OK; i++) {
+    const int nc = spans[i].n;
+    KfScanJob& J = jobs[(size_t)i];
+    rc = cfear_scan_alloc(ctx, nc, nc, kd, nc, &scans[i], &J.dst, &J.hdr);
+    if (rc != CFEAR_OK) break;
+    J.src = L.cells + (size_t)spans[i].sequence * L.max_cells + spans[i].first;
+    J.n = nc; J.part_doubles = (int)part_doubles;
+    J.vcur = reinterpret_cast<int*>(wb + jobs_b + (vcur_b + part_b) * (size_t)i);
+    J.part = kd ? reinterpret_cast<double*>(wb + jobs_b + (vcur_b + part_b) * (size_t)i + vcur_b) : nullptr;
+  }
+  hipError_t e = hipSuccess;
+  if (rc == CFEAR_OK) {
+    e = hipMemcpyAsync(wb, jobs.data(), sizeof(KfScanJob) * (size_t)m, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) {
+      cfear_launch_keyframe_scans(reinterpret_cast<const KfScanJob*>(wb), m, odo_params(ctx, o).fp /* the context's feature parameters */, ctx->stream);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // the job table is read until here
+    if (e != hipSuccess) rc = cfear_fail(ctx, CFEAR_ERR_HIP, what, e);
+  }
+  cfear_pool_free(ctx, work, work_bytes);
+  if (rc != CFEAR_OK)
+    for (int i = 0; i < m; i++) { cfear_scan_release(ctx, scans[i]); scans[i] = nullptr; }
+  else if (blocks) {
+    blocks->resize((size_t)m);
+    for (int i = 0; i < m; i++) (*blocks)[(size_t)i] = jobs[(size_t)i].dst;
+  }
+  return rc;
 }
 
 extern "C" {
@@ -411,8 +535,7 @@ int cfear_odometry_keyframe_scans(cfear_ctx* ctx, cfear_odometry* o, int sequenc
   for (int i = 0; i < m; i++) scans[i] = nullptr;
   std::vector<int> off;
   CFEAR_TRY(odo_kf_offsets(ctx, L, sequence, cnt, off));
-  const bool kd = ctx->tune_nn_tie == 2;
-  int nmax = 0;
+  std::vector<KfSpan> spans((size_t)m);
   for (int i = 0; i < m; i++) {
     CFEAR_TRY(odo_kf_index_check(ctx, "odometry_keyframe_scans", i, indices[i], sequence, cnt[0]));
     const int nc = off[(size_t)indices[i] + 1] - off[(size_t)indices[i]];
@@ -421,40 +544,131 @@ int cfear_odometry_keyframe_scans(cfear_ctx* ctx, cfear_odometry* o, int sequenc
       snprintf(msg, sizeof(msg), "odometry_keyframe_scans: keyframe %d of sequence %d has no cells (reference: 'error, cloud empty' + exit)", indices[i], sequence);
       return cfear_fail(ctx, CFEAR_ERR_EMPTY, msg);
     }
-    nmax = std::max(nmax, nc);
+    spans[(size_t)i] = {sequence, off[(size_t)indices[i]], nc};
   }
-  // working memory of the m workgroups (one block of the pool): the job table, the grid cursors and - parity mode - the kd build's stacks
-  const size_t part_doubles = kd ? 7 * (size_t)std::max(nmax, ctx->A * ctx->par.k_strongest) : 0;
-  const size_t jobs_b = align_up(sizeof(KfScanJob) * (size_t)m, 256), vcur_b = align_up(sizeof(int) * (CFEAR_GRID_CAP + 4), 256), part_b = align_up(sizeof(double) * part_doubles, 256);
+  return odo_kf_build_scans(ctx, o, L, spans.data(), m, scans, "odometry_keyframe_scans");
+}
+
+// Constraints between any keyframes of a log, registered in one batch (keyframe_edges_kernel). On the host: the checks, the distinct
+// keyframes of the job list rebuilt once (odo_kf_build_scans), every job's slice of the match / assoc arrays by a prefix sum, one block of
+// the pool for all of it, one launch, the results back - and everything returned to the pool.
+int cfear_odometry_keyframe_edges(cfear_ctx* ctx, cfear_odometry* o, const cfear_keyframe_edge_job* jobs, int m, cfear_keyframe_edge* edges, double* cov6,
+                                  cfear_reg_summary* summaries) {
+  const char* what = "odometry_keyframe_edges";
+  CFEAR_TRY(odo_kf_read(ctx, o, what, -1, nullptr));
+  const KfLog L = o->kf.view();
+  if (!(L.what & CFEAR_KF_CELLS)) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_keyframe_edges: the log was switched on without CFEAR_KF_CELLS");
+  if (!jobs || !edges || m < 1) return cfear_fail(ctx, CFEAR_ERR_INVALID, "odometry_keyframe_edges: bad argument");
+  const auto refuse = [&](int code, int job, const char* field, int value, const char* text) {
+    char msg[256];
+    snprintf(msg, sizeof(msg), "%s: jobs[%d].%s = %d: %s", what, job, field, value, text);
+    return cfear_fail(ctx, code, msg);
+  };
+  // ---- the checks: nothing is launched, and no edge written, before every job has passed ----
+  const int B = o->B;
+  std::vector<int> counts(4 * (size_t)B);
+  CFEAR_HIP_CHECK(ctx, hipMemcpy(counts.data(), L.counts, sizeof(int) * counts.size(), hipMemcpyDeviceToHost));
+  std::vector<std::vector<int>> off((size_t)B);  // the cell offsets of the sequences the jobs name
+  for (int j = 0; j < m; j++) {
+    const cfear_keyframe_edge_job& J = jobs[j];
+    if (J.sequence < 0 || J.sequence >= B) return refuse(CFEAR_ERR_INVALID, j, "sequence", J.sequence, "no such sequence");
+    if (J.n_from < 1 || J.n_from > CFEAR_KF_EDGE_MAX_FROM) return refuse(CFEAR_ERR_INVALID, j, "n_from", J.n_from, "1 .. CFEAR_KF_EDGE_MAX_FROM keyframes");
+    if (J.ref < 0 || J.ref >= J.n_from) return refuse(CFEAR_ERR_INVALID, j, "ref", J.ref, "a position in from[0 .. n_from - 1]");
+    const int* cnt = counts.data() + 4 * (size_t)J.sequence;
+    if (J.to < 0 || J.to >= cnt[0]) return refuse(CFEAR_ERR_INVALID, j, "to", J.to, "outside the keyframes its sequence has recorded");
+    for (int i = 0; i < J.n_from; i++)
+      if (J.from[i] < 0 || J.from[i] >= cnt[0]) {
+        char field[32];
+        snprintf(field, sizeof(field), "from[%d]", i);
+        return refuse(CFEAR_ERR_INVALID, j, field, J.from[i], "outside the keyframes its sequence has recorded");
+      }
+    if ((J.flags & 1) && !(std::isfinite(J.guess_xyt[0]) && std::isfinite(J.guess_xyt[1]) && std::isfinite(J.guess_xyt[2])))
+      return refuse(CFEAR_ERR_INVALID, j, "guess_xyt", 0, "the guess is not finite");
+    std::vector<int>& of = off[(size_t)J.sequence];
+    if (of.empty()) CFEAR_TRY(odo_kf_offsets(ctx, L, J.sequence, cnt, of));
+    for (int i = 0; i <= J.n_from; i++) {
+      const int k = i < J.n_from ? J.from[i] : J.to;
+      if (of[(size_t)k + 1] - of[(size_t)k] < 1) {
+        char field[32];
+        if (i < J.n_from) snprintf(field, sizeof(field), "from[%d]", i); else snprintf(field, sizeof(field), "to");
+        return refuse(CFEAR_ERR_EMPTY, j, field, k, "the keyframe has no cells (reference: 'error, cloud empty' + exit)");
+      }
+    }
+  }
+  CFEAR_TRY(odo_seq_sync(ctx, o, what));  // (cfear_set_params since the rows' table was built: the table follows, as before a step)
+  // ---- the distinct keyframes of the list, each rebuilt once; every job's slice of the match / assoc arrays ----
+  std::vector<std::vector<int>> slot((size_t)B);  // [sequence][keyframe] -> position in the scan table, -1: not needed
+  std::vector<KfSpan> spans;
+  std::vector<KfEdgeJob> dj((size_t)m);
+  unsigned long long pairs_total = 0;
+  for (int j = 0; j < m; j++) {
+    const cfear_keyframe_edge_job& J = jobs[j];
+    const std::vector<int>& of = off[(size_t)J.sequence];
+    std::vector<int>& sl = slot[(size_t)J.sequence];
+    if (sl.empty()) sl.assign(of.size(), -1);
+    const auto scan_of = [&](int k) {
+      if (sl[(size_t)k] < 0) { sl[(size_t)k] = (int)spans.size(); spans.push_back({J.sequence, of[(size_t)k], of[(size_t)k + 1] - of[(size_t)k]}); }
+      return sl[(size_t)k];
+    };
+    KfEdgeJob& D = dj[(size_t)j];
+    memset(&D, 0, sizeof(D));
+    D.sequence = J.sequence; D.to = J.to; D.n_from = J.n_from; D.ref = J.ref; D.has_guess = J.flags & 1;
+    for (int i = 0; i < J.n_from; i++) { D.from[i] = J.from[i]; D.from_scan[i] = scan_of(J.from[i]); }
+    D.to_scan = scan_of(J.to);
+    for (int i = 0; i < 3; i++) D.guess[i] = J.guess_xyt[i];
+    // the job's own problem - max(n_from, 4) x cells(to) pairs, the rule of cfear_odo_capacities with the job's numbers: every pair's match
+    // fits, the grouped association can always park (6 ints per (group of four, cell) <= 3 per pair), as under the per-call capacity - and
+    // under a non-zero tie rule its 8192 pairs for the kd descent's stacks; a multiple of 64 pairs keeps every slice 256-byte aligned
+    long long pairs = (long long)std::max(J.n_from, 4) * (of[(size_t)J.to + 1] - of[(size_t)J.to]);
+    if (ctx->tune_nn_tie != 0) pairs = std::max(pairs, 8192LL);
+    pairs = (pairs + 63) / 64 * 64;
+    D.pair_cap = (int)pairs; D.pair_off = pairs_total;
+    pairs_total += (unsigned long long)pairs;
+  }
+  const int u = (int)spans.size();
+  std::vector<cfear_scan*> scans((size_t)u, nullptr);
+  std::vector<ScanDev*> scan_blocks;
+  CFEAR_TRY(odo_kf_build_scans(ctx, o, L, spans.data(), u, scans.data(), what, &scan_blocks));
+  // one block of the pool: job table | scan table | match | assoc | covariances | summaries | edges
+  const size_t jobs_b = align_up(sizeof(KfEdgeJob) * (size_t)m, 256), tab_b = align_up(sizeof(ScanDev*) * (size_t)u, 256);
+  const size_t match_b = align_up(sizeof(double) * 8 * (size_t)pairs_total, 256), assoc_b = align_up(sizeof(int) * 3 * (size_t)pairs_total, 256);
+  const size_t cov_b = align_up(sizeof(double) * 36 * (size_t)m, 256), sum_b = align_up(sizeof(cfear_reg_summary) * (size_t)m, 256);
+  const size_t edge_b = align_up(sizeof(cfear_keyframe_edge) * (size_t)m, 256);
   void* work = nullptr;
   size_t work_bytes = 0;
-  CFEAR_TRY(cfear_pool_alloc(ctx, jobs_b + (vcur_b + part_b) * (size_t)m, &work, &work_bytes));
-  unsigned char* wb = static_cast<unsigned char*>(work);
-  std::vector<KfScanJob> jobs((size_t)m);
-  int rc = CFEAR_OK;
-  for (int i = 0; i < m && rc == CFEAR_OK; i++) {
-    const int nc = off[(size_t)indices[i] + 1] - off[(size_t)indices[i]];
-    KfScanJob& J = jobs[(size_t)i];
-    rc = cfear_scan_alloc(ctx, nc, nc, kd, nc, &scans[i], &J.dst, &J.hdr);
-    if (rc != CFEAR_OK) break;
-    J.src = L.cells + (size_t)sequence * L.max_cells + off[(size_t)indices[i]];
-    J.n = nc; J.part_doubles = (int)part_doubles;
-    J.vcur = reinterpret_cast<int*>(wb + jobs_b + (vcur_b + part_b) * (size_t)i);
-    J.part = kd ? reinterpret_cast<double*>(wb + jobs_b + (vcur_b + part_b) * (size_t)i + vcur_b) : nullptr;
-  }
-  hipError_t e = hipSuccess;
+  int rc = cfear_pool_alloc(ctx, jobs_b + tab_b + match_b + assoc_b + cov_b + sum_b + edge_b, &work, &work_bytes);
   if (rc == CFEAR_OK) {
-    e = hipMemcpyAsync(wb, jobs.data(), sizeof(KfScanJob) * (size_t)m, hipMemcpyHostToDevice, ctx->stream);
+    unsigned char* wb = static_cast<unsigned char*>(work);
+    unsigned char* d_tab = wb + jobs_b;
+    double* d_match = reinterpret_cast<double*>(d_tab + tab_b);
+    int* d_assoc = reinterpret_cast<int*>(d_tab + tab_b + match_b);
+    double* d_cov = reinterpret_cast<double*>(d_tab + tab_b + match_b + assoc_b);
+    cfear_reg_summary* d_sum = reinterpret_cast<cfear_reg_summary*>(reinterpret_cast<unsigned char*>(d_cov) + cov_b);
+    cfear_keyframe_edge* d_edges = reinterpret_cast<cfear_keyframe_edge*>(reinterpret_cast<unsigned char*>(d_sum) + sum_b);
+    size_t scan_bytes = 0;
+    for (int i = 0; i < u; i++) scan_bytes += cfear_scan_bytes(scans[(size_t)i]);
+    static const bool stats = getenv("CFEAR_KF_EDGES_STATS") != nullptr;  // tools/gpu_keyframe_edges.py: what the call took from the pool
+    if (stats)
+      fprintf(stderr, "cfear_odometry_keyframe_edges: %d jobs, %d scans of %zu bytes, %llu pairs of match / assoc arrays in a block of %zu bytes\n", m, u, scan_bytes,
+              pairs_total, work_bytes);
+    std::vector<cfear_keyframe_edge> he((size_t)m);  // (the caller's array stays untouched unless the whole call succeeds)
+    hipError_t e = hipMemcpyAsync(wb, dj.data(), sizeof(KfEdgeJob) * (size_t)m, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_tab, scan_blocks.data(), sizeof(ScanDev*) * (size_t)u, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) {
-      cfear_launch_keyframe_scans(reinterpret_cast<const KfScanJob*>(wb), m, odo_params(ctx, o).fp /* the context's feature parameters */, ctx->stream);
+      hipLaunchKernelGGL(keyframe_edges_kernel, dim3(m), dim3(BLOCK_R), 0, ctx->stream, reinterpret_cast<const KfEdgeJob*>(wb), reinterpret_cast<ScanDev* const*>(d_tab), L,
+                         odo_params(ctx, o), d_match, d_assoc, d_cov, d_sum, d_edges);
       e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // the job table is read until here
-    if (e != hipSuccess) rc = cfear_fail(ctx, CFEAR_ERR_HIP, "odometry_keyframe_scans", e);
+    if (e == hipSuccess) e = hipMemcpyAsync(he.data(), d_edges, sizeof(cfear_keyframe_edge) * (size_t)m, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess && cov6) e = hipMemcpyAsync(cov6, d_cov, sizeof(double) * 36 * (size_t)m, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess && summaries) e = hipMemcpyAsync(summaries, d_sum, sizeof(cfear_reg_summary) * (size_t)m, hipMemcpyDeviceToHost, ctx->stream);
+    const hipError_t es = hipStreamSynchronize(ctx->stream);  // (the host tables are read, and the block is in use, until here)
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) rc = cfear_fail(ctx, CFEAR_ERR_HIP, what, e);
+    else memcpy(edges, he.data(), sizeof(cfear_keyframe_edge) * (size_t)m);
+    cfear_pool_free(ctx, work, work_bytes);
   }
-  cfear_pool_free(ctx, work, work_bytes);
-  if (rc != CFEAR_OK)
-    for (int i = 0; i < m; i++) { cfear_scan_release(ctx, scans[i]); scans[i] = nullptr; }
+  for (int i = 0; i < u; i++) cfear_scan_release(ctx, scans[(size_t)i]);
   return rc;
 }
 

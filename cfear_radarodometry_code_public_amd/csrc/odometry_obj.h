@@ -2,7 +2,7 @@
 // pipeline.hip (the step's kernels, the launch layer that names them, the scan and scratch layouts, the surface and cov-sampling routes),
 // odometry_run.hip (the object's life: creation, reset, destruction, the steps, the profile, the replay, and the plain reads: poses,
 // covariances, status, summary), odometry_seq.hip (the per-sequence configuration: setters, getters, the device table) and keyframes.hip
-// (the keyframe graph: its three kernels, its setters and its reading routes over KeyframeLog, keyframe_dev.h). The middle two hold no kernel.
+// (the keyframe graph: its four kernels, its setters and its reading routes over KeyframeLog, keyframe_dev.h). The middle two hold no kernel.
 #pragma once
 #include <memory>
 

@@ -942,6 +942,7 @@ __attribute__((visibility("hidden"))) int cfear_scan_alloc(cfear_ctx* ctx, int c
   *out = s;
   return CFEAR_OK;
 }
+__attribute__((visibility("hidden"))) size_t cfear_scan_bytes(const cfear_scan* s) { return s ? s->bytes : 0; }
 
 int cfear_scan_create(cfear_ctx* ctx, const cfear_cloud* cloud, cfear_scan** scan) {
   if (!ctx || !cloud || !scan) return cfear_fail(ctx, CFEAR_ERR_INVALID, "scan_create: bad argument");

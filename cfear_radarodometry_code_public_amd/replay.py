@@ -145,32 +145,88 @@ def drift_dict(row):
 G2O_INFO = (0, 1, 5)  # rows / columns of the 6x6 information (x, y, z, roll, pitch, yaw) a planar EDGE_SE2 carries: x, y, yaw
 
 
-def write_g2o(path, nodes):
+def loop_candidates(nodes, min_index_gap=6, max_dist=3.0, max_per_node=None):
+    """Pairs of keyframes far apart in the log and close in space - where a back end looks for the constraints the odometry chain does not
+    have: (from, to) with from < to, to - from >= min_index_gap and |pose_to - pose_from| <= max_dist (metres, x and y of the node
+    poses), per `to` nearest first (ties: the smaller index) and cut at max_per_node, `to` ascending. nodes: KEYFRAME_NODE_DTYPE (or
+    anything with a "pose" field) -> int32 [n, 2]. Pure numpy (no device)."""
+    xy = np.asarray(nodes["pose"], dtype=np.float64).reshape(-1, 3)[:, :2]
+    pairs = []
+    for to in range(len(xy)):
+        last = to - int(min_index_gap)
+        if last < 0:
+            continue
+        d = np.hypot(xy[:last + 1, 0] - xy[to, 0], xy[:last + 1, 1] - xy[to, 1])
+        near = np.flatnonzero(d <= max_dist)
+        near = near[np.argsort(d[near], kind="stable")]
+        if max_per_node is not None:
+            near = near[:int(max_per_node)]
+        pairs.extend((int(f), to) for f in near)
+    return np.array(pairs, dtype=np.int32).reshape(-1, 2)
+
+
+def edge_jobs(sequence, pairs, n_side=0, n_nodes=None):
+    """The jobs of capi.Odometry.keyframe_edges for (from, to) pairs of one sequence (loop_candidates): `to` is registered against the
+    candidate and up to n_side neighbours on each side of it - a small submap around the place revisited - clipped to the log (0 ..
+    n_nodes - 1; n_nodes None: up to the candidate's own index + n_side) and never `to` itself. The candidate is from[0] and the keyframe the
+    constraint is expressed to (ref = 0); the guess is `to`'s recorded pose. -> KEYFRAME_EDGE_JOB_DTYPE [len(pairs)]. Pure numpy."""
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    n_side = int(n_side)
+    if not 0 <= 2 * n_side + 1 <= capi.KF_EDGE_MAX_FROM:
+        raise ValueError("edge_jobs: n_side %d gives more than %d `from` keyframes" % (n_side, capi.KF_EDGE_MAX_FROM))
+    out = np.zeros(len(pairs), dtype=capi.KEYFRAME_EDGE_JOB_DTYPE)
+    for k, (f, to) in enumerate(pairs):
+        f, to = int(f), int(to)
+        side = [i for i in range(f - n_side, f + n_side + 1) if i != f and i != to and i >= 0 and (n_nodes is None or i < int(n_nodes))]
+        frm = [f] + side
+        out[k]["sequence"], out[k]["to"], out[k]["n_from"] = int(sequence), to, len(frm)
+        out[k]["from"][:len(frm)] = frm
+    return out
+
+
+def write_g2o(path, nodes, edges=None):
     """The keyframe graph of one sequence (capi.Odometry.keyframes: KEYFRAME_NODE_DTYPE) as g2o text: `VERTEX_SE2 index x y theta` per
     node and, for every node with a previous one, `EDGE_SE2 index prev dx dy dtheta i11 i12 i13 i22 i23 i33` - the constraint AddToGraph
     stores (odometrykeyframefuser.cpp:435-443: from the new keyframe to the previous one) with the upper triangle of the information's
-    (x, y, yaw) block. Floats are written with repr: read_g2o gives back the same bits. Pure Python (no device)."""
+    (x, y, yaw) block. edges: constraints between any keyframes (capi.Odometry.keyframe_edges: KEYFRAME_EDGE_DTYPE) - those with `success`
+    follow as `EDGE_SE2 to from ...`, by the same rule; None: the text is the nodes' alone. Floats are written with repr: read_g2o /
+    read_g2o_edges give back the same bits. Pure Python (no device)."""
     with open(path, "w") as f:
-        f.write(g2o_text(nodes))
+        f.write(g2o_text(nodes, edges))
 
 
-def g2o_text(nodes):
+def _g2o_edge(a, b, t_be, information):
+    info = np.asarray(information).reshape(6, 6)
+    tri = [info[G2O_INFO[i], G2O_INFO[j]] for i in range(3) for j in range(i, 3)]
+    return "EDGE_SE2 %d %d %s" % (int(a), int(b), " ".join(repr(float(v)) for v in list(t_be) + tri))
+
+
+def g2o_text(nodes, edges=None):
     lines = []
     for nd in nodes:
         lines.append("VERTEX_SE2 %d %s" % (int(nd["index"]), " ".join(repr(float(v)) for v in nd["pose"])))
     for nd in nodes:
         if int(nd["prev"]) < 0:
             continue
-        info = np.asarray(nd["information"]).reshape(6, 6)
-        tri = [info[G2O_INFO[i], G2O_INFO[j]] for i in range(3) for j in range(i, 3)]
-        lines.append("EDGE_SE2 %d %d %s" % (int(nd["index"]), int(nd["prev"]), " ".join(repr(float(v)) for v in list(nd["t_be"]) + tri)))
+        lines.append(_g2o_edge(nd["index"], nd["prev"], nd["t_be"], nd["information"]))
+    for e in (edges if edges is not None else ()):
+        if int(e["success"]):
+            lines.append(_g2o_edge(e["to"], e["from"], e["t_be"], e["information"]))
     return "".join(l + "\n" for l in lines)
 
 
-def read_g2o(path):
-    """write_g2o's text -> nodes (KEYFRAME_NODE_DTYPE) in file order: index, pose, prev (-1 without an edge), t_be and the (x, y, yaw)
-    block of the information, both triangles; what the text does not carry (sweep, n_cells, motion, the other information entries) is 0."""
-    verts, edges = [], {}
+def _g2o_info(v, information):
+    tri = iter(v)
+    for i in range(3):
+        for j in range(i, 3):
+            x = next(tri)
+            information[G2O_INFO[i], G2O_INFO[j]] = x
+            information[G2O_INFO[j], G2O_INFO[i]] = x
+
+
+def _g2o_lines(path):
+    """-> (vertices [(index, pose)], edges [(a, b, nine floats)], the first `EDGE_SE2 a a-1` of every a: a node's own edge)"""
+    verts, edges, own = [], [], {}
     with open(path) as f:
         for line in f:
             w = line.split()
@@ -179,20 +235,39 @@ def read_g2o(path):
             if w[0] == "VERTEX_SE2":
                 verts.append((int(w[1]), [float(v) for v in w[2:5]]))
             elif w[0] == "EDGE_SE2":
-                edges[int(w[1])] = (int(w[2]), [float(v) for v in w[3:12]])
+                a, b = int(w[1]), int(w[2])
+                if b == a - 1 and a not in own:
+                    own[a] = len(edges)
+                edges.append((a, b, [float(v) for v in w[3:12]]))
+    return verts, edges, own
+
+
+def read_g2o(path):
+    """write_g2o's text -> nodes (KEYFRAME_NODE_DTYPE) in file order: index, pose, prev (-1 without an edge), t_be and the (x, y, yaw)
+    block of the information, both triangles; what the text does not carry (sweep, n_cells, motion, the other information entries) is 0.
+    A node's own edge is the one to index - 1 (the first such line); the other edges of the file are read_g2o_edges'."""
+    verts, edges, own = _g2o_lines(path)
     nodes = np.zeros(len(verts), dtype=capi.KEYFRAME_NODE_DTYPE)
     for k, (idx, pose) in enumerate(verts):
         nodes[k]["index"], nodes[k]["pose"], nodes[k]["prev"] = idx, pose, -1
-        if idx in edges:
-            prev, v = edges[idx]
+        if idx in own:
+            _, prev, v = edges[own[idx]]
             nodes[k]["prev"], nodes[k]["t_be"] = prev, v[:3]
-            tri = iter(v[3:])
-            for i in range(3):
-                for j in range(i, 3):
-                    x = next(tri)
-                    nodes[k]["information"][G2O_INFO[i], G2O_INFO[j]] = x
-                    nodes[k]["information"][G2O_INFO[j], G2O_INFO[i]] = x
+            _g2o_info(v[3:], nodes[k]["information"])
     return nodes
+
+
+def read_g2o_edges(path):
+    """The edges of write_g2o's text that are no node's own (read_g2o) -> KEYFRAME_EDGE_DTYPE in file order: to, from, t_be and the (x, y,
+    yaw) block of the information, both triangles, success = usable = 1; what the text does not carry is 0."""
+    _, edges, own = _g2o_lines(path)
+    mine = set(own.values())
+    rest = [e for k, e in enumerate(edges) if k not in mine]
+    out = np.zeros(len(rest), dtype=capi.KEYFRAME_EDGE_DTYPE)
+    for k, (a, b, v) in enumerate(rest):
+        out[k]["to"], out[k]["from"], out[k]["t_be"], out[k]["success"], out[k]["usable"] = a, b, v[:3], 1, 1
+        _g2o_info(v[3:], out[k]["information"])
+    return out
 
 
 def write_keyframe_clouds(path, clouds, peaks=None):
@@ -232,7 +307,7 @@ def read_keyframe_clouds(path):
 
 
 def replay_grid(frames, rows, A=None, R=None, gt=None, device=0, piece=256, context_params=None, options=None, drift_on="host", keyframes=None,
-                max_keyframes=None, max_cells=None, max_points=None):
+                max_keyframes=None, max_cells=None, max_points=None, edges=None):
     """One recording under len(rows) parameter sets in one batched odometry object: frames uint8 [n, A, R], rows a list of capi.Params that
     agree in the object-wide fields (param_grid of one base does; k_strongest and submap_scan_size may be axes: the context then runs with
     the largest of each, grid_context_params, unless context_params says otherwise; so may cost: rows that differ from the context in cost
@@ -248,11 +323,18 @@ def replay_grid(frames, rows, A=None, R=None, gt=None, device=0, piece=256, cont
     per-row node arrays (KEYFRAME_NODE_DTYPE), `keyframes_dropped` [rows] and, with "cells", `keyframe_cells`: per row a list of cell
     arrays (KEYFRAME_CELL_DTYPE), one per node. keyframes="clouds": the nodes and their two clouds (capi.KF_CLOUD | capi.KF_PEAKS; max_points per
     row, default n * A * k_strongest of the context - 12 bytes a point: size it yourself for a long recording) -> `keyframe_clouds` and
-    `keyframe_peaks`: per row a list of float32 [points, 3] arrays (x, y, intensity), one per node - what write_keyframe_clouds takes."""
+    `keyframe_peaks`: per row a list of float32 [points, 3] arrays (x, y, intensity), one per node - what write_keyframe_clouds takes.
+    edges (with keyframes="cells"): dict(min_index_gap=, max_dist=, n_side=, max_per_node=), each optional - every row's loop_candidates from
+    its own nodes, registered as edge_jobs for all rows in ONE Odometry.keyframe_edges call, each row under its own parameters -> `keyframe_edges`:
+    per row an array of KEYFRAME_EDGE_DTYPE (what write_g2o takes beside the row's nodes)."""
     if drift_on not in ("host", "device"):
         raise ValueError("replay_grid: drift_on is 'host' or 'device'")
     if keyframes not in (None, "nodes", "cells", "clouds"):
         raise ValueError("replay_grid: keyframes is None, 'nodes', 'cells' or 'clouds'")
+    if edges is not None and keyframes != "cells":
+        raise ValueError("replay_grid: edges need keyframes='cells' (the keyframes are registered from their recorded cells)")
+    if edges is not None and set(edges) - {"min_index_gap", "max_dist", "n_side", "max_per_node"}:
+        raise ValueError("replay_grid: edges takes min_index_gap, max_dist, n_side and max_per_node")
     frames = np.ascontiguousarray(frames, dtype=np.uint8)
     n, A, R = frames.shape
     rows = list(rows)
@@ -288,6 +370,8 @@ def replay_grid(frames, rows, A=None, R=None, gt=None, device=0, piece=256, cont
             graph = {"keyframes": [odo.keyframes(q) for q in range(len(rows))], "keyframes_dropped": odo.keyframe_counts()[1]}
             if keyframes == "cells":
                 graph["keyframe_cells"] = [[odo.keyframe_cells(q, i) for i in range(len(nodes))] for q, nodes in enumerate(graph["keyframes"])]
+            if edges is not None:
+                graph["keyframe_edges"] = grid_edges(odo, graph["keyframes"], **edges)
             if keyframes == "clouds":
                 graph["keyframe_clouds"] = [[odo.keyframe_cloud(q, i) for i in range(len(nodes))] for q, nodes in enumerate(graph["keyframes"])]
                 graph["keyframe_peaks"] = [[odo.keyframe_cloud(q, i, peaks=True) for i in range(len(nodes))] for q, nodes in enumerate(graph["keyframes"])]
@@ -311,6 +395,18 @@ def replay_grid(frames, rows, A=None, R=None, gt=None, device=0, piece=256, cont
     if graph is not None:
         out.update(graph)
     return out
+
+
+def grid_edges(odo, nodes_per_row, min_index_gap=6, max_dist=3.0, n_side=0, max_per_node=None):
+    """The loop candidates of every sequence of `odo` (loop_candidates on nodes_per_row[q]) as edge_jobs, all of them in one
+    keyframe_edges call -> per sequence the edges of its candidates, in loop_candidates' order"""
+    jobs = [edge_jobs(q, loop_candidates(nodes, min_index_gap, max_dist, max_per_node), n_side, len(nodes)) for q, nodes in enumerate(nodes_per_row)]
+    count = [len(j) for j in jobs]
+    if sum(count) == 0:
+        return [np.zeros(0, dtype=capi.KEYFRAME_EDGE_DTYPE) for _ in jobs]
+    got = odo.keyframe_edges(np.concatenate(jobs))
+    cuts = np.cumsum([0] + count)
+    return [got[cuts[q]:cuts[q + 1]].copy() for q in range(len(jobs))]
 
 
 def sweeps(args):
@@ -354,6 +450,10 @@ def main(argv=None):
     ap.add_argument("--store_graph", default=None, metavar="PATH",
                     help="record the keyframe graph on the device (offline_odometry --store_graph) and write it to PATH as g2o text (write_g2o)")
     ap.add_argument("--max_keyframes", type=int, default=65536, help="with --store_graph: nodes the log holds (later keyframes are dropped and reported)")
+    ap.add_argument("--loop_edges", default=None, metavar="GAP,DIST[,SIDE]",
+                    help="with --store_graph: also register every keyframe against the keyframes at least GAP nodes earlier and within DIST metres of it "
+                         "(loop_candidates; SIDE neighbours on each side of the candidate join it, default 0) in one batch and append the edges to the graph")
+    ap.add_argument("--max_cells", type=int, default=4194304, help="with --loop_edges: cells the log holds, 72 bytes each (later keyframes are dropped and reported)")
     ap.add_argument("--store_clouds", default=None, metavar="PATH",
                     help="with --store_graph: also record every node's motion-compensated filtered and peaks cloud and write them to PATH (.npz, write_keyframe_clouds)")
     ap.add_argument("--max_points", type=int, default=16777216, help="with --store_clouds: points the log holds, 12 bytes each (later keyframes are dropped and reported)")
@@ -362,6 +462,14 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.store_clouds and not args.store_graph:
         ap.error("--store_clouds needs --store_graph (the clouds belong to the graph's nodes)")
+    loop = None
+    if args.loop_edges:
+        if not args.store_graph:
+            ap.error("--loop_edges needs --store_graph (the edges join the graph's nodes)")
+        w = args.loop_edges.split(",")
+        if len(w) not in (2, 3):
+            ap.error("--loop_edges takes GAP,DIST[,SIDE]")
+        loop = dict(min_index_gap=int(w[0]), max_dist=float(w[1]), n_side=int(w[2]) if len(w) == 3 else 0)
     cost = {"P2P": 0, "P2L": 1, "P2D": 2}[args.cost_type]
     loss = {"None": 0, "Huber": 1, "Cauchy": 2, "SoftLOne": 3, "Combined": 4, "Tukey": 5}[args.loss_type]
     import time
@@ -406,7 +514,8 @@ def main(argv=None):
             ctx = capi.Context(p, img.shape[0], img.shape[1], device=args.device)
             odo = ctx.odometry(1)
             if args.store_graph:
-                odo.record_keyframes(capi.KF_NODES | (capi.KF_CLOUD | capi.KF_PEAKS if args.store_clouds else 0), args.max_keyframes, 0, args.max_points)
+                odo.record_keyframes(capi.KF_NODES | (capi.KF_CELLS if loop else 0) | (capi.KF_CLOUD | capi.KF_PEAKS if args.store_clouds else 0), args.max_keyframes,
+                                     args.max_cells if loop else 0, args.max_points)
             buf = ctx.pinned((max(1, args.piece), 1, img.shape[0], img.shape[1]))
         buf[fill, 0] = img
         fill += 1
@@ -434,8 +543,11 @@ def main(argv=None):
         out["drift"] = kitti.drift(np.array(gts[:m]), est_T[:m])
     if args.store_graph:
         nodes = odo.keyframes(0)
-        write_g2o(args.store_graph, nodes)
+        loop_edges = grid_edges(odo, [nodes], **loop)[0] if loop else None
+        write_g2o(args.store_graph, nodes, loop_edges)
         out["keyframes"] = int(len(nodes))
+        if loop:
+            out["loop_candidates"], out["loop_edges"] = int(len(loop_edges)), int(np.count_nonzero(loop_edges["success"]))
         out["keyframes_dropped"] = int(odo.keyframe_counts()[1][0])
         if args.store_clouds:
             write_keyframe_clouds(args.store_clouds, [[odo.keyframe_cloud(0, i) for i in range(len(nodes))]],

@@ -691,6 +691,47 @@ int cfear_odometry_keyframe_cloud(cfear_ctx* ctx, cfear_odometry* odo, int seque
  * cfear_cloud_download and cfear_cloud_release. Errors as above; nothing is created then. Synchronous. */
 int cfear_odometry_keyframe_clouds(cfear_ctx* ctx, cfear_odometry* odo, int sequence, const int32_t* indices, int m, int peaks, cfear_cloud** clouds);
 
+/* ---- Constraints between ANY keyframes of a log, registered in one batch: the edges a SLAM back end adds to the odometry chain
+ * (Constraint3d::type loop_appearance / mini_loop / candidate, types.h:150-190). One job registers keyframe `to` - the "current scan" -
+ * against 1 .. CFEAR_KF_EDGE_MAX_FROM keyframes of the same sequence that sit fixed at their recorded node poses: Register(scans =
+ * from[0 .. n_from - 1] + [to]) exactly as cfear_register runs it (outer loop, solver, covariance, summary; no prior) under the
+ * parameters of the job's sequence - its cfear_params row and its shape's cost where it has them. All jobs run in one launch, a workgroup
+ * each; every distinct keyframe of the job list is rebuilt from the log once (as cfear_odometry_keyframe_scans builds it, under
+ * cfear_tune NN_TIE_RULE = 2 with its kd-tree) and read by all the jobs that name it. `to` may appear in `from`. */
+#define CFEAR_KF_EDGE_MAX_FROM 16
+typedef struct cfear_keyframe_edge_job {   /* 112 bytes */
+  int32_t sequence;      /* whose log */
+  int32_t to;            /* the keyframe that is registered */
+  int32_t n_from;        /* 1 .. CFEAR_KF_EDGE_MAX_FROM fixed keyframes it is registered against */
+  int32_t ref;           /* position in from[] of the keyframe the constraint is expressed to */
+  int32_t flags;         /* bit 0: guess_xyt is given; otherwise the guess is `to`'s recorded pose */
+  int32_t pad_;
+  int32_t from[CFEAR_KF_EDGE_MAX_FROM];
+  double guess_xyt[3];   /* pose of `to` in the frame of the recorded node poses */
+} cfear_keyframe_edge_job;
+/* The edge of one job, by the rule of a node's own edge: t_be and information = cfear_keyframe_constraint(from = the registered pose of
+ * `to`, to = the node pose of from[ref], cov = the registration's covariance, which starts as zeros). A registration without a usable
+ * solution leaves the covariance untouched, as cfear_register does: success = 0, t_be and information all zero. A covariance that cannot
+ * be inverted leaves inf / NaN, as in the nodes. */
+typedef struct cfear_keyframe_edge {       /* 400 bytes */
+  int32_t sequence, to, from /* = job.from[job.ref] */, n_from;
+  int32_t status;        /* 0, or a CFEAR_ERR_* of this job alone (CFEAR_ERR_UNSUPPORTED: NN_TIE_RULE could not be honoured, as cfear_register reports it) */
+  int32_t success, usable, outer_iterations;   /* as cfear_reg_summary */
+  int32_t num_residuals, num_residual_blocks, assoc_path, pad_;
+  double pose[3];        /* registered pose of `to` (the guess where the registration has no usable solution) */
+  double t_be[3];
+  double final_cost, score;
+  double information[36];
+} cfear_keyframe_edge;
+/* m jobs -> edges[m]; cov6 (m x 36 doubles) and summaries (m) receive every job's covariance and cfear_reg_summary, either may be NULL.
+ * Checked on the host before anything is launched, each refusal naming job and field: CFEAR_ERR_INVALID for a sequence out of range, an
+ * index outside the recorded prefix, n_from outside 1 .. CFEAR_KF_EDGE_MAX_FROM, ref outside 0 .. n_from - 1, a guess that is not finite
+ * or a log without CFEAR_KF_CELLS; CFEAR_ERR_EMPTY for a keyframe without cells. No edge is written then. Working memory (the scans, and
+ * per job match arrays of max(n_from, 4) x cells(to) pairs) comes from the context's pool and is back there on return. Synchronous;
+ * drains the streams the reading calls drain; writes nothing to the log or the object. */
+int cfear_odometry_keyframe_edges(cfear_ctx* ctx, cfear_odometry* odo, const cfear_keyframe_edge_job* jobs, int m, cfear_keyframe_edge* edges,
+                                  double* cov6, cfear_reg_summary* summaries);
+
 /* ---- KITTI drift of a batch's trajectories on the device: the metric of include/cfear_hip/kitti_metric.hpp (kitti_drift,
  * kitti_drift_by_length; what the reference's evaluation worker computes per job, launch/oxford/eval/utils/worker:94-98) for every
  * sequence of a batch at once. Segments: a start every 10 poses, lengths 100 ... 800 m, `last` = the first pose whose cumulative 3-D

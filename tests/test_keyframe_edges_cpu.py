@@ -1,0 +1,156 @@
+"""Constraints between any keyframes, the parts that need no device: the C ABI of cfear_odometry_keyframe_edges (header, EXPORTS, record
+sizes, the symbol in a library built for gfx950), the candidate search and the job builder of replay.py, and the graph's g2o text with
+loop edges."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from cfear_radarodometry_code_public_amd import capi, replay
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_abi_header_exports_and_sizes(hip_lib):
+    txt = open(os.path.join(ROOT, "include", "cfear_hip.h")).read()
+    assert re.search(r"#define CFEAR_KF_EDGE_MAX_FROM 16\b", txt) and capi.KF_EDGE_MAX_FROM == 16
+    assert re.search(r"int cfear_odometry_keyframe_edges\(cfear_ctx\* ctx, cfear_odometry\* odo, const cfear_keyframe_edge_job\* jobs, int m, cfear_keyframe_edge\* edges,", txt)
+    assert "cfear_odometry_keyframe_edges" in capi.EXPORTS and hasattr(hip_lib, "cfear_odometry_keyframe_edges")
+    assert capi.KEYFRAME_EDGE_JOB_DTYPE.itemsize == C.sizeof(capi.KeyframeEdgeJob) == 112
+    assert capi.KEYFRAME_EDGE_DTYPE.itemsize == C.sizeof(capi.KeyframeEdge) == 400
+    # the records field by field, as the header lays them out
+    for dt, st, ren in ((capi.KEYFRAME_EDGE_JOB_DTYPE, capi.KeyframeEdgeJob, {"from": "from_"}), (capi.KEYFRAME_EDGE_DTYPE, capi.KeyframeEdge, {"from": "from_"})):
+        for name in dt.names:
+            assert dt.fields[name][1] == getattr(st, ren.get(name, name)).offset, name
+    assert capi.KEYFRAME_EDGE_JOB_DTYPE.fields["guess_xyt"][1] == 88 and capi.KEYFRAME_EDGE_DTYPE.fields["information"][1] == 112
+    # the library is a gfx950 build that exports the entry (and the kernel is in it)
+    out = subprocess.check_output(["nm", "-D", "--defined-only", capi.lib_path()]).decode()
+    assert re.search(r" T cfear_odometry_keyframe_edges$", out, flags=re.M)
+    blob = open(capi.lib_path(), "rb").read()
+    assert b"keyframe_edges_kernel" in blob and b"gfx950" in blob
+
+
+def test_job_lists():
+    J = capi.keyframe_edge_jobs([(1, 7, 2), (0, 9, [3, 4, 5], 2), (0, 9, [3], 0, (1.0, 2.0, 0.5)), dict(sequence=2, to=5, ref=1, guess=None, **{"from": [0, 1]})])
+    assert J.dtype == capi.KEYFRAME_EDGE_JOB_DTYPE and len(J) == 4
+    assert J["sequence"].tolist() == [1, 0, 0, 2] and J["to"].tolist() == [7, 9, 9, 5] and J["n_from"].tolist() == [1, 3, 1, 2] and J["ref"].tolist() == [0, 2, 0, 1]
+    assert J["from"][1].tolist() == [3, 4, 5] + [0] * 13 and J["flags"].tolist() == [0, 0, 1, 0] and J["guess_xyt"][2].tolist() == [1.0, 2.0, 0.5]
+    assert capi.keyframe_edge_jobs(J) is not None and capi.keyframe_edge_jobs(J).tobytes() == J.tobytes()
+    for bad in ([], list(range(17))):
+        with pytest.raises(capi.CfearError):
+            capi.keyframe_edge_jobs([(0, 1, bad)])
+
+
+def nodes_at(xy):
+    n = np.zeros(len(xy), dtype=capi.KEYFRAME_NODE_DTYPE)
+    n["index"] = np.arange(len(xy))
+    n["prev"] = n["index"] - 1
+    if len(xy):
+        n["pose"][:, :2] = xy
+    return n
+
+
+def test_loop_candidates_on_crafted_poses():
+    # a line out along x, one step per node, and node 10 back at the origin's side
+    xy = [(float(i), 0.0) for i in range(10)] + [(0.0, 1.0)]
+    n = nodes_at(xy)
+    assert replay.loop_candidates(n, 6, 1.0).tolist() == [[0, 10]]  # the only pair within 1 m; 4 .. 9 are too close in the log whatever their distance
+    # the index gap: exactly min_index_gap is a candidate, one less is not
+    xy = [(0.0, 0.0)] * 8
+    n = nodes_at(xy)
+    got = replay.loop_candidates(n, 6, 1.0).tolist()
+    assert got == [[0, 6], [0, 7], [1, 7]], got
+    assert replay.loop_candidates(n, 7, 1.0).tolist() == [[0, 7]] and len(replay.loop_candidates(n, 8, 1.0)) == 0
+    # the distance: just inside and just outside max_dist (3-4-5 triangles: exactly 5.0 away)
+    n = nodes_at([(3.0, 4.0), (0.0, 100.0), (0.0, 200.0), (0.0, 0.0)])
+    assert replay.loop_candidates(n, 3, 5.0).tolist() == [[0, 3]] and replay.loop_candidates(n, 3, np.nextafter(5.0, 0.0)).tolist() == []
+    assert replay.loop_candidates(n, 3, 5.000001).tolist() == [[0, 3]] and replay.loop_candidates(n, 3, 4.999999).tolist() == []
+    # order: `to` ascending, per `to` nearest first (ties: the smaller index), and the max_per_node cut keeps the nearest
+    n = nodes_at([(2.0, 0.0), (0.5, 0.0), (1.0, 0.0), (-1.0, 0.0), (50.0, 0.0), (0.0, 0.0), (0.25, 0.0)])
+    assert replay.loop_candidates(n, 2, 2.5).tolist() == [[0, 2], [1, 3], [1, 5], [2, 5], [3, 5], [0, 5], [1, 6], [2, 6], [3, 6], [0, 6]]  # (0 is 3 m from 3)
+    assert replay.loop_candidates(n, 2, 2.5, max_per_node=2).tolist() == [[0, 2], [1, 3], [1, 5], [2, 5], [1, 6], [2, 6]]
+    assert replay.loop_candidates(n, 2, 2.5, max_per_node=1).tolist() == [[0, 2], [1, 3], [1, 5], [1, 6]]
+    got = replay.loop_candidates(n, 2, 2.5)
+    assert got.dtype == np.int32 and got.shape == (10, 2) and np.all(got[:, 0] < got[:, 1])
+    assert replay.loop_candidates(nodes_at([]), 6, 3.0).shape == (0, 2)
+    # the heading plays no part
+    n["pose"][:, 2] = np.linspace(-3, 3, len(n))
+    assert np.array_equal(replay.loop_candidates(n, 2, 2.5), got)
+
+
+def test_edge_jobs_clip_at_both_ends_and_around_to():
+    J = replay.edge_jobs(3, [(0, 9), (1, 9), (5, 9), (7, 9), (8, 10), (9, 10), (4, 5)], n_side=2, n_nodes=11)
+    assert J.dtype == capi.KEYFRAME_EDGE_JOB_DTYPE and np.all(J["sequence"] == 3) and not J["ref"].any() and not J["flags"].any()
+    got = [(int(j["to"]), j["from"][:int(j["n_from"])].tolist()) for j in J]
+    assert got == [(9, [0, 1, 2]),               # the log's start
+                   (9, [1, 0, 2, 3]),
+                   (9, [5, 3, 4, 6, 7]),         # the whole neighbourhood
+                   (9, [7, 5, 6, 8]),            # never `to`
+                   (10, [8, 6, 7, 9]),           # never `to`, the log's end
+                   (10, [9, 7, 8]),
+                   (5, [4, 2, 3, 6])], got
+    assert not J["from"][0][3:].any()
+    # no n_nodes: nothing is clipped above
+    assert replay.edge_jobs(0, [(9, 20)], n_side=2)["from"][0][:5].tolist() == [9, 7, 8, 10, 11]
+    alone = replay.edge_jobs(0, [(2, 9)])
+    assert alone["n_from"].tolist() == [1] and alone["from"][0][0] == 2
+    assert len(replay.edge_jobs(0, np.zeros((0, 2), dtype=np.int32), 2, 5)) == 0
+    with pytest.raises(ValueError):
+        replay.edge_jobs(0, [(0, 9)], n_side=8)  # 17 keyframes
+    assert replay.edge_jobs(0, [(20, 40)], n_side=7, n_nodes=50)["n_from"].tolist() == [15]
+
+
+def graph(seed=3, n=9):
+    rng = np.random.default_rng(seed)
+    nodes = nodes_at(rng.normal(size=(n, 2)) * 7)
+    nodes["pose"][:, 2] = rng.uniform(-3, 3, n)
+    nodes["t_be"][1:] = rng.normal(size=(n - 1, 3))
+    nodes["information"][1:] = rng.normal(size=(n - 1, 6, 6)) * 1e3
+    edges = np.zeros(6, dtype=capi.KEYFRAME_EDGE_DTYPE)
+    edges["to"], edges["from"] = [6, 7, 7, 8, 5, 8], [0, 1, 0, 2, 4, 7]  # (two share their first id with each other and with a node's own edge; two go to `to - 1`)
+    edges["success"] = [1, 1, 0, 1, 1, 1]
+    edges["usable"] = 1
+    edges["t_be"] = rng.normal(size=(6, 3))
+    edges["information"] = rng.normal(size=(6, 6, 6)) * 1e3
+    edges["pose"] = rng.normal(size=(6, 3))
+    return nodes, edges
+
+
+def test_g2o_with_loop_edges(tmp_path):
+    nodes, edges = graph()
+    a, b, c = tmp_path / "a.g2o", tmp_path / "b.g2o", tmp_path / "c.g2o"
+    replay.write_g2o(a, nodes)
+    replay.write_g2o(b, nodes, edges=None)
+    replay.write_g2o(c, nodes, edges)
+    text = open(a).read()
+    assert open(b).read() == text == replay.g2o_text(nodes)  # without the argument: today's text, byte for byte
+    assert text.count("EDGE_SE2") == len(nodes) - 1 and text.count("VERTEX_SE2") == len(nodes)
+    full = open(c).read()
+    assert full.startswith(text) and full[len(text):].count("\n") == 5  # the edge without `success` is not written
+    assert full[len(text):].splitlines()[0].startswith("EDGE_SE2 6 0 ") and "EDGE_SE2 7 0 " not in full
+    # the nodes of the file with edges are the nodes of the file without
+    assert replay.read_g2o(c).tobytes() == replay.read_g2o(a).tobytes()
+    back = replay.read_g2o(a)
+    for f in ("index", "prev", "pose", "t_be"):
+        assert back[f].tobytes() == nodes[f].tobytes(), f
+    # ... and the edges come back bit for bit
+    got = replay.read_g2o_edges(c)
+    exp = edges[edges["success"] == 1]
+    assert got.dtype == capi.KEYFRAME_EDGE_DTYPE and len(got) == 5 and got["success"].all()
+    blk = np.ix_(replay.G2O_INFO, replay.G2O_INFO)
+    for f in ("to", "from", "t_be"):
+        assert got[f].tobytes() == exp[f].tobytes(), f
+    for g, e in zip(got, exp):
+        up = np.triu(e["information"][blk])
+        assert g["information"][blk].tobytes() == (up + np.triu(up, 1).T).tobytes()
+        rest = g["information"].copy(); rest[blk] = 0
+        assert not rest.any() and not g["pose"].any()
+    assert len(replay.read_g2o_edges(a)) == 0
+    # no edges at all, and none that succeeded
+    replay.write_g2o(b, nodes, edges[:0])
+    assert open(b).read() == text
+    replay.write_g2o(b, nodes, edges[2:3])
+    assert open(b).read() == text
