@@ -242,9 +242,11 @@ extern "C" __attribute__((visibility("hidden"))) int cfear_ensure_hstage(cfear_c
 extern "C" __attribute__((visibility("hidden"))) void* cfear_hpool_alloc(cfear_ctx* ctx, size_t bytes, size_t* got);  // null: no mirror (not an error)
 extern "C" __attribute__((visibility("hidden"))) void cfear_hpool_free(cfear_ctx* ctx, void* p, size_t bytes);
 extern "C" __attribute__((visibility("hidden"))) int cfear_upload_image(cfear_ctx* ctx, void* d_dst, const void* h_src, size_t bytes);
+// one axis of a cost surface around v0: the coordinates of the cells the reference's loop visits into out[0 .. pixels) (null: only counted); their number
+extern "C" __attribute__((visibility("hidden"))) int cfear_surface_axis(double v0, double res, int width, int pixels, double* out);
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-// pipeline.hip
+// percall.hip: the per-call API (its kernels are pipeline.hip's, behind pipeline_launch.h). What other units need of it: a cloud ...
 extern "C" __attribute__((visibility("hidden"))) int cfear_cloud_alloc(cfear_ctx* ctx, int cap, cfear_cloud** out);
 // ... and a blank per-call scan of cap_points points and cap_cells cells (their cfear_cell records included; with_kd: and the kd-tree's arrays):
 // the handle, its block of the context's pool (*d_block) and in *hdr the header that belongs at the block's front. n_cells: what

@@ -13,7 +13,7 @@
 // Behind the kernels the graph's host side: the log is cfear_odometry::kf (KeyframeLog, keyframe_dev.h). pipeline.hip's sweep launches the
 // recorder and the cloud stage through the two launchers of that header; the setters (cfear_odometry_set_keyframe_recording / _clouds)
 // and the reading routes (counts, nodes, cells, scans, edges, cloud sizes, cloud, clouds) are here. A scan rebuilt from the log is a per-call
-// scan of pipeline.hip: cfear_scan_alloc makes the blank one, cfear_scan_release takes it back.
+// scan of percall.hip: cfear_scan_alloc makes the blank one, cfear_scan_release takes it back.
 #include <algorithm>
 
 #include "odometry_obj.h"

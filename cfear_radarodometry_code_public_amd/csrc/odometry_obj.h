@@ -1,8 +1,9 @@
 // odometry_obj.h -- the batched odometry object (cfear_odometry) and the few helpers that more than one translation unit needs:
-// pipeline.hip (the step's kernels, the launch layer that names them, the scan and scratch layouts, the surface and cov-sampling routes),
+// pipeline.hip (the step's kernels and the launch layer that names them, the object's scan and scratch blocks over scan_layout.h),
 // odometry_run.hip (the object's life: creation, reset, destruction, the steps, the profile, the replay, and the plain reads: poses,
-// covariances, status, summary), odometry_seq.hip (the per-sequence configuration: setters, getters, the device table) and keyframes.hip
-// (the keyframe graph: its four kernels, its setters and its reading routes over KeyframeLog, keyframe_dev.h). The middle two hold no kernel.
+// covariances, status, summary), odometry_seq.hip (the per-sequence configuration: setters, getters, the device table), odometry_cov.hip
+// (the cost-sampling and surface routes over the registrations' records) and keyframes.hip (the keyframe graph: its four kernels, its
+// setters and its reading routes over KeyframeLog, keyframe_dev.h). The middle three hold no kernel.
 #pragma once
 #include <memory>
 
@@ -180,7 +181,7 @@ static cfear_seq_object odo_seq_object(const cfear_ctx* ctx, const cfear_odometr
     const int _rc = (expr);                                                \
     if (_rc != CFEAR_OK) return cfear_fail((ctx), _rc, msg.c_str());       \
   } while (0)
-// ---- pipeline.hip: what odometry_run.hip calls of the launch layer ----
+// ---- pipeline.hip: what odometry_run.hip and odometry_cov.hip call of the launch layer ----
 // the kernel parameters of one odometry step of `o` under the context's current settings
 __attribute__((visibility("hidden"))) OdoParams odo_params(const cfear_ctx* ctx, const cfear_odometry* o);
 // Where a sweep's points come from: the filter's slots, or clouds of `cap` points each with their counts

@@ -1,7 +1,8 @@
 // odometry_run.hip -- the life of a batched odometry object (struct cfear_odometry, odometry_obj.h): creation, reset and destruction, the step
 // entry points, the phase times and the profile, the replay of a recording, and the plain reads (poses, covariances, status, summary). No kernel is defined here: the sweeps go through the launch
 // layer of pipeline.hip (odo_params, odo_launch_sweep, odo_launch_cfar), the filters through kstrongest.hip / cfar.hip, the persistent replay
-// through replay.hip; the sizes and schedules are odometry_plan.h's.
+// through replay.hip; the sizes and schedules are odometry_plan.h's. What the object does with the records of its registrations
+// (cost-sampling covariance, cost surfaces) is odometry_cov.hip's.
 #include <algorithm>
 #include <memory>
 #include <new>

@@ -94,7 +94,7 @@ __global__ __launch_bounds__(BLOCK_F) void replay_chunk_cloud_kernel(const float
 }
 }  // namespace
 
-// pipeline.hip (replay_impl_queue): the chunk kernels on `stream`
+// odometry_run.hip (replay_impl_queue): the chunk kernels on `stream`
 void cfear_launch_replay_chunk_cloud(const float* d_xyi, int cap, const int* d_counts, int cnt, int B, const OdoParams& OP, SeqState* states, const BlockScratch* scratch,
                                      double* cov_work, cfear_reg_summary* summaries, double* poses_out, cfear_sweep_record* records, hipStream_t stream) {
   hipLaunchKernelGGL(replay_chunk_cloud_kernel, dim3(B), dim3(BLOCK_F), 0, stream, d_xyi, cap, d_counts, cnt, B, OP, states, scratch, cov_work, summaries, poses_out, records);

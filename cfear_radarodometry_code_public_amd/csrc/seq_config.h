@@ -1,8 +1,8 @@
 // seq_config.h -- what the sequences of a batched odometry object run with, as ONE value: the five per-sequence tables
 // (cfear_odometry_set_sequence_params / _sources / _shapes / _detectors, cfear_odometry_set_fuser_options), the one accessor that answers
 // "what does sequence q run with?", the facts the launch layer derives from the tables, and every rule a setter refuses by. Host arithmetic
-// only (no device, no context): shared by odometry_seq.hip (the setters and the one commit path), pipeline.hip (the step, replay and
-// surface routes) and host/seq_config_check (tests/test_seq_config_cpu.py).
+// only (no device, no context): shared by odometry_seq.hip (the setters and the one commit path), pipeline.hip (the step and replay
+// launches), odometry_cov.hip (the surface route) and host/seq_config_check (tests/test_seq_config_cpu.py).
 //
 // A setter is one cfear_seq_set_* call - the call's checks, a candidate that is the object's configuration with one table replaced, the
 // consistency check of the candidate - and the commit of the candidate (odo_commit_config); a refused candidate never touches the object.

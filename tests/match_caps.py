@@ -23,7 +23,7 @@ def caps_of(match_lds_cap):
     return {P2D: doubles // 8, P2L: doubles // 7, P2P: doubles // 5}
 
 
-# per-call entries and the 64-scan step kernels (pipeline.hip compiles registration_dev.h with its default)
+# the kernels of the per-call entries (percall.hip) and the 64-scan step kernels (pipeline.hip compiles registration_dev.h with its default)
 LDS_CAP = caps_of(_define("registration_dev.h", "CFEAR_MATCH_LDS_CAP"))
 REG_BLOCK = _define("registration_dev.h", "CFEAR_REG_BLOCK")  # BLOCK_R: one block of source cells (association path 1)
 # instantiation -> ({cost: capacity}, threads that evaluate). (register_step_large.hip has a second value for its two-workgroup A/B

@@ -263,7 +263,7 @@ def _world(T, sigma, seed, polar):
 #   step64: the same entry, submap_scan_size 8, cfear_tune LARGE_SUBMAP_KERNEL 1: the 64-scan step kernel of pipeline.hip
 #   large:  the same, LARGE_SUBMAP_KERNEL 2: register_step_large_kernel
 #   replay: cfear_odometry_replay_host on rendered sweeps, submap_scan_size 11 (twelve sweeps): replay_chunk_kernel
-#   call:   cfear_register / cfear_get_cost and the other per-call entries on scans of the clouds, four keyframes (pipeline.hip)
+#   call:   cfear_register / cfear_get_cost and the other per-call entries on scans of the clouds, four keyframes (percall.hip; their kernels are pipeline.hip's)
 ROUTES = {"step4": ("register_step", 4, False), "step64": ("pipeline", 8, False), "large": ("register_step_large", 8, False),
           "replay": ("replay", 11, True), "call": ("pipeline", 4, False)}
 LOSS_NAME = {HUBER: "huber", CAUCHY: "cauchy", TUKEY: "tukey"}
