@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from cfear_radarodometry_code_public_amd import capi, synth
+from sweep_compare import assert_sweep_is_the_fusers
 
 pytestmark = pytest.mark.gpu
 RR = np.float32(0.0595238)
@@ -127,13 +128,7 @@ def test_batched_odometry_with_more_bearings_than_the_cloud_pass_tabulates(oracl
         got = odo.poses()
         for q in range(2):
             exp = fus[q].process_polar(streams[q][t])
-            S, nc, nk = odo.summary(q)
-            So = fus[q].last_summary()
-            assert nc == len(fus[q].last_cells()), (t, q, nc, len(fus[q].last_cells()))
-            if t > 0:
-                assert (nk, S.outer_iterations, S.num_residuals) == (fus[q].num_keyframes, So.outer_iterations, So.num_residuals), (t, q)
-                assert list(S.inner_iterations[:8]) == list(So.inner_iterations[:8]), (t, q)
-                assert np.all(np.abs(got[q][:2] - exp[:2]) < 1e-4) and abs(got[q][2] - exp[2]) < 1e-5, (t, q, got[q], exp)
+            assert_sweep_is_the_fusers(odo, q, t, got[q], fus[q], exp)
     assert len(fus[0].last_cells()) > 50
     odo.release()
     ctx.close()
