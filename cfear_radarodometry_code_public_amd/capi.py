@@ -169,6 +169,59 @@ def keyframe_edge_jobs(jobs):
     return out
 
 
+# cfear_pg_edge / cfear_pg_options / cfear_pg_summary (include/cfear_hip.h): the batched planar pose-graph optimiser (pose_graph.hip). An
+# edge is a g2o `EDGE_SE2 a b ...` line as replay writes it; posegraph.py builds them from nodes and keyframe edges
+class PgEdge(C.Structure):
+    _fields_ = [("a", C.c_int32), ("b", C.c_int32), ("flags", C.c_int32), ("pad_", C.c_int32), ("z", C.c_double * 3), ("info", C.c_double * 6)]
+
+
+class PgOptions(C.Structure):
+    _fields_ = [("max_iterations", C.c_int32), ("max_linear_iterations", C.c_int32), ("loss", C.c_int32), ("pad_", C.c_int32),
+                ("linear_tolerance", C.c_double), ("function_tolerance", C.c_double), ("parameter_tolerance", C.c_double),
+                ("initial_damping", C.c_double), ("loss_limit", C.c_double)]
+
+    def __repr__(self):
+        return "PgOptions(%s)" % ", ".join("%s=%r" % (f, getattr(self, f)) for f, _ in self._fields_ if f != "pad_")
+
+
+class PgSummary(C.Structure):
+    _fields_ = [("initial_cost", C.c_double), ("final_cost", C.c_double), ("iterations", C.c_int32), ("accepted", C.c_int32),
+                ("linear_iterations", C.c_int32), ("edges_used", C.c_int32), ("edges_skipped", C.c_int32), ("termination", C.c_int32),
+                ("status", C.c_int32), ("pad_", C.c_int32)]
+
+
+PG_EDGE_DTYPE = np.dtype([("a", "i4"), ("b", "i4"), ("flags", "i4"), ("pad_", "i4"), ("z", "f8", 3), ("info", "f8", 6)])
+PG_SUMMARY_DTYPE = np.dtype([("initial_cost", "f8"), ("final_cost", "f8"), ("iterations", "i4"), ("accepted", "i4"), ("linear_iterations", "i4"),
+                             ("edges_used", "i4"), ("edges_skipped", "i4"), ("termination", "i4"), ("status", "i4"), ("pad_", "i4")])
+assert PG_EDGE_DTYPE.itemsize == C.sizeof(PgEdge) == 88 and PG_SUMMARY_DTYPE.itemsize == C.sizeof(PgSummary) == 48 and C.sizeof(PgOptions) == 56
+PG_CONVERGED_COST, PG_CONVERGED_STEP, PG_ITERATION_LIMIT, PG_DAMPING_LIMIT, PG_NOTHING_TO_DO = 0, 1, 2, 3, 4  # CFEAR_PG_*
+PG_TERMINATION = ("converged on cost", "converged on step", "iteration limit", "damping limit", "nothing to do")
+LOSS_NONE, LOSS_HUBER, LOSS_CAUCHY = 0, 1, 2  # CFEAR_LOSS_* the optimiser takes
+
+
+def pg_options(**kw):
+    """cfear_pg_default_options with fields replaced: max_iterations (50), max_linear_iterations (0 = 30 x nodes), linear_tolerance (1e-8),
+    function_tolerance (1e-12), parameter_tolerance (1e-10), initial_damping (1e-4), loss (LOSS_NONE), loss_limit (0.1)"""
+    o = PgOptions()
+    lib().cfear_pg_default_options(C.byref(o))
+    for k, v in kw.items():
+        if k == "pad_" or not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
+
+
+def pose_graph_cost_host(poses, edges, loss=0, loss_limit=0.1):
+    """cfear_pose_graph_cost_host (host only, no device): F of one graph at poses [n, 3] -> (cost, edges used, edges skipped)"""
+    x = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3)
+    E = np.ascontiguousarray(edges, dtype=PG_EDGE_DTYPE).reshape(-1)
+    cost, used, skipped = C.c_double(), C.c_int32(), C.c_int32()
+    rc = lib().cfear_pose_graph_cost_host(x.ctypes.data, len(x), E.ctypes.data, len(E), int(loss), float(loss_limit), C.byref(cost), C.byref(used), C.byref(skipped))
+    if rc != 0:
+        raise CfearError("cfear_pose_graph_cost_host failed rc=%d" % rc)
+    return cost.value, used.value, skipped.value
+
+
 KF_NODES, KF_CELLS = 1, 2  # CFEAR_KF_NODES / CFEAR_KF_CELLS
 KF_CLOUD, KF_PEAKS = 4, 8  # CFEAR_KF_CLOUD / CFEAR_KF_PEAKS (cfear_odometry_set_keyframe_clouds)
 STATUS_CELLS_LOST, STATUS_POINTS_LOST, STATUS_KEYFRAMES_DROPPED = 1, 2, 4  # the bits of a sequence's word in cfear_odometry_status
@@ -213,6 +266,7 @@ EXPORTS = [
     "cfear_keyframe_constraint", "cfear_odometry_set_keyframe_recording", "cfear_odometry_keyframe_counts", "cfear_odometry_keyframe_nodes",
     "cfear_odometry_keyframe_cells", "cfear_odometry_keyframe_scans", "cfear_odometry_keyframe_edges",
     "cfear_odometry_set_keyframe_clouds", "cfear_odometry_keyframe_cloud_sizes", "cfear_odometry_keyframe_cloud", "cfear_odometry_keyframe_clouds",
+    "cfear_pg_default_options", "cfear_pose_graph_optimize", "cfear_odometry_keyframe_optimize", "cfear_pose_graph_cost_host",
     "cfear_drift_segments", "cfear_drift_plan_create", "cfear_drift_plan_release", "cfear_drift_device", "cfear_drift_host",
 ]
 
@@ -325,6 +379,10 @@ def lib():
         "cfear_odometry_keyframe_cloud_sizes": (C.c_int, [vp, vp, C.c_int, C.c_int, i32p, i32p, C.c_int, C.POINTER(C.c_int)]),
         "cfear_odometry_keyframe_cloud": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, f32p, C.c_int, C.POINTER(C.c_int)]),
         "cfear_odometry_keyframe_clouds": (C.c_int, [vp, vp, C.c_int, i32p, C.c_int, C.c_int, C.POINTER(vp)]),
+        "cfear_pg_default_options": (None, [C.POINTER(PgOptions)]),
+        "cfear_pose_graph_optimize": (C.c_int, [vp, C.c_int, i32p, i32p, vp, i32p, C.POINTER(PgOptions), f64p, vp]),
+        "cfear_odometry_keyframe_optimize": (C.c_int, [vp, vp, vp, C.c_int, C.POINTER(PgOptions), f64p, C.c_int, i32p, vp]),
+        "cfear_pose_graph_cost_host": (C.c_int, [f64p, C.c_int, vp, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
         "cfear_drift_segments": (C.c_int, [f64p, C.c_int, i32p, i32p, i32p, C.c_int, C.POINTER(C.c_int)]),
         "cfear_drift_plan_create": (C.c_int, [vp, f64p, C.c_int, C.POINTER(vp)]),
         "cfear_drift_plan_release": (None, [vp, vp]),
@@ -698,6 +756,35 @@ class Context:
         h = C.c_void_p()
         self._check(self._L.cfear_drift_plan_create(self._h, g.ctypes.data, len(g), C.byref(h)), "cfear_drift_plan_create")
         return DriftPlan(self, h, len(g))
+
+    def pose_graph_optimize(self, poses, edges, fixed=None, options=None, **kw):
+        """cfear_pose_graph_optimize: many planar pose graphs in one launch. poses: a list of [n_g, 3] arrays (x, y, theta), one per graph, or one
+        such array (a single graph); edges: per graph an array of PG_EDGE_DTYPE (posegraph.problem builds them); fixed: per graph the node
+        that is held (None: node 0); options: a PgOptions, or its fields as keywords (pg_options). -> (optimised poses in the shape given,
+        summaries: PG_SUMMARY_DTYPE [graphs]). The input arrays are not changed."""
+        single = isinstance(poses, np.ndarray) and poses.ndim == 2
+        P = [poses] if single else list(poses)
+        E = [edges] if single else list(edges)
+        if len(P) != len(E) or not P:
+            raise CfearError("pose_graph_optimize: %d pose arrays, %d edge arrays" % (len(P), len(E)))
+        P = [np.ascontiguousarray(p, dtype=np.float64).reshape(-1, 3) for p in P]
+        E = [np.ascontiguousarray(e, dtype=PG_EDGE_DTYPE).reshape(-1) for e in E]
+        noff = np.concatenate([[0], np.cumsum([len(p) for p in P])]).astype(np.int32)
+        eoff = np.concatenate([[0], np.cumsum([len(e) for e in E])]).astype(np.int32)
+        x = np.ascontiguousarray(np.concatenate(P, axis=0))
+        ed = np.ascontiguousarray(np.concatenate(E))
+        fx = None
+        if fixed is not None:
+            fx = np.ascontiguousarray(np.atleast_1d(fixed), dtype=np.int32)
+            if len(fx) != len(P):
+                raise CfearError("pose_graph_optimize: %d fixed nodes for %d graphs" % (len(fx), len(P)))
+        opt = options if options is not None else pg_options(**kw)
+        sums = np.zeros(len(P), dtype=PG_SUMMARY_DTYPE)
+        self._check(self._L.cfear_pose_graph_optimize(self._h, len(P), noff.ctypes.data, eoff.ctypes.data, ed.ctypes.data if len(ed) else None,
+                                                      fx.ctypes.data if fx is not None else None, C.byref(opt), x.ctypes.data if len(x) else None,
+                                                      sums.ctypes.data), "cfear_pose_graph_optimize")
+        out = [x[noff[g]:noff[g + 1]].copy() for g in range(len(P))]
+        return (out[0] if single else out), sums
 
     def odometry(self, n_sequences, overlap=None, filter_cus=None, max_cells=None, reg_order=None, large_kernel=None):
         """overlap: None = the context's setting; 0 / False = the three kernels in turn on the context stream; n >= 1 = the filter one
@@ -1142,6 +1229,22 @@ class Odometry:
         self._ctx._check(self._ctx._L.cfear_odometry_keyframe_edges(self._ctx._h, self._h, J.ctypes.data, m, edges.ctypes.data, cov.ctypes.data if details else None,
                                                                     sums if details else None), "cfear_odometry_keyframe_edges")
         return (edges, cov, [sums[i] for i in range(m)]) if details else edges
+
+    def keyframe_optimize(self, edges=None, options=None, **kw):
+        """cfear_odometry_keyframe_optimize: the graphs of the log, one per sequence, optimised in one launch - the chain and the initial
+        poses are read from the recorded nodes on the device, edges (KEYFRAME_EDGE_DTYPE, as keyframe_edges returned them; any sequences,
+        any order; those without success are left out) join them under the options' loss. options: a PgOptions, or its fields as keywords.
+        -> (per sequence an array [n_q, 3] of optimised poses, summaries: PG_SUMMARY_DTYPE [B]). Nothing is written to the log."""
+        E = np.zeros(0, dtype=KEYFRAME_EDGE_DTYPE) if edges is None else np.ascontiguousarray(edges, dtype=KEYFRAME_EDGE_DTYPE).reshape(-1)
+        opt = options if options is not None else pg_options(**kw)
+        off = np.zeros(self.B + 1, dtype=np.int32)
+        fn, ctx = self._ctx._L.cfear_odometry_keyframe_optimize, self._ctx
+        ep = E.ctypes.data if len(E) else None
+        ctx._check(fn(ctx._h, self._h, ep, len(E), C.byref(opt), None, 0, off.ctypes.data, None), "cfear_odometry_keyframe_optimize")
+        x = np.zeros((max(int(off[-1]), 1), 3))
+        sums = np.zeros(self.B, dtype=PG_SUMMARY_DTYPE)
+        ctx._check(fn(ctx._h, self._h, ep, len(E), C.byref(opt), x.ctypes.data, int(off[-1]), off.ctypes.data, sums.ctypes.data), "cfear_odometry_keyframe_optimize")
+        return [x[off[q]:off[q + 1]].copy() for q in range(self.B)], sums
 
     def keyframe_cloud_sizes(self, q):
         """-> (n_cloud [n], n_peaks [n]): points of the filtered and of the peaks cloud of every recorded node of sequence q"""

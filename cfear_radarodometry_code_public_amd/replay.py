@@ -270,6 +270,29 @@ def read_g2o_edges(path):
     return out
 
 
+def rebase_trajectory(poses, nodes, optimised):
+    """The per-sweep trajectory of one sequence carried onto its optimised keyframes: for each sweep s, T'_s = T'_k * T_k^-1 * T_s with k the
+    last keyframe whose `sweep` <= s (T_k the node's recorded pose, T'_k its optimised one). poses [n, 3] (x, y, theta), nodes
+    KEYFRAME_NODE_DTYPE (or anything with "sweep" and "pose"), optimised [len(nodes), 3] (Odometry.keyframe_optimize) -> [n, 3]. Sweeps in
+    front of the first keyframe stay. Headings are not wrapped. Pure numpy (no device)."""
+    poses = np.asarray(poses, dtype=np.float64).reshape(-1, 3)
+    opt = np.asarray(optimised, dtype=np.float64).reshape(-1, 3)
+    kp = np.asarray(nodes["pose"], dtype=np.float64).reshape(-1, 3)
+    sweep = np.asarray(nodes["sweep"], dtype=np.int64).reshape(-1)
+    if len(opt) != len(kp):
+        raise ValueError("rebase_trajectory: %d optimised poses for %d nodes" % (len(opt), len(kp)))
+    out = poses.copy()
+    k = np.searchsorted(sweep, np.arange(len(poses)), side="right") - 1
+    has = k >= 0
+    k = k[has]
+    c, s = np.cos(kp[k, 2]), np.sin(kp[k, 2])
+    dx, dy = poses[has, 0] - kp[k, 0], poses[has, 1] - kp[k, 1]
+    rx, ry, rt = c * dx + s * dy, -s * dx + c * dy, poses[has, 2] - kp[k, 2]
+    c, s = np.cos(opt[k, 2]), np.sin(opt[k, 2])
+    out[has] = np.stack([opt[k, 0] + c * rx - s * ry, opt[k, 1] + s * rx + c * ry, opt[k, 2] + rt], axis=1)
+    return out
+
+
 def write_keyframe_clouds(path, clouds, peaks=None):
     """The recorded clouds of one run as one .npz: clouds / peaks are per sequence a list of float32 [n, 3] arrays, one per node
     (capi.Odometry.keyframe_cloud(q, i) / (q, i, peaks=True); peaks None: a run without peaks clouds). Per sequence q the file holds the
@@ -307,7 +330,7 @@ def read_keyframe_clouds(path):
 
 
 def replay_grid(frames, rows, A=None, R=None, gt=None, device=0, piece=256, context_params=None, options=None, drift_on="host", keyframes=None,
-                max_keyframes=None, max_cells=None, max_points=None, edges=None):
+                max_keyframes=None, max_cells=None, max_points=None, edges=None, optimise=None):
     """One recording under len(rows) parameter sets in one batched odometry object: frames uint8 [n, A, R], rows a list of capi.Params that
     agree in the object-wide fields (param_grid of one base does; k_strongest and submap_scan_size may be axes: the context then runs with
     the largest of each, grid_context_params, unless context_params says otherwise; so may cost: rows that differ from the context in cost
@@ -326,7 +349,11 @@ def replay_grid(frames, rows, A=None, R=None, gt=None, device=0, piece=256, cont
     `keyframe_peaks`: per row a list of float32 [points, 3] arrays (x, y, intensity), one per node - what write_keyframe_clouds takes.
     edges (with keyframes="cells"): dict(min_index_gap=, max_dist=, n_side=, max_per_node=), each optional - every row's loop_candidates from
     its own nodes, registered as edge_jobs for all rows in ONE Odometry.keyframe_edges call, each row under its own parameters -> `keyframe_edges`:
-    per row an array of KEYFRAME_EDGE_DTYPE (what write_g2o takes beside the row's nodes)."""
+    per row an array of KEYFRAME_EDGE_DTYPE (what write_g2o takes beside the row's nodes).
+    optimise (with keyframes): a dict of capi.pg_options fields (may be empty) - every row's graph, its chain and with edges= its loop edges,
+    optimised in ONE Odometry.keyframe_optimize call -> `keyframe_poses_optimised`: per row [nodes, 3], `optimise_summaries`
+    (capi.PG_SUMMARY_DTYPE [rows]), `poses_optimised` [n, rows, 3]: every row's trajectory carried onto its optimised keyframes
+    (rebase_trajectory) and, with gt, `drift_optimised`: its drift beside `drift`, scored the same way. None: nothing of this runs."""
     if drift_on not in ("host", "device"):
         raise ValueError("replay_grid: drift_on is 'host' or 'device'")
     if keyframes not in (None, "nodes", "cells", "clouds"):
@@ -335,6 +362,8 @@ def replay_grid(frames, rows, A=None, R=None, gt=None, device=0, piece=256, cont
         raise ValueError("replay_grid: edges need keyframes='cells' (the keyframes are registered from their recorded cells)")
     if edges is not None and set(edges) - {"min_index_gap", "max_dist", "n_side", "max_per_node"}:
         raise ValueError("replay_grid: edges takes min_index_gap, max_dist, n_side and max_per_node")
+    if optimise is not None and keyframes is None:
+        raise ValueError("replay_grid: optimise needs keyframes (the graphs are the recorded ones)")
     frames = np.ascontiguousarray(frames, dtype=np.uint8)
     n, A, R = frames.shape
     rows = list(rows)
@@ -375,11 +404,19 @@ def replay_grid(frames, rows, A=None, R=None, gt=None, device=0, piece=256, cont
             if keyframes == "clouds":
                 graph["keyframe_clouds"] = [[odo.keyframe_cloud(q, i) for i in range(len(nodes))] for q, nodes in enumerate(graph["keyframes"])]
                 graph["keyframe_peaks"] = [[odo.keyframe_cloud(q, i, peaks=True) for i in range(len(nodes))] for q, nodes in enumerate(graph["keyframes"])]
-        scored = None
+        rebased = None
+        if optimise is not None:
+            loops = np.concatenate(graph["keyframe_edges"]) if edges is not None else None
+            graph["keyframe_poses_optimised"], graph["optimise_summaries"] = odo.keyframe_optimize(loops, **optimise)
+            rebased = np.stack([rebase_trajectory(poses[:, q], graph["keyframes"][q], graph["keyframe_poses_optimised"][q]) for q in range(len(rows))], axis=1)
+            graph["poses_optimised"] = rebased
+        scored = scored_opt = None
         if gt is not None and drift_on == "device":
             plan = ctx.drift_plan(np.asarray(gt)[:n])
             try:
                 scored = plan.score(poses)
+                if rebased is not None:
+                    scored_opt = plan.score(rebased)
             finally:
                 plan.release()
     finally:
@@ -394,6 +431,11 @@ def replay_grid(frames, rows, A=None, R=None, gt=None, device=0, piece=256, cont
     out = {"poses": poses, "records": rec, "drift": drift}
     if graph is not None:
         out.update(graph)
+    if rebased is not None and gt is not None:
+        if scored_opt is not None:
+            out["drift_optimised"] = [drift_dict(r) for r in scored_opt]
+        else:
+            out["drift_optimised"] = [kitti.drift(np.asarray(gt)[:n], kitti.poses_from_xyt(rebased[:, q])) for q in range(len(rows))]
     return out
 
 
@@ -453,6 +495,11 @@ def main(argv=None):
     ap.add_argument("--loop_edges", default=None, metavar="GAP,DIST[,SIDE]",
                     help="with --store_graph: also register every keyframe against the keyframes at least GAP nodes earlier and within DIST metres of it "
                          "(loop_candidates; SIDE neighbours on each side of the candidate join it, default 0) in one batch and append the edges to the graph")
+    ap.add_argument("--optimize", action="store_true",
+                    help="with --store_graph: optimise the graph - the chain and, with --loop_edges, the loop edges - on the device (Odometry.keyframe_optimize) "
+                         "and write the optimised vertices; the edges are written as recorded")
+    ap.add_argument("--optimize_loss", default="None", choices=["None", "Huber", "Cauchy"], help="with --optimize: the loss on the loop edges")
+    ap.add_argument("--optimize_loss_limit", type=float, default=1.0, help="with --optimize_loss: its limit, on the edge's whitened error")
     ap.add_argument("--max_cells", type=int, default=4194304, help="with --loop_edges: cells the log holds, 72 bytes each (later keyframes are dropped and reported)")
     ap.add_argument("--store_clouds", default=None, metavar="PATH",
                     help="with --store_graph: also record every node's motion-compensated filtered and peaks cloud and write them to PATH (.npz, write_keyframe_clouds)")
@@ -462,6 +509,8 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.store_clouds and not args.store_graph:
         ap.error("--store_clouds needs --store_graph (the clouds belong to the graph's nodes)")
+    if args.optimize and not args.store_graph:
+        ap.error("--optimize needs --store_graph (the graph that is optimised is the one that is written)")
     loop = None
     if args.loop_edges:
         if not args.store_graph:
@@ -544,6 +593,12 @@ def main(argv=None):
     if args.store_graph:
         nodes = odo.keyframes(0)
         loop_edges = grid_edges(odo, [nodes], **loop)[0] if loop else None
+        if args.optimize:
+            opt, sums = odo.keyframe_optimize(loop_edges, loss={"None": 0, "Huber": 1, "Cauchy": 2}[args.optimize_loss], loss_limit=args.optimize_loss_limit)
+            nodes = nodes.copy()
+            nodes["pose"] = opt[0]
+            out["optimize"] = {f: (float(sums[0][f]) if f.endswith("_cost") else int(sums[0][f])) for f in capi.PG_SUMMARY_DTYPE.names if f != "pad_"}
+            out["optimize"]["termination"] = capi.PG_TERMINATION[int(sums[0]["termination"])]
         write_g2o(args.store_graph, nodes, loop_edges)
         out["keyframes"] = int(len(nodes))
         if loop:

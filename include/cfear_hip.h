@@ -776,6 +776,89 @@ int cfear_drift_device(cfear_ctx* ctx, const cfear_drift_plan* plan, const void*
 int cfear_drift_host(cfear_ctx* ctx, const cfear_drift_plan* plan, const void* h_poses, size_t sweep_stride, size_t seq_stride,
                      int n_sweeps, int n_sequences, cfear_drift* h_out);
 
+/* ---- Optimising the keyframe graph on the device: batched SE(2) pose graphs (pose_graph.hip). Many independent graphs in one call and
+ * one launch, a workgroup per graph with the whole Levenberg-Marquardt loop on the device. A graph is a set of nodes (x, y, theta) and
+ * edges; one edge is exactly a g2o `EDGE_SE2 a b ...` line as this project writes it (replay._g2o_edge): for a node's own edge a is the
+ * node's index and b its `prev`, for a cfear_keyframe_edge a is `to` and b is `from`. The error of an edge is expressed in the frame of
+ * a, where the recorded information lives (cfear_keyframe_constraint turns the covariance by the rotation of Tfrom^-1; the form of
+ * Ceres' pose_graph_2d):
+ *   e_xy = R(theta_a)^T (t_b - t_a) - z_xy,  e_th = wrap(theta_b - theta_a - z_th) to [-pi, pi),  F = 1/2 sum_e rho_e(e^T Omega e)
+ * with analytic Jacobians (csrc/pose_graph_dev.h: one function for the host and the device). rho is the identity on edges without
+ * flag bit 0; on edges with it the options' loss (CFEAR_LOSS_NONE, CFEAR_LOSS_HUBER or CFEAR_LOSS_CAUCHY with loss_limit, Ceres'
+ * definitions on the squared norm; any other CFEAR_LOSS_*: CFEAR_ERR_UNSUPPORTED), applied as iteratively reweighted least squares: the
+ * edge's Omega is scaled by rho'(s) at the linearisation point, the reported cost uses rho(s).
+ * The solver: (H + lambda diag(H)) p = -g (diag(H) clamped from below at 1e-6) by conjugate gradients under a block-Jacobi preconditioner
+ * (the inverse of every node's damped 3x3 block); H is never assembled. A step is accepted when the robust cost falls, then lambda <-
+ * max(lambda / 3, 1e-12); otherwise lambda <- min(4 lambda, 1e8). It stops on an accepted step with F - F_new <= function_tolerance * F,
+ * on max|p| < parameter_tolerance (the step is not applied), at the iteration limit, or on a rejected step at the damping limit; CG stops
+ * at |r| <= linear_tolerance * |g| or at its iteration limit. All sums run in a fixed order and there are no floating-point atomics: a
+ * graph's poses and summary are bit-identical from run to run and whatever batch the graph is solved in.
+ * Rules:
+ *   - an edge whose z or info is not finite is skipped and counted in edges_skipped (node records carry inf / NaN information by design);
+ *     the result is that of the graph without it, bit for bit;
+ *   - a == b, or an index outside the edge's graph, is CFEAR_ERR_INVALID: the refusal names graph, edge and field, is made on the host
+ *     before anything is launched, and no output is written;
+ *   - the fixed node keeps its bits; a graph with no usable edge keeps all its poses bit for bit and reports CFEAR_PG_NOTHING_TO_DO;
+ *   - a component that the fixed node does not reach is held by the damping alone (its blocks stay regular): it moves only as far as its
+ *     own edges disagree; theta is not wrapped by the update (the error wraps);
+ *   - an empty graph (0 nodes) in a batch is allowed. */
+typedef struct cfear_pg_edge {       /* 88 bytes */
+  int32_t a, b;          /* node indices inside the edge's graph */
+  int32_t flags;         /* bit 0: the edge is robustified (the options' loss) */
+  int32_t pad_;
+  double z[3];           /* the measurement T_a^-1 * T_b as (x, y, theta) */
+  double info[6];        /* upper triangle of the 3x3 information over (x, y, yaw): xx, xy, xt, yy, yt, tt (replay._g2o_edge's order) */
+} cfear_pg_edge;
+typedef struct cfear_pg_options {    /* 56 bytes */
+  int32_t max_iterations;         /* 50: Levenberg-Marquardt iterations, accepted or not */
+  int32_t max_linear_iterations;  /* 0: 30 x the graph's nodes; CG iterations per solve */
+  int32_t loss;                   /* CFEAR_LOSS_NONE (default), CFEAR_LOSS_HUBER or CFEAR_LOSS_CAUCHY: on edges with flag bit 0 */
+  int32_t pad_;
+  double linear_tolerance;        /* 1e-8 */
+  double function_tolerance;      /* 1e-12 */
+  double parameter_tolerance;     /* 1e-10 */
+  double initial_damping;         /* 1e-4 */
+  double loss_limit;              /* 0.1 */
+} cfear_pg_options;
+enum { CFEAR_PG_CONVERGED_COST = 0, CFEAR_PG_CONVERGED_STEP = 1, CFEAR_PG_ITERATION_LIMIT = 2, CFEAR_PG_DAMPING_LIMIT = 3,
+       CFEAR_PG_NOTHING_TO_DO = 4 };
+typedef struct cfear_pg_summary {    /* 48 bytes, one per graph */
+  double initial_cost, final_cost;  /* F at the poses given and at the poses returned */
+  int32_t iterations;               /* Levenberg-Marquardt iterations run */
+  int32_t accepted;                 /* ... of which accepted */
+  int32_t linear_iterations;        /* CG iterations, summed over the solves */
+  int32_t edges_used, edges_skipped;
+  int32_t termination;              /* CFEAR_PG_* */
+  int32_t status;                   /* 0 */
+  int32_t pad_;
+} cfear_pg_summary;
+void cfear_pg_default_options(cfear_pg_options* options);
+/* n_graphs graphs: graph g owns nodes node_offsets[g] .. node_offsets[g + 1] - 1 of poses_xyt (3 doubles each, in / out) and edges
+ * edge_offsets[g] .. edge_offsets[g + 1] - 1, whose a / b count from the graph's first node. fixed: per graph the node that is held (NULL:
+ * node 0 of every graph). options NULL: the defaults. Host pointers; synchronous; the working memory (30 doubles per node, 16 per edge,
+ * the adjacency lists) comes from the context's pool and is back there on return. The graphs are handed to the workgroups largest
+ * first; no result depends on that. CFEAR_ERR_INVALID (graph, edge and field named; nothing written) for offsets that do not ascend from
+ * 0, a fixed node or an edge index out of range, a == b, or options that are not finite / negative; CFEAR_ERR_UNSUPPORTED for a loss
+ * other than the three above. */
+int cfear_pose_graph_optimize(cfear_ctx* ctx, int n_graphs, const int32_t* node_offsets, const int32_t* edge_offsets, const cfear_pg_edge* edges,
+                              const int32_t* fixed, const cfear_pg_options* options, double* poses_xyt, cfear_pg_summary* summaries);
+/* The graphs of an object's keyframe log, one per sequence, optimised in the same launch: the chain edges (a node's t_be / information
+ * to `prev`, flag bit 0 clear) and the initial poses are read from the recorded nodes on the device - no download -, the caller adds m
+ * records as cfear_odometry_keyframe_edges returned them, of any sequences in any order (they keep their order inside a sequence and
+ * carry flag bit 0); those with success == 0 or status != 0 are left out. Node 0 of every sequence is held. pose_offsets: n_sequences + 1
+ * words, sequence q's poses are poses_out[3 * pose_offsets[q] .. 3 * pose_offsets[q + 1]); capacity: the poses poses_out holds (too few:
+ * CFEAR_ERR_CAPACITY with the offsets written, nothing else); poses_out and summaries NULL with capacity 0: the offsets alone. The result is
+ * cfear_pose_graph_optimize's on the downloaded nodes and edges, bit for bit. Nothing is written to the log or the object: a replay
+ * continued afterwards is byte-identical. CFEAR_ERR_INVALID while recording is off, for an edge whose sequence, to or from lies outside
+ * the log, or to == from (the message names the edge and the field). Synchronous; drains the streams the reading calls drain. */
+int cfear_odometry_keyframe_optimize(cfear_ctx* ctx, cfear_odometry* odo, const cfear_keyframe_edge* edges, int m, const cfear_pg_options* options,
+                                     double* poses_out, int capacity, int32_t* pose_offsets, cfear_pg_summary* summaries);
+/* F of one graph at given poses, host only (no context, no device), through the functions the kernel runs (pose_graph_dev.h); the edges
+ * that are not finite are skipped and counted. used / skipped may be NULL. CFEAR_ERR_INVALID for a null pointer, an index out of range
+ * or a == b; CFEAR_ERR_UNSUPPORTED for a loss other than NONE / HUBER / CAUCHY. */
+int cfear_pose_graph_cost_host(const double* poses_xyt, int n_nodes, const cfear_pg_edge* edges, int n_edges, int loss, double loss_limit,
+                               double* cost, int32_t* used, int32_t* skipped);
+
 /* Filter-kernel timing with HIP events (bench.py roofline leg): enable, run steps, read. filter_seconds is the sum
  * of the durations of the filter launches, each measured on the stream it ran on. The events come from a pool created
  * when profiling is enabled (and grown in blocks), not one hipEventCreate per launch. */

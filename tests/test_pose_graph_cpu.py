@@ -1,0 +1,222 @@
+"""The pose-graph optimiser, the parts that need no device: the C ABI (header, EXPORTS, record sizes, the symbols and the kernel in a library
+built for gfx950), the host cost (cfear_pose_graph_cost_host, the kernel's own functions) against posegraph.cost, the numpy twin's Jacobians
+against central differences, the twin (Levenberg-Marquardt + block-Jacobi CG) against the independent direct solver, the loss on an
+outlier, rebase_trajectory, and that replay's existing outputs are what they were.
+
+The twin against the direct solver on the 12-, 70- and 400-node out-and-back graphs of posegraph.out_and_back (seed = nodes), as the test
+prints it: 7.7e-13 m / 1.7e-13 rad, 3.2e-9 m / 8.1e-11 rad and 1.1e-7 m / 5.1e-10 rad, costs equal to 1e-15 relative. The bound asserted is ten times
+that, 1e-6 m / 1e-8 rad: both solvers stop on their own criteria in a valley whose floor is flat to the cost's rounding (the twin at a
+relative cost decrease of 1e-12, the direct solver where its Newton steps stop shrinking), so they agree to the valley's width, not to
+rounding."""
+import ctypes as C
+import hashlib
+import inspect
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from cfear_radarodometry_code_public_amd import capi, posegraph as pg, replay
+import pose_graph_inputs as pgi
+import test_keyframe_edges_cpu as ke
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_abi_header_exports_and_sizes(hip_lib):
+    txt = open(os.path.join(ROOT, "include", "cfear_hip.h")).read()
+    for name in ("cfear_pose_graph_optimize", "cfear_odometry_keyframe_optimize", "cfear_pose_graph_cost_host", "cfear_pg_default_options"):
+        assert re.search(r"\b(int|void) %s\(" % name, txt), name
+        assert name in capi.EXPORTS and hasattr(hip_lib, name), name
+    out = subprocess.check_output(["nm", "-D", "--defined-only", capi.lib_path()]).decode()
+    assert re.search(r" T cfear_pose_graph_optimize$", out, flags=re.M) and re.search(r" T cfear_odometry_keyframe_optimize$", out, flags=re.M)
+    blob = open(capi.lib_path(), "rb").read()
+    assert b"pose_graph_kernel" in blob and b"pose_graph_prep_kernel" in blob and b"gfx950" in blob
+    # the records: sizes as the header states them, the numpy dtypes field by field at the ctypes offsets
+    for cname, size, st, dt in (("cfear_pg_edge", 88, capi.PgEdge, capi.PG_EDGE_DTYPE), ("cfear_pg_options", 56, capi.PgOptions, None),
+                                ("cfear_pg_summary", 48, capi.PgSummary, capi.PG_SUMMARY_DTYPE)):
+        assert re.search(r"typedef struct %s \{\s*/\* %d bytes" % (cname, size), txt), cname
+        assert C.sizeof(st) == size
+        if dt is not None:
+            assert dt.itemsize == size and [n for n in dt.names] == [f for f, _ in st._fields_]
+            for name in dt.names:
+                assert dt.fields[name][1] == getattr(st, name).offset, name
+    assert capi.PG_EDGE_DTYPE.fields["z"][1] == 16 and capi.PG_EDGE_DTYPE.fields["info"][1] == 40
+    # the defaults the header states
+    o = capi.pg_options()
+    assert (o.max_iterations, o.max_linear_iterations, o.loss) == (50, 0, capi.LOSS_NONE)
+    assert (o.linear_tolerance, o.function_tolerance, o.parameter_tolerance, o.initial_damping, o.loss_limit) == (1e-8, 1e-12, 1e-10, 1e-4, 0.1)
+    m = re.search(r"enum \{ CFEAR_PG_CONVERGED_COST = 0, CFEAR_PG_CONVERGED_STEP = 1, CFEAR_PG_ITERATION_LIMIT = 2, CFEAR_PG_DAMPING_LIMIT = 3,\s*CFEAR_PG_NOTHING_TO_DO = 4 \}", txt)
+    assert m and (capi.PG_CONVERGED_COST, capi.PG_CONVERGED_STEP, capi.PG_ITERATION_LIMIT, capi.PG_DAMPING_LIMIT, capi.PG_NOTHING_TO_DO) == (0, 1, 2, 3, 4)
+    assert hasattr(capi.Context, "pose_graph_optimize") and hasattr(capi.Odometry, "keyframe_optimize")
+
+
+def wrap_graph(seed):
+    """a graph whose headings sit on both sides of +-pi and whose measured rotations are near +-pi"""
+    rng = np.random.default_rng(seed)
+    n = 24
+    x = np.zeros((n, 3))
+    x[:, :2] = rng.normal(size=(n, 2)) * 8.0
+    x[:, 2] = np.where(np.arange(n) % 2 == 0, np.pi - rng.uniform(0.0, 0.05, n), -np.pi + rng.uniform(0.0, 0.05, n))
+    a = rng.integers(0, n, 80)
+    b = (a + rng.integers(1, n, 80)) % n
+    z = rng.normal(size=(80, 3)) * 3.0
+    z[:, 2] = np.where(rng.integers(0, 2, 80) == 0, np.pi - rng.uniform(0.0, 0.01, 80), -np.pi + rng.uniform(0.0, 0.01, 80))
+    z[:8, 2] = [np.pi, -np.pi, np.nextafter(np.pi, 0.0), -np.nextafter(np.pi, 0.0), 0.0, 3.0, -3.0, 1.0]
+    L = rng.normal(size=(80, 3, 3))
+    info = np.einsum("mij,mkj->mik", L, L) * 50.0
+    return x, pg.make_edges(a, b, z, info, (np.arange(80) % 3 == 0).astype(np.int32))
+
+
+def test_host_cost_is_the_twins(hip_lib):
+    for seed in range(4):
+        x, E = wrap_graph(seed)
+        assert np.abs(pg.errors(x, E)[:, 2]).max() > 3.0  # wrapped errors near both ends of [-pi, pi)
+        for loss, limit in ((capi.LOSS_NONE, 0.1), (capi.LOSS_HUBER, 0.7), (capi.LOSS_CAUCHY, 0.7), (capi.LOSS_CAUCHY, 30.0)):
+            c, used, skipped = capi.pose_graph_cost_host(x, E, loss, limit)
+            ref = pg.cost(x, E, loss, limit)
+            assert (used, skipped) == (80, 0) and abs(c - ref) <= 1e-12 * ref, (seed, loss, c, ref)
+    # an edge that is not finite is skipped and counted, by both
+    x, E = wrap_graph(9)
+    E["info"][5, 2] = np.nan
+    E["z"][17, 0] = np.inf
+    c, used, skipped = capi.pose_graph_cost_host(x, E, capi.LOSS_HUBER, 0.5)
+    keep = np.ones(80, dtype=bool)
+    keep[[5, 17]] = False
+    ref = pg.cost(x, E[keep], capi.LOSS_HUBER, 0.5)
+    assert (used, skipped) == (78, 2) and abs(c - ref) <= 1e-12 * ref and abs(pg.cost(x, E, capi.LOSS_HUBER, 0.5) - ref) <= 1e-12 * ref
+    # refusals
+    bad = E.copy(); bad["a"][3] = 24
+    same = E.copy(); same["b"][3] = same["a"][3]
+    for e, loss in ((bad, 0), (same, 0)):
+        with pytest.raises(capi.CfearError, match="rc=-1"):
+            capi.pose_graph_cost_host(x, e, loss)
+    with pytest.raises(capi.CfearError, match="rc=-3"):
+        capi.pose_graph_cost_host(x, E, 5)  # CFEAR_LOSS_TUKEY
+
+
+def test_twin_jacobians_against_central_differences():
+    x, E = wrap_graph(2)
+    E = E[np.abs(np.abs(pg.errors(x, E)[:, 2]) - np.pi) > 1e-3]  # (the error jumps by 2 pi where it wraps: no derivative there)
+    assert len(E) > 40
+    A, B = pg.jacobians(x, E)
+    h = 1e-6
+    worst = 0.0
+    for k, e in enumerate(E):
+        for side, J in ((e["a"], A[k]), (e["b"], B[k])):
+            for c in range(3):
+                xp, xm = x.copy(), x.copy()
+                xp[side, c] += h
+                xm[side, c] -= h
+                d = pg.wrap_pi(pg.errors(xp, E[k:k + 1])[0] - pg.errors(xm, E[k:k + 1])[0]) / (2.0 * h)
+                worst = max(worst, float(np.max(np.abs(d - J[:, c]) / (1.0 + np.abs(J[:, c])))))
+    # central differences of a function with second derivatives of the size of the coordinates (<= 30 m): h^2 * 30 / 6 + eps * 30 / h ~ 1e-8
+    assert worst <= 1e-7, worst
+
+
+@pytest.mark.parametrize("n", [12, 70, 400])
+def test_twin_against_the_direct_solver(n):
+    x0, E, _ = pg.out_and_back(n, seed=n)
+    assert (E["flags"] & 1).sum() >= 8
+    xt, S = pg.optimize(x0, E)
+    xd, info = pg.optimize_direct(x0, E)
+    dxy, dth = pgi.pose_diff(xt, xd)
+    print("nodes", n, "edges", len(E), S, info, "dxy", dxy, "dth", dth)
+    assert S["termination"] in (capi.PG_CONVERGED_COST, capi.PG_CONVERGED_STEP) and S["iterations"] <= 50 and S["edges_used"] == len(E)
+    assert S["final_cost"] < S["initial_cost"] and abs(S["final_cost"] - info["cost"]) <= 1e-9 * info["cost"]
+    assert abs(S["final_cost"] - pg.cost(xt, E)) <= 1e-12 * S["final_cost"] and xt[0].tobytes() == x0[0].tobytes()
+    assert dxy <= 1e-6 and dth <= 1e-8, (dxy, dth)
+
+
+def test_a_gross_outlier_under_the_loss():
+    x0, E, _ = pg.out_and_back(70, seed=70)
+    clean, _ = pg.optimize_direct(x0, E)
+    bad = pgi.with_outlier(x0, E, 5.0, flagged=True)
+    none, _ = pg.optimize(x0, bad, loss=capi.LOSS_NONE)
+    cauchy, Sc = pg.optimize(x0, bad, loss=capi.LOSS_CAUCHY, loss_limit=1.0)
+    huber, _ = pg.optimize(x0, bad, loss=capi.LOSS_HUBER, loss_limit=1.0)
+    d_none, d_cauchy, d_huber = pgi.pose_diff(none, clean)[0], pgi.pose_diff(cauchy, clean)[0], pgi.pose_diff(huber, clean)[0]
+    print("distance to the outlier-free optimum: no loss", d_none, "Huber", d_huber, "Cauchy", d_cauchy)
+    assert d_cauchy < d_none and d_huber < d_none and d_cauchy < 0.5 * d_none
+    # an edge that is not flagged does not see the loss: the same bits under every loss
+    plain = bad.copy()
+    plain["flags"] = 0
+    ref, S0 = pg.optimize(x0, plain, loss=capi.LOSS_NONE)
+    for loss in (capi.LOSS_HUBER, capi.LOSS_CAUCHY):
+        got, S1 = pg.optimize(x0, plain, loss=loss, loss_limit=0.01)
+        assert got.tobytes() == ref.tobytes() and S1 == S0, loss
+    with pytest.raises(ValueError):
+        pg.optimize(x0, bad, loss=3)
+
+
+def test_problem_from_nodes_and_edges(tmp_path):
+    nodes, edges = ke.graph()
+    x, E = pg.problem(nodes, edges)
+    assert x.tobytes() == np.ascontiguousarray(nodes["pose"]).tobytes() and E.dtype == capi.PG_EDGE_DTYPE
+    assert len(E) == 8 + 5 and E["flags"].tolist() == [0] * 8 + [1] * 5  # the edge without success is left out
+    assert E["a"][:8].tolist() == list(range(1, 9)) and E["b"][:8].tolist() == list(range(8)) and E["a"][8:].tolist() == [6, 7, 8, 5, 8] and E["b"][8:].tolist() == [0, 1, 2, 4, 7]
+    # ... one edge per EDGE_SE2 line of the graph's text, number for number
+    lines = [l.split() for l in replay.g2o_text(nodes, edges).splitlines() if l.startswith("EDGE_SE2")]
+    assert len(lines) == len(E)
+    for l, e in zip(lines, E):
+        assert (int(l[1]), int(l[2])) == (e["a"], e["b"]) and [float(v) for v in l[3:6]] == e["z"].tolist() and [float(v) for v in l[6:12]] == e["info"].tolist()
+    # ... and the same problem from the file
+    g = tmp_path / "g.g2o"
+    replay.write_g2o(g, nodes, edges)
+    x2, E2 = pg.problem(replay.read_g2o(g), replay.read_g2o_edges(g))
+    assert x2.tobytes() == x.tobytes() and E2.tobytes() == E.tobytes()
+    edges["status"][0] = -3
+    assert len(pg.problem(nodes, edges)[1]) == 12 and len(pg.problem(nodes)[1]) == 8
+
+
+def test_rebase_trajectory():
+    rng = np.random.default_rng(4)
+    n = 60
+    poses = np.cumsum(rng.normal(size=(n, 3)) * [1.0, 0.3, 0.05], axis=0)
+    sweeps = np.array([0, 3, 4, 9, 20, 21, 40, 59])
+    nodes = np.zeros(len(sweeps), dtype=capi.KEYFRAME_NODE_DTYPE)
+    nodes["index"], nodes["sweep"], nodes["pose"] = np.arange(len(sweeps)), sweeps, poses[sweeps]
+    same = replay.rebase_trajectory(poses, nodes, nodes["pose"])
+    assert np.max(np.abs(same - poses)) <= 8 * np.finfo(float).eps * np.max(np.abs(poses))  # the rounding of one compose
+    opt = nodes["pose"] + rng.normal(size=(len(sweeps), 3)) * [0.5, 0.5, 0.1]
+    out = replay.rebase_trajectory(poses, nodes, opt)
+    assert np.max(np.abs(out[sweeps] - opt)) <= 1e-15 * 60  # at a keyframe: the optimised keyframe
+    for k, s in enumerate(sweeps):  # behind it: the recorded relative motion on the new keyframe
+        for t in range(s, sweeps[k + 1] if k + 1 < len(sweeps) else n):
+            rel_old = pgi.rel(poses[s], poses[t])
+            rel_new = pgi.rel(out[s], out[t])
+            assert np.max(np.abs(rel_old - rel_new)) <= 1e-12, (s, t)
+    # sweeps in front of the first keyframe stay
+    nodes["sweep"][0] = 2
+    assert replay.rebase_trajectory(poses, nodes, opt)[:2].tobytes() == poses[:2].tobytes()
+    with pytest.raises(ValueError):
+        replay.rebase_trajectory(poses, nodes, opt[:-1])
+
+
+def test_stand_alone_host_check_plain_and_under_the_sanitizers():
+    """host/pose_graph_check.cpp: the functions the kernel runs, on the CPU with no library - and once more under ASan / UBSan"""
+    host = os.path.join(ROOT, "cfear_radarodometry_code_public_amd", "host")
+    subprocess.check_call(["make", "-C", host, "pose_graph_check"], stdout=subprocess.DEVNULL)
+    plain = subprocess.run([os.path.join(host, "pose_graph_check")], capture_output=True, text=True)
+    assert plain.returncode == 0 and plain.stdout.splitlines()[-1] == "ok" and "FAILED" not in plain.stdout, plain.stdout + plain.stderr
+    probe = subprocess.run(["g++", "-fsanitize=address,undefined", "-x", "c++", "-", "-o", os.devnull], input="int main() { return 0; }\n", capture_output=True, text=True)
+    if probe.returncode != 0:
+        pytest.skip("no -fsanitize=address,undefined runtime for g++ here: the sanitized run does not happen")
+    subprocess.check_call(["make", "-C", host, "pose_graph_check_san"], stdout=subprocess.DEVNULL)
+    san = subprocess.run([os.path.join(host, "pose_graph_check_san")], capture_output=True, text=True)
+    assert san.returncode == 0 and san.stdout == plain.stdout, san.stdout + san.stderr  # (-O2 and no contraction in both: the same figures)
+
+
+def test_existing_outputs_are_untouched():
+    """the g2o text of the existing crafted graph, byte for byte what the parent wrote; optimise is off unless asked for"""
+    nodes, edges = ke.graph()
+    assert hashlib.sha256(replay.g2o_text(nodes, edges).encode()).hexdigest() == G2O_SHA256
+    sig = inspect.signature(replay.replay_grid)
+    assert sig.parameters["optimise"].default is None and list(sig.parameters)[-1] == "optimise"
+    with pytest.raises(ValueError):
+        replay.replay_grid(np.zeros((1, 4, 8), dtype=np.uint8), [capi.Params()], optimise={})  # needs keyframes: refused before any device is touched
+
+
+G2O_SHA256 = "8cdbe16bcf671fb7485cc452a730bd1d683d4bf25ed25414894e1a8de918a04f"  # of the text the commit before this feature wrote
