@@ -222,6 +222,49 @@ def pose_graph_cost_host(poses, edges, loss=0, loss_limit=0.1):
     return cost.value, used.value, skipped.value
 
 
+# cfear_sc_params / cfear_sc_candidate (include/cfear_hip.h): Scan-Context descriptors and loop candidates by appearance (scan_context.hip).
+# scancontext.py states the definition in numpy
+class ScParams(C.Structure):
+    _fields_ = [("n_rings", C.c_int32), ("n_sectors", C.c_int32), ("value", C.c_int32), ("source", C.c_int32), ("min_index_gap", C.c_int32),
+                ("n_keys", C.c_int32), ("max_per_node", C.c_int32), ("pad_", C.c_int32), ("max_range", C.c_double), ("max_distance", C.c_double)]
+
+    def __repr__(self):
+        return "ScParams(%s)" % ", ".join("%s=%r" % (f, getattr(self, f)) for f, _ in self._fields_ if f != "pad_")
+
+
+class ScCandidate(C.Structure):
+    _fields_ = [("sequence", C.c_int32), ("to", C.c_int32), ("from", C.c_int32), ("shift", C.c_int32), ("distance", C.c_double), ("yaw", C.c_double),
+                ("key_distance", C.c_uint64)]
+
+
+SC_CANDIDATE_DTYPE = np.dtype([("sequence", "i4"), ("to", "i4"), ("from", "i4"), ("shift", "i4"), ("distance", "f8"), ("yaw", "f8"), ("key_distance", "u8")])
+assert SC_CANDIDATE_DTYPE.itemsize == C.sizeof(ScCandidate) == 40 and C.sizeof(ScParams) == 48
+SC_MAX, SC_SUM, SC_COUNT = 0, 1, 2  # CFEAR_SC_MAX / CFEAR_SC_SUM / CFEAR_SC_COUNT
+SC_MAX_RINGS, SC_MAX_SECTORS, SC_MAX_KEYS, SC_MAX_PER_NODE, SC_MAX_POINTS = 40, 120, 64, 16, 65536  # CFEAR_SC_MAX_*
+
+
+def sc_params(**kw):
+    """cfear_sc_default_params with fields replaced: n_rings (20), n_sectors (60), max_range (80 m), value (SC_MAX), source (0 = the filtered
+    cloud, 1 = the peaks cloud; the log routes), min_index_gap (6), n_keys (10; 0 = exhaustive), max_per_node (1), max_distance (0.4)"""
+    p = ScParams()
+    lib().cfear_sc_default_params(C.byref(p))
+    for k, v in kw.items():
+        if k == "pad_" or not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def scan_context_layout(params=None, **kw):
+    """cfear_scan_context_layout (host only, no device): the table the kernels read -> (ring_edge2 [n_rings + 1], sector_dir [n_sectors, 2])"""
+    p = params if params is not None else sc_params(**kw)
+    edge, sdir = np.zeros(max(int(p.n_rings), 0) + 1), np.zeros((max(int(p.n_sectors), 1), 2))
+    rc = lib().cfear_scan_context_layout(C.byref(p), edge.ctypes.data, sdir.ctypes.data)
+    if rc != 0:
+        raise CfearError("cfear_scan_context_layout failed rc=%d (%r)" % (rc, p))
+    return edge, sdir
+
+
 KF_NODES, KF_CELLS = 1, 2  # CFEAR_KF_NODES / CFEAR_KF_CELLS
 KF_CLOUD, KF_PEAKS = 4, 8  # CFEAR_KF_CLOUD / CFEAR_KF_PEAKS (cfear_odometry_set_keyframe_clouds)
 STATUS_CELLS_LOST, STATUS_POINTS_LOST, STATUS_KEYFRAMES_DROPPED = 1, 2, 4  # the bits of a sequence's word in cfear_odometry_status
@@ -267,6 +310,8 @@ EXPORTS = [
     "cfear_odometry_keyframe_cells", "cfear_odometry_keyframe_scans", "cfear_odometry_keyframe_edges",
     "cfear_odometry_set_keyframe_clouds", "cfear_odometry_keyframe_cloud_sizes", "cfear_odometry_keyframe_cloud", "cfear_odometry_keyframe_clouds",
     "cfear_pg_default_options", "cfear_pose_graph_optimize", "cfear_odometry_keyframe_optimize", "cfear_pose_graph_cost_host",
+    "cfear_sc_default_params", "cfear_scan_context_layout", "cfear_scan_context_describe", "cfear_scan_context_match",
+    "cfear_odometry_keyframe_descriptors", "cfear_odometry_keyframe_candidates",
     "cfear_drift_segments", "cfear_drift_plan_create", "cfear_drift_plan_release", "cfear_drift_device", "cfear_drift_host",
 ]
 
@@ -383,6 +428,12 @@ def lib():
         "cfear_pose_graph_optimize": (C.c_int, [vp, C.c_int, i32p, i32p, vp, i32p, C.POINTER(PgOptions), f64p, vp]),
         "cfear_odometry_keyframe_optimize": (C.c_int, [vp, vp, vp, C.c_int, C.POINTER(PgOptions), f64p, C.c_int, i32p, vp]),
         "cfear_pose_graph_cost_host": (C.c_int, [f64p, C.c_int, vp, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+        "cfear_sc_default_params": (None, [C.POINTER(ScParams)]),
+        "cfear_scan_context_layout": (C.c_int, [C.POINTER(ScParams), f64p, f64p]),
+        "cfear_scan_context_describe": (C.c_int, [vp, C.POINTER(ScParams), f32p, i32p, C.c_int, u32p, u32p, i32p]),
+        "cfear_scan_context_match": (C.c_int, [vp, C.POINTER(ScParams), C.c_int, i32p, u32p, vp, C.c_int, C.POINTER(C.c_int)]),
+        "cfear_odometry_keyframe_descriptors": (C.c_int, [vp, vp, C.POINTER(ScParams), C.c_int, C.c_int, u32p, u32p, C.c_int, C.POINTER(C.c_int)]),
+        "cfear_odometry_keyframe_candidates": (C.c_int, [vp, vp, C.POINTER(ScParams), vp, C.c_int, C.POINTER(C.c_int)]),
         "cfear_drift_segments": (C.c_int, [f64p, C.c_int, i32p, i32p, i32p, C.c_int, C.POINTER(C.c_int)]),
         "cfear_drift_plan_create": (C.c_int, [vp, f64p, C.c_int, C.POINTER(vp)]),
         "cfear_drift_plan_release": (None, [vp, vp]),
@@ -785,6 +836,42 @@ class Context:
                                                       sums.ctypes.data), "cfear_pose_graph_optimize")
         out = [x[noff[g]:noff[g + 1]].copy() for g in range(len(P))]
         return (out[0] if single else out), sums
+
+    def scan_context(self, clouds, params=None, **kw):
+        """cfear_scan_context_describe: the Scan-Context descriptors of host clouds, a workgroup each in one launch. clouds: a list of [n, 3]
+        arrays (x, y, intensity; a cloud may be empty) or one such array; params: a ScParams, or its fields as keywords (sc_params).
+        -> (bins uint32 [clouds, n_sectors, n_rings], ring_sums uint32 [clouds, n_rings], dropped int32 [clouds]: the points with a field
+        that is not finite); for a single array the three without the leading axis."""
+        single = isinstance(clouds, np.ndarray) and clouds.ndim == 2
+        cl = [np.ascontiguousarray(c, dtype=np.float32).reshape(-1, 3) for c in ([clouds] if single else list(clouds))]
+        p = params if params is not None else sc_params(**kw)
+        off = np.concatenate([[0], np.cumsum([len(c) for c in cl])]).astype(np.int32)
+        xyi = np.ascontiguousarray(np.concatenate(cl, axis=0)) if cl else np.zeros((0, 3), dtype=np.float32)
+        m = len(cl)
+        bins = np.zeros((m, max(int(p.n_sectors), 1), max(int(p.n_rings), 1)), dtype=np.uint32)
+        ring = np.zeros((m, max(int(p.n_rings), 1)), dtype=np.uint32)
+        drop = np.zeros(m, dtype=np.int32)
+        self._check(self._L.cfear_scan_context_describe(self._h, C.byref(p), xyi.ctypes.data if len(xyi) else None, off.ctypes.data, m,
+                                                        bins.ctypes.data if m else None, ring.ctypes.data if m else None, drop.ctypes.data if m else None),
+                    "cfear_scan_context_describe")
+        return (bins[0], ring[0], drop[0]) if single else (bins, ring, drop)
+
+    def scan_context_match(self, descriptor_sets, params=None, **kw):
+        """cfear_scan_context_match: the loop candidates of sets of descriptors, all sets in one launch. descriptor_sets: a list of uint32
+        [n_g, n_sectors, n_rings] arrays (scan_context's bins), one per set, or one such array (a single set). -> SC_CANDIDATE_DTYPE, (set,
+        to, distance) ascending; `sequence` is the set."""
+        single = isinstance(descriptor_sets, np.ndarray) and descriptor_sets.ndim == 3
+        p = params if params is not None else sc_params(**kw)
+        shape = (-1, int(p.n_sectors), int(p.n_rings))
+        S = [np.ascontiguousarray(d, dtype=np.uint32).reshape(shape) for d in ([descriptor_sets] if single else list(descriptor_sets))]
+        off = np.concatenate([[0], np.cumsum([len(d) for d in S])]).astype(np.int32)
+        bins = np.ascontiguousarray(np.concatenate(S, axis=0)) if S else np.zeros((0,) + shape[1:], dtype=np.uint32)
+        cap = int(off[-1]) * int(p.max_per_node)
+        out = np.zeros(max(cap, 1), dtype=SC_CANDIDATE_DTYPE)
+        n = C.c_int()
+        self._check(self._L.cfear_scan_context_match(self._h, C.byref(p), len(S), off.ctypes.data, bins.ctypes.data if len(bins) else None, out.ctypes.data, cap,
+                                                     C.byref(n)), "cfear_scan_context_match")
+        return out[:n.value].copy()
 
     def odometry(self, n_sequences, overlap=None, filter_cus=None, max_cells=None, reg_order=None, large_kernel=None):
         """overlap: None = the context's setting; 0 / False = the three kernels in turn on the context stream; n >= 1 = the filter one
@@ -1245,6 +1332,31 @@ class Odometry:
         sums = np.zeros(self.B, dtype=PG_SUMMARY_DTYPE)
         ctx._check(fn(ctx._h, self._h, ep, len(E), C.byref(opt), x.ctypes.data, int(off[-1]), off.ctypes.data, sums.ctypes.data), "cfear_odometry_keyframe_optimize")
         return [x[off[q]:off[q + 1]].copy() for q in range(self.B)], sums
+
+    def keyframe_descriptors(self, q, params=None, **kw):
+        """cfear_odometry_keyframe_descriptors: the Scan-Context descriptors of every recorded keyframe, from the point log on the device in
+        one launch; those of sequence q come back -> (bins uint32 [n, n_sectors, n_rings], ring_sums uint32 [n, n_rings]). params: a ScParams,
+        or its fields as keywords (source=1: of the peaks clouds). Needs a log with KF_CLOUD. Nothing is written to the log."""
+        p = params if params is not None else sc_params(**kw)
+        fn, ctx = self._ctx._L.cfear_odometry_keyframe_descriptors, self._ctx
+        n = C.c_int()
+        ctx._check(fn(ctx._h, self._h, C.byref(p), int(q), 0, None, None, 0, C.byref(n)), "cfear_odometry_keyframe_descriptors")
+        bins = np.zeros((max(n.value, 1), int(p.n_sectors), int(p.n_rings)), dtype=np.uint32)
+        ring = np.zeros((max(n.value, 1), int(p.n_rings)), dtype=np.uint32)
+        ctx._check(fn(ctx._h, self._h, C.byref(p), int(q), 0, bins.ctypes.data, ring.ctypes.data, n.value, C.byref(n)), "cfear_odometry_keyframe_descriptors")
+        return bins[:n.value], ring[:n.value]
+
+    def keyframe_candidates(self, params=None, **kw):
+        """cfear_odometry_keyframe_candidates: loop candidates by appearance for every sequence of the object - describe and match on the
+        device, no cloud or descriptor comes to the host -> SC_CANDIDATE_DTYPE, (sequence, to, distance) ascending (replay.appearance_jobs
+        turns a sequence's into keyframe_edges jobs). Nothing is written to the log."""
+        p = params if params is not None else sc_params(**kw)
+        fn, ctx = self._ctx._L.cfear_odometry_keyframe_candidates, self._ctx
+        cap = int(self.keyframe_counts()[0].sum()) * int(p.max_per_node)
+        out = np.zeros(max(cap, 1), dtype=SC_CANDIDATE_DTYPE)
+        n = C.c_int()
+        ctx._check(fn(ctx._h, self._h, C.byref(p), out.ctypes.data, cap, C.byref(n)), "cfear_odometry_keyframe_candidates")
+        return out[:n.value].copy()
 
     def keyframe_cloud_sizes(self, q):
         """-> (n_cloud [n], n_peaks [n]): points of the filtered and of the peaks cloud of every recorded node of sequence q"""

@@ -184,6 +184,23 @@ def edge_jobs(sequence, pairs, n_side=0, n_nodes=None):
     return out
 
 
+def appearance_jobs(sequence, candidates, nodes, n_side=0):
+    """The jobs of capi.Odometry.keyframe_edges for the appearance candidates of one sequence (capi.Odometry.keyframe_candidates /
+    scancontext.candidates: SC_CANDIDATE_DTYPE; records of other sequences are passed over): as edge_jobs - the candidate is from[0] and
+    ref, up to n_side neighbours on each side join it - but with a guess (flag bit 0): `to` is placed ON the candidate, at the recorded
+    pose of `from` with the match's yaw added to its angle. The odometry's own pose of `to` is the wrong start exactly when the loop is
+    worth closing: it is off by the drift. nodes: the sequence's KEYFRAME_NODE_DTYPE. -> KEYFRAME_EDGE_JOB_DTYPE. Pure numpy."""
+    cand = np.asarray(candidates, dtype=capi.SC_CANDIDATE_DTYPE).reshape(-1)
+    cand = cand[cand["sequence"] == int(sequence)]
+    out = edge_jobs(sequence, np.stack([cand["from"], cand["to"]], axis=1) if len(cand) else np.zeros((0, 2), dtype=np.int64), n_side, len(nodes))
+    pose = np.asarray(nodes["pose"], dtype=np.float64).reshape(-1, 3)
+    for k, c in enumerate(cand):
+        g = pose[int(c["from"])].copy()
+        g[2] += float(c["yaw"])
+        out[k]["flags"], out[k]["guess_xyt"] = 1, g
+    return out
+
+
 def write_g2o(path, nodes, edges=None):
     """The keyframe graph of one sequence (capi.Odometry.keyframes: KEYFRAME_NODE_DTYPE) as g2o text: `VERTEX_SE2 index x y theta` per
     node and, for every node with a previous one, `EDGE_SE2 index prev dx dy dtheta i11 i12 i13 i22 i23 i33` - the constraint AddToGraph
@@ -350,17 +367,26 @@ def replay_grid(frames, rows, A=None, R=None, gt=None, device=0, piece=256, cont
     edges (with keyframes="cells"): dict(min_index_gap=, max_dist=, n_side=, max_per_node=), each optional - every row's loop_candidates from
     its own nodes, registered as edge_jobs for all rows in ONE Odometry.keyframe_edges call, each row under its own parameters -> `keyframe_edges`:
     per row an array of KEYFRAME_EDGE_DTYPE (what write_g2o takes beside the row's nodes).
+    keyframes="cells+clouds": both logs ("cells" and "clouds" together). With it edges=dict(appearance=dict(<capi.ScParams fields>), n_side=) proposes
+    the loop pairs by appearance instead - all rows' candidates from ONE Odometry.keyframe_candidates call (Scan-Context descriptors of the
+    recorded clouds, no pose involved), registered as appearance_jobs in ONE keyframe_edges call -> `keyframe_candidates` (per row,
+    SC_CANDIDATE_DTYPE) beside `keyframe_edges`.
     optimise (with keyframes): a dict of capi.pg_options fields (may be empty) - every row's graph, its chain and with edges= its loop edges,
     optimised in ONE Odometry.keyframe_optimize call -> `keyframe_poses_optimised`: per row [nodes, 3], `optimise_summaries`
     (capi.PG_SUMMARY_DTYPE [rows]), `poses_optimised` [n, rows, 3]: every row's trajectory carried onto its optimised keyframes
     (rebase_trajectory) and, with gt, `drift_optimised`: its drift beside `drift`, scored the same way. None: nothing of this runs."""
     if drift_on not in ("host", "device"):
         raise ValueError("replay_grid: drift_on is 'host' or 'device'")
-    if keyframes not in (None, "nodes", "cells", "clouds"):
-        raise ValueError("replay_grid: keyframes is None, 'nodes', 'cells' or 'clouds'")
-    if edges is not None and keyframes != "cells":
+    if keyframes not in (None, "nodes", "cells", "clouds", "cells+clouds"):
+        raise ValueError("replay_grid: keyframes is None, 'nodes', 'cells', 'clouds' or 'cells+clouds'")
+    if edges is not None and keyframes not in ("cells", "cells+clouds"):
         raise ValueError("replay_grid: edges need keyframes='cells' (the keyframes are registered from their recorded cells)")
-    if edges is not None and set(edges) - {"min_index_gap", "max_dist", "n_side", "max_per_node"}:
+    if edges is not None and "appearance" in edges:
+        if keyframes != "cells+clouds":
+            raise ValueError("replay_grid: edges by appearance need keyframes='cells+clouds' (the candidates are matched on the recorded clouds)")
+        if set(edges) - {"appearance", "n_side"}:
+            raise ValueError("replay_grid: edges by appearance take appearance (a dict of capi.ScParams fields) and n_side")
+    elif edges is not None and set(edges) - {"min_index_gap", "max_dist", "n_side", "max_per_node"}:
         raise ValueError("replay_grid: edges takes min_index_gap, max_dist, n_side and max_per_node")
     if optimise is not None and keyframes is None:
         raise ValueError("replay_grid: optimise needs keyframes (the graphs are the recorded ones)")
@@ -388,7 +414,8 @@ def replay_grid(frames, rows, A=None, R=None, gt=None, device=0, piece=256, cont
                 raise ValueError("replay_grid: %d option sets for %d rows" % (len(opts), len(rows)))
             odo.set_fuser_options(opts)
         if keyframes is not None:
-            what = capi.KF_NODES | {"nodes": 0, "cells": capi.KF_CELLS, "clouds": capi.KF_CLOUD | capi.KF_PEAKS}[keyframes]
+            what = capi.KF_NODES | {"nodes": 0, "cells": capi.KF_CELLS, "clouds": capi.KF_CLOUD | capi.KF_PEAKS,
+                                    "cells+clouds": capi.KF_CELLS | capi.KF_CLOUD | capi.KF_PEAKS}[keyframes]
             odo.record_keyframes(what, max_keyframes if max_keyframes is not None else n, max_cells if max_cells is not None else 256 * n,
                                  max_points if max_points is not None else n * A * int(cpar.k_strongest))
         recs = [odo.replay_host(frames[t0:t0 + piece, None]) for t0 in range(0, n, piece)]
@@ -397,11 +424,13 @@ def replay_grid(frames, rows, A=None, R=None, gt=None, device=0, piece=256, cont
         graph = None
         if keyframes is not None:
             graph = {"keyframes": [odo.keyframes(q) for q in range(len(rows))], "keyframes_dropped": odo.keyframe_counts()[1]}
-            if keyframes == "cells":
+            if keyframes in ("cells", "cells+clouds"):
                 graph["keyframe_cells"] = [[odo.keyframe_cells(q, i) for i in range(len(nodes))] for q, nodes in enumerate(graph["keyframes"])]
-            if edges is not None:
+            if edges is not None and "appearance" in edges:
+                graph["keyframe_candidates"], graph["keyframe_edges"] = grid_appearance_edges(odo, graph["keyframes"], edges["appearance"], edges.get("n_side", 0))
+            elif edges is not None:
                 graph["keyframe_edges"] = grid_edges(odo, graph["keyframes"], **edges)
-            if keyframes == "clouds":
+            if keyframes in ("clouds", "cells+clouds"):
                 graph["keyframe_clouds"] = [[odo.keyframe_cloud(q, i) for i in range(len(nodes))] for q, nodes in enumerate(graph["keyframes"])]
                 graph["keyframe_peaks"] = [[odo.keyframe_cloud(q, i, peaks=True) for i in range(len(nodes))] for q, nodes in enumerate(graph["keyframes"])]
         rebased = None
@@ -451,6 +480,21 @@ def grid_edges(odo, nodes_per_row, min_index_gap=6, max_dist=3.0, n_side=0, max_
     return [got[cuts[q]:cuts[q + 1]].copy() for q in range(len(jobs))]
 
 
+def grid_appearance_edges(odo, nodes_per_row, appearance=None, n_side=0):
+    """Loop edges by appearance for every sequence of `odo`: the candidates of all sequences from ONE keyframe_candidates call (Scan-Context
+    descriptors of the recorded clouds, matched on the device; appearance: a dict of capi.ScParams fields), as appearance_jobs all of them
+    in ONE keyframe_edges call -> (per sequence its candidates, SC_CANDIDATE_DTYPE; per sequence the edges of its candidates, in their order)"""
+    cand = odo.keyframe_candidates(**(appearance or {}))
+    per_row = [cand[cand["sequence"] == q] for q in range(len(nodes_per_row))]
+    jobs = [appearance_jobs(q, per_row[q], nodes, n_side) for q, nodes in enumerate(nodes_per_row)]
+    count = [len(j) for j in jobs]
+    if sum(count) == 0:
+        return per_row, [np.zeros(0, dtype=capi.KEYFRAME_EDGE_DTYPE) for _ in jobs]
+    got = odo.keyframe_edges(np.concatenate(jobs))
+    cuts = np.cumsum([0] + count)
+    return per_row, [got[cuts[q]:cuts[q + 1]].copy() for q in range(len(jobs))]
+
+
 def sweeps(args):
     if args.bag:
         for kind, t, payload in readers.BagReader(args.bag).sweeps_and_gt(args.image_topic, args.gt_topic):
@@ -495,6 +539,10 @@ def main(argv=None):
     ap.add_argument("--loop_edges", default=None, metavar="GAP,DIST[,SIDE]",
                     help="with --store_graph: also register every keyframe against the keyframes at least GAP nodes earlier and within DIST metres of it "
                          "(loop_candidates; SIDE neighbours on each side of the candidate join it, default 0) in one batch and append the edges to the graph")
+    ap.add_argument("--loop_edges_appearance", default=None, metavar="GAP,MAX_DISTANCE[,SIDE]",
+                    help="with --store_graph: propose the loop pairs by appearance instead of by pose - Scan-Context descriptors of the recorded clouds, matched "
+                         "on the device (Odometry.keyframe_candidates: keyframes at least GAP nodes apart whose descriptor distance is at most MAX_DISTANCE) - "
+                         "register them in one batch with the match's yaw as the guess and append the edges to the graph")
     ap.add_argument("--optimize", action="store_true",
                     help="with --store_graph: optimise the graph - the chain and, with --loop_edges, the loop edges - on the device (Odometry.keyframe_optimize) "
                          "and write the optimised vertices; the edges are written as recorded")
@@ -519,6 +567,16 @@ def main(argv=None):
         if len(w) not in (2, 3):
             ap.error("--loop_edges takes GAP,DIST[,SIDE]")
         loop = dict(min_index_gap=int(w[0]), max_dist=float(w[1]), n_side=int(w[2]) if len(w) == 3 else 0)
+    appearance = None
+    if args.loop_edges_appearance:
+        if not args.store_graph:
+            ap.error("--loop_edges_appearance needs --store_graph (the edges join the graph's nodes)")
+        if args.loop_edges:
+            ap.error("--loop_edges_appearance and --loop_edges propose the same edges in two ways: give one")
+        w = args.loop_edges_appearance.split(",")
+        if len(w) not in (2, 3):
+            ap.error("--loop_edges_appearance takes GAP,MAX_DISTANCE[,SIDE]")
+        appearance = dict(appearance=dict(min_index_gap=int(w[0]), max_distance=float(w[1])), n_side=int(w[2]) if len(w) == 3 else 0)
     cost = {"P2P": 0, "P2L": 1, "P2D": 2}[args.cost_type]
     loss = {"None": 0, "Huber": 1, "Cauchy": 2, "SoftLOne": 3, "Combined": 4, "Tukey": 5}[args.loss_type]
     import time
@@ -563,8 +621,9 @@ def main(argv=None):
             ctx = capi.Context(p, img.shape[0], img.shape[1], device=args.device)
             odo = ctx.odometry(1)
             if args.store_graph:
-                odo.record_keyframes(capi.KF_NODES | (capi.KF_CELLS if loop else 0) | (capi.KF_CLOUD | capi.KF_PEAKS if args.store_clouds else 0), args.max_keyframes,
-                                     args.max_cells if loop else 0, args.max_points)
+                odo.record_keyframes(capi.KF_NODES | (capi.KF_CELLS if loop or appearance else 0) |
+                                     (capi.KF_CLOUD | capi.KF_PEAKS if args.store_clouds or appearance else 0), args.max_keyframes,
+                                     args.max_cells if loop or appearance else 0, args.max_points)
             buf = ctx.pinned((max(1, args.piece), 1, img.shape[0], img.shape[1]))
         buf[fill, 0] = img
         fill += 1
@@ -593,6 +652,10 @@ def main(argv=None):
     if args.store_graph:
         nodes = odo.keyframes(0)
         loop_edges = grid_edges(odo, [nodes], **loop)[0] if loop else None
+        if appearance:
+            cand, per_row = grid_appearance_edges(odo, [nodes], appearance["appearance"], appearance["n_side"])
+            loop_edges = per_row[0]
+            out["appearance_candidates"] = int(len(cand[0]))
         if args.optimize:
             opt, sums = odo.keyframe_optimize(loop_edges, loss={"None": 0, "Huber": 1, "Cauchy": 2}[args.optimize_loss], loss_limit=args.optimize_loss_limit)
             nodes = nodes.copy()
@@ -601,6 +664,8 @@ def main(argv=None):
             out["optimize"]["termination"] = capi.PG_TERMINATION[int(sums[0]["termination"])]
         write_g2o(args.store_graph, nodes, loop_edges)
         out["keyframes"] = int(len(nodes))
+        if appearance:
+            out["loop_edges"] = int(np.count_nonzero(loop_edges["success"]))
         if loop:
             out["loop_candidates"], out["loop_edges"] = int(len(loop_edges)), int(np.count_nonzero(loop_edges["success"]))
         out["keyframes_dropped"] = int(odo.keyframe_counts()[1][0])

@@ -859,6 +859,89 @@ int cfear_odometry_keyframe_optimize(cfear_ctx* ctx, cfear_odometry* odo, const 
 int cfear_pose_graph_cost_host(const double* poses_xyt, int n_nodes, const cfear_pg_edge* edges, int n_edges, int loss, double loss_limit,
                                double* cost, int32_t* used, int32_t* skipped);
 
+/* ---- Loop candidates by appearance: Scan-Context descriptors and their matching on the device (scan_context.hip; Kim & Kim, IROS 2018).
+ * A descriptor is a polar image of a cloud in the sensor frame, bins[sector][ring] (uint32, n_sectors x n_rings, ring fastest), and its
+ * ring key ring_sum[ring] = the sum of bins over the sectors.
+ * Layout: ring_edge2[i] = (i * max_range / n_rings)^2 for i = 0 .. n_rings and sector_dir[j] = (cos, sin)(2 pi j / n_sectors), in double,
+ *   the entries on the four axes exact. The table is computed once on the host (cfear_scan_context_layout); the kernels read it and take
+ *   no cosine themselves.
+ * Bin of a point (x, y, intensity), float32 widened to double, products and sums not contracted:
+ *   - a point with a field that is not finite is skipped and counted in `dropped`; v = clamp(trunc(intensity), 0, 255);
+ *   - r2 = x * x + y * y; r2 >= ring_edge2[n_rings]: out of range, skipped, not counted;
+ *   - ring = #{ i in 1 .. n_rings - 1 : r2 >= ring_edge2[i] };
+ *   - sector = 0 at x == 0 and y == 0; otherwise with cross_j = dir_j.x * y - dir_j.y * x: in the upper half plane (y > 0, or y == 0 and
+ *     x >= 0) #{ j >= 1, 2j < n_sectors : cross_j >= 0 }, in the lower #{ j >= 1 : 2j <= n_sectors } + #{ j : 2j > n_sectors, cross_j >= 0 }.
+ *   bins holds per bin the maximum of v, the sum of v, or the number of points (value). All integers: exact and free of any order. A
+ *   cloud has at most CFEAR_SC_MAX_POINTS points, so every sum stays below 2^24.
+ * Key distance (stage 1): K(a, b) = sum over rings of (ring_sum_a - ring_sum_b)^2 in 64 bits, exact; ties go to the smaller index.
+ * Distance (stage 2): column j of a descriptor is bins[j][.]. For a shift s in 0 .. n_sectors - 1
+ *     d(s) = 1 - (1 / n) sum_j cos(a_j, b_((j + s) mod n_sectors))  over the n columns j where both columns are nonzero, 1 when n = 0;
+ *   distance = min_s d(s), shift = the smallest s that reaches it, yaw = shift * 2 pi / n_sectors in (-pi, pi]. a is `to`, b is `from`,
+ *   and theta_to ~ theta_from + yaw. The device evaluates d in float32 in a fixed order (csrc/scan_context_dev.h): rings ascending with
+ *   fused multiply-adds, columns ascending; a pair's distance is bit-identical whatever batch it is matched in and within
+ *   (n_rings + n_sectors + 8) * 2^-24 of the float64 value.
+ * Candidates of a set of N descriptors (one sequence's keyframes in log order): for every `to` the eligible `from` are 0 .. to -
+ *   min_index_gap; stage 1 keeps the n_keys with the smallest K (all of them for n_keys = 0 or when fewer are eligible); stage 2 takes
+ *   the distance of each; the max_per_node smallest distances <= max_distance are handed back, ties to the smaller `from`. Order of the
+ *   output: set ascending, `to` ascending, then distance. */
+#define CFEAR_SC_MAX 0   /* a bin holds the largest v of its points */
+#define CFEAR_SC_SUM 1   /* ... their sum */
+#define CFEAR_SC_COUNT 2 /* ... their number */
+#define CFEAR_SC_MAX_RINGS 40
+#define CFEAR_SC_MAX_SECTORS 120
+#define CFEAR_SC_MAX_KEYS 64
+#define CFEAR_SC_MAX_PER_NODE 16
+#define CFEAR_SC_MAX_POINTS 65536
+typedef struct cfear_sc_params {     /* 48 bytes */
+  int32_t n_rings;        /* 1 .. 40, 20 */
+  int32_t n_sectors;      /* 1 .. 120, 60 */
+  int32_t value;          /* CFEAR_SC_MAX (default), CFEAR_SC_SUM or CFEAR_SC_COUNT */
+  int32_t source;         /* the log routes: 0 = the filtered cloud of a keyframe (default), 1 = its peaks cloud */
+  int32_t min_index_gap;  /* >= 1, 6 */
+  int32_t n_keys;         /* 0 = every eligible keyframe goes to stage 2, else 1 .. 64; 10 */
+  int32_t max_per_node;   /* 1 .. 16, 1 */
+  int32_t pad_;
+  double max_range;       /* metres, finite and > 0; 80 */
+  double max_distance;    /* in (0, 1]; 0.4 */
+} cfear_sc_params;
+typedef struct cfear_sc_candidate {  /* 40 bytes */
+  int32_t sequence;       /* the set */
+  int32_t to, from;       /* positions in the set, from <= to - min_index_gap */
+  int32_t shift;
+  double distance, yaw;
+  uint64_t key_distance;
+} cfear_sc_candidate;
+void cfear_sc_default_params(cfear_sc_params* params);
+/* The layout table of params (n_rings, n_sectors, max_range), host only: ring_edge2[n_rings + 1], sector_dir[n_sectors][2]. CFEAR_ERR_INVALID
+ * for a null pointer or a field out of range. */
+int cfear_scan_context_layout(const cfear_sc_params* params, double* ring_edge2, double* sector_dir);
+/* Descriptors of n_clouds caller clouds in host memory, a workgroup each in one launch: cloud c is points point_offsets[c] ..
+ * point_offsets[c + 1] - 1 of xyi (x, y, intensity; point_offsets[0] = 0, ascending; a cloud may be empty). bins: n_clouds x n_sectors x
+ * n_rings, ring_sums: n_clouds x n_rings, dropped: n_clouds (the last two may be NULL). params NULL: the defaults. CFEAR_ERR_INVALID, the
+ * field - or the cloud - named and nothing written, for a parameter out of range, offsets that do not ascend from 0 or a cloud of more
+ * than CFEAR_SC_MAX_POINTS points. Synchronous; working memory from the context's pool. */
+int cfear_scan_context_describe(cfear_ctx* ctx, const cfear_sc_params* params, const float* xyi, const int32_t* point_offsets, int n_clouds, uint32_t* bins,
+                                uint32_t* ring_sums, int32_t* dropped);
+/* The candidates of n_sets sets of caller descriptors in one launch: set g owns descriptors set_offsets[g] .. set_offsets[g + 1] - 1 of
+ * bins (as cfear_scan_context_describe wrote them; set_offsets[0] = 0, ascending, a set may be empty). *n: the candidates there are;
+ * more than `capacity`: CFEAR_ERR_CAPACITY and nothing is written to `candidates` (NULL with capacity 0: the count alone). The
+ * candidates of a set do not depend on the other sets of the call. Synchronous. */
+int cfear_scan_context_match(cfear_ctx* ctx, const cfear_sc_params* params, int n_sets, const int32_t* set_offsets, const uint32_t* bins,
+                             cfear_sc_candidate* candidates, int capacity, int* n);
+/* The descriptors of every recorded keyframe of every sequence of the object, from the point log on the device in one launch (params.source:
+ * the filtered or the peaks cloud); those of keyframes first .. of `sequence` are handed back, at most `capacity` (bins / ring_sums as
+ * above, either may be NULL); *n: the keyframes the sequence has recorded. Needs a log with CFEAR_KF_CLOUD, and CFEAR_KF_PEAKS for
+ * source = 1 (CFEAR_ERR_INVALID otherwise). Nothing is written to the log or the object: a replay continued afterwards is byte-identical.
+ * Synchronous; drains the streams the reading calls drain. */
+int cfear_odometry_keyframe_descriptors(cfear_ctx* ctx, cfear_odometry* odo, const cfear_sc_params* params, int sequence, int first, uint32_t* bins,
+                                        uint32_t* ring_sums, int capacity, int* n);
+/* Describe and match in one go: a set per sequence, its recorded keyframes in log order; clouds and descriptors stay on the device.
+ * candidates / capacity / n as cfear_scan_context_match, `sequence` of a record is the sequence. The result is
+ * cfear_scan_context_match's on the descriptors cfear_odometry_keyframe_descriptors hands back, byte for byte. The same conditions, and
+ * as little written to the log. */
+int cfear_odometry_keyframe_candidates(cfear_ctx* ctx, cfear_odometry* odo, const cfear_sc_params* params, cfear_sc_candidate* candidates, int capacity,
+                                       int* n);
+
 /* Filter-kernel timing with HIP events (bench.py roofline leg): enable, run steps, read. filter_seconds is the sum
  * of the durations of the filter launches, each measured on the stream it ran on. The events come from a pool created
  * when profiling is enabled (and grown in blocks), not one hipEventCreate per launch. */
