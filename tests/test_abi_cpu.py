@@ -1,18 +1,60 @@
 """CPU tests of the C-ABI library: it builds for gfx950, loads, exports every symbol declared in
-include/cfear_hip.h, its PODs match the oracle's, and without a GPU it fails loudly (no fallback)."""
+include/cfear_hip.h, its PODs match the oracle's, and without a GPU it fails loudly (no fallback); and of the header's image in abi.py:
+the host C compiler is asked for every record's size and every field's offset and size, for every constant, and the declarations are
+counted against the signature table."""
 import ctypes as C
 import os
 import re
+import subprocess
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+INCLUDE = os.path.join(ROOT, "include")
+
+
+def header_text():
+    """include/cfear_hip.h without its comments"""
+    return re.sub(r"/\*.*?\*/", "", open(os.path.join(INCLUDE, "cfear_hip.h")).read(), flags=re.S)
 
 
 def declared_functions():
-    txt = open(os.path.join(ROOT, "include", "cfear_hip.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(cfear_[a-z_0-9]+)\s*\(", txt)))
+    return sorted(set(re.findall(r"\b(cfear_[a-z_0-9]+)\s*\(", header_text())))
+
+
+def test_records_match_the_header():
+    from cfear_radarodometry_code_public_amd import abi
+    records = [v for v in vars(abi).values() if isinstance(v, type) and issubclass(v, abi.Record) and hasattr(v, "_c_name_")]
+    # no struct of the header without its record
+    assert sorted(r._c_name_ for r in records) == sorted(re.findall(r"typedef struct (cfear_\w+)\s*\{", header_text()))
+    lines = ["#include <stddef.h>", '#include "cfear_hip.h"']
+    for r in records:
+        fields = sorted((getattr(r, f).offset, getattr(r, f).size, f) for f, _ in r._fields_)
+        # the fields tile the record: with equal sizes the header then has no field the record lacks
+        end = 0
+        for off, size, f in fields:
+            assert off == end, (r._c_name_, f, off, end)
+            end = off + size
+        assert end == C.sizeof(r), r._c_name_
+        dt = abi.record_dtype(r)  # ... and its numpy dtype is the same layout
+        assert dt.itemsize == C.sizeof(r) and sorted((dt.fields[f][1], dt.fields[f][0].itemsize, f) for f in dt.names) == fields, r._c_name_
+        lines.append('_Static_assert(sizeof(%s) == %d, "sizeof %s");' % (r._c_name_, C.sizeof(r), r._c_name_))
+        for off, size, f in fields:
+            lines.append('_Static_assert(offsetof(%s, %s) == %d && sizeof(((%s*)0)->%s) == %d, "%s.%s");' % (r._c_name_, f, off, r._c_name_, f, size, r._c_name_, f))
+    for macro, value in abi.HEADER_CONSTANTS.items():
+        lines.append('_Static_assert(%s == %d, "%s");' % (macro, value, macro))
+    cc = subprocess.run(["gcc", "-x", "c", "-std=c11", "-fsyntax-only", "-I", INCLUDE, "-"], input="\n".join(lines) + "\n", capture_output=True, text=True)
+    assert cc.returncode == 0, cc.stderr
+
+
+def test_signatures_match_the_header():
+    from cfear_radarodometry_code_public_amd import abi
+    decls = re.findall(r"(?m)^\s*((?:const\s+)?\w+\s*\**)\s*\b(cfear_[a-z_0-9]+)\s*\(([^)]*)\)\s*;", header_text())
+    assert sorted(name for _, name, _ in decls) == declared_functions() == sorted(abi.SIGNATURES)
+    for result, name, args in decls:
+        res, argtypes = abi.SIGNATURES[name]
+        assert (res is None) == (result.strip() == "void"), name
+        assert len(argtypes) == (0 if args.strip() in ("", "void") else len(args.split(","))), name
 
 
 def test_library_exports_every_declared_symbol(hip_lib):

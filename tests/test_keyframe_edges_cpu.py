@@ -21,10 +21,7 @@ def test_abi_header_exports_and_sizes(hip_lib):
     assert "cfear_odometry_keyframe_edges" in capi.EXPORTS and hasattr(hip_lib, "cfear_odometry_keyframe_edges")
     assert capi.KEYFRAME_EDGE_JOB_DTYPE.itemsize == C.sizeof(capi.KeyframeEdgeJob) == 112
     assert capi.KEYFRAME_EDGE_DTYPE.itemsize == C.sizeof(capi.KeyframeEdge) == 400
-    # the records field by field, as the header lays them out
-    for dt, st, ren in ((capi.KEYFRAME_EDGE_JOB_DTYPE, capi.KeyframeEdgeJob, {"from": "from_"}), (capi.KEYFRAME_EDGE_DTYPE, capi.KeyframeEdge, {"from": "from_"})):
-        for name in dt.names:
-            assert dt.fields[name][1] == getattr(st, ren.get(name, name)).offset, name
+    # (field by field, against the compiled header: test_abi_cpu.test_records_match_the_header)
     assert capi.KEYFRAME_EDGE_JOB_DTYPE.fields["guess_xyt"][1] == 88 and capi.KEYFRAME_EDGE_DTYPE.fields["information"][1] == 112
     # the library is a gfx950 build that exports the entry (and the kernel is in it)
     out = subprocess.check_output(["nm", "-D", "--defined-only", capi.lib_path()]).decode()

@@ -113,12 +113,4 @@ def test_struct_sizes_match_the_dtypes(hip_lib):
     from cfear_radarodometry_code_public_amd import capi
     assert C.sizeof(capi.KeyframeNode) == capi.KEYFRAME_NODE_DTYPE.itemsize == 376
     assert C.sizeof(capi.KeyframeCell) == capi.KEYFRAME_CELL_DTYPE.itemsize == 72
-    for f, _ in capi.KeyframeNode._fields_:
-        assert getattr(capi.KeyframeNode, f).offset == capi.KEYFRAME_NODE_DTYPE.fields[f][1], f
-    for f, _ in capi.KeyframeCell._fields_:
-        assert getattr(capi.KeyframeCell, f).offset == capi.KEYFRAME_CELL_DTYPE.fields[f][1], f
-    # and the header says the same
-    import os
-    import re
-    txt = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "cfear_hip.h")).read()
-    assert re.search(r"}\s*cfear_keyframe_node;\s*/\* 376 bytes \*/", txt) and re.search(r"}\s*cfear_keyframe_cell;\s*/\* 72 bytes \*/", txt)
+    # (field by field, against the compiled header: test_abi_cpu.test_records_match_the_header)
